@@ -1,6 +1,6 @@
 """BICOS hot-path benchmark (driver contract: one JSON line on rank 0).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU, RCCL)
 
 A step = one full BICOS::match of the configured synthetic stereo frame
@@ -20,7 +20,25 @@ previous frame's search leaves idle in its last round of workgroups (narrow row 
 and `ms_per_step` are the throughput over the K steps, and `ms_per_match_one_at_a_time`
 is the latency of one match with nothing overlapping it (this rank's band, no gather).
 
-Extra keys on the JSON line:
+A plain run sets up, warms up, times the K steps, writes its outputs when --dump-outputs
+is given and prints the line: `value`, `ms_per_step` and what describes the run. Everything
+else the bench measures or checks takes runs of its own and needs --full: the one-at-a-time
+latency, the kernel rooflines, the CPU baseline, the host-buffer path, the comparison with
+the published figures, and for N > 1 the gather timed alone and the gathered frames verified
+against the oracle's hashes. Without --full those keys are null.
+
+--dump-outputs DIR: after the timed steps, the maps the last timed step produced -- what a
+caller of the match receives -- are written as DIR/disparity.npy and DIR/corrmap.npy
+(float32; corrmap only with the NXC stage), the whole frame on rank 0. The files hold finite
+numbers only, so that two builds can be compared with plain arithmetic: where a map holds
+NaN (a pixel without a correlation; an invalid pixel of a subpixel disparity map) the file
+holds -32768 in the disparity (the value that marks an invalid pixel in every other disparity
+map) and -2 in the corrmap (outside a correlation's [-1, 1]). Outputs above 60 MB in
+all (cfg5, readme, integ-*) are cut to a fixed, seeded sample of their pixels, the same
+pixels in every run. The synthetic frame is seeded, so two runs with the same arguments
+match the same inputs.
+
+Extra keys on the JSON line (--full):
   roofline      the dominant kernel (the Hamming search), timed live with HIP
                 events on the stream it runs on. Default (matrix-core search,
                 search_mx.hip): algorithmic FP4 MFMA FLOPs per launch (2 x descriptor
@@ -366,6 +384,31 @@ def launch_ranks(world: int) -> int:
     return rc
 
 
+DUMP_LIMIT_BYTES = 60_000_000
+DUMP_SAMPLE_SEED = 0x600DF00D
+# what a NaN of a map (a pixel the match left invalid) is written as: outside the map's range
+DUMP_INVALID = {"disparity": -32768.0, "corrmap": -2.0}
+
+
+def dump_outputs(path, arrays, np):
+    """--dump-outputs: every array as path/<name>.npy in float32 (float64 stays float64).
+    More than DUMP_LIMIT_BYTES in all: each array is cut to the same fraction of its
+    elements, a sample drawn without replacement from a fixed seed (flat indices, sorted).
+    The files hold finite numbers only: a NaN becomes the map's DUMP_INVALID value, an
+    infinity the largest finite number of its sign."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+              for k, a in arrays.items() if a is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = int(a.size * DUMP_LIMIT_BYTES // total)
+            idx = np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, keep, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        a = np.nan_to_num(a, nan=DUMP_INVALID[name])
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -376,7 +419,17 @@ def main():
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="strong: one frame split in row bands; weak: a full frame per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also everything that takes runs of its own: the "
+                         "one-at-a-time latency, the kernel rooflines, the CPU baseline, the "
+                         "host-buffer path, vs_published, and for N > 1 the gather timed alone and "
+                         "the gathered frames verified (off: those keys are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the maps of the last timed step (rank 0: the whole frame) as "
+                         "DIR/disparity.npy and DIR/corrmap.npy, float32; a fixed seeded sample "
+                         "of the pixels when they exceed 60 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
                     help="target wall time of the CPU baseline sample")
     ap.add_argument("--kernel-reps", type=int, default=10)
@@ -390,7 +443,7 @@ def main():
                          "(band 0 of 8: cfg5 0.2140-0.2146 vs 0.2244-0.2281 ms with 3, cfg2 within "
                          "1 %%; profiles/bands_inflight_r05.jsonl)")
     ap.add_argument("--no-host-path", action="store_true",
-                    help="skip the end-to-end host-buffer measurement (rank 0, N=1)")
+                    help="--full without the end-to-end host-buffer measurement (rank 0, N=1)")
     ap.add_argument("--selftest-launch", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (production); gloo = rehearsal of the N>1 "
@@ -398,7 +451,7 @@ def main():
     ap.add_argument("--verify-gather", action="store_true",
                     help="(default; kept for old command lines) verify the gathered frames")
     ap.add_argument("--no-verify-gather", action="store_true",
-                    help="skip the untimed check of the gathered frames (by default, after the "
+                    help="--full without the untimed check of the gathered frames (after the "
                          "timed run, NB more steps land over a sentinel and rank 0 checks every "
                          "gather slot's whole frame against the oracle's sha256 in "
                          "tests/golden/frames.json, or a one-GPU match of the whole frame)")
@@ -437,6 +490,8 @@ def main():
     ap.add_argument("--root-load-high-priority", action="store_true",
                     help="--root-load: the ingress stream at high priority")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without torchrun: start the N ranks ourselves, before
         # this process touches torch or HIP (no exec from a GPU-initialised process)
@@ -763,12 +818,29 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- after the timed region: the gather alone, then the gathered frames verified
+    if args.dump_outputs and rank == 0:
+        # the maps of the last timed step: its frame slot's buffers, or with the gather the
+        # frame that landed on rank 0 (every band cut to its rows)
+        k_last = state["k"] - 1
+        if gather:
+            i = k_last % NB
+            dmap = (frame_disps[i] if i16 else disp_view(recv_all[i])).cpu().numpy()
+            cmap = corr_view(recv_all[i]).cpu().numpy() if has_corr else None
+            heights = [band_rows(H, world, r) for r in range(world)]
+            dmap = np.concatenate([dmap[r, :re_ - rb] for r, (rb, re_) in enumerate(heights)])
+            if has_corr:
+                cmap = np.concatenate([cmap[r, :re_ - rb] for r, (rb, re_) in enumerate(heights)])
+        else:
+            dmap = outs[k_last % F].cpu().numpy()
+            cmap = corrs[k_last % F].cpu().numpy() if has_corr else None
+        dump_outputs(args.dump_outputs, {"disparity": dmap, "corrmap": cmap}, np)
+
+    # ---- after the timed region (--full): the gather alone, then the gathered frames verified
     gather_info = None
     verify = None
     if not gather:
         gather_choice = None
-    if gather:
+    if gather and args.full:
         if dma is not None:
             gather_info = time_dma_exchange(dist, torch, dev, rank, world, dma, streams[0], nbytes)
             if nccl:  # the RCCL gather of the same buffers beside it (both timed)
@@ -794,27 +866,27 @@ def main():
     # one match at a time on one stream (this rank's band, no gather): the latency of a
     # frame, reported beside the pipelined throughput
     serial = []
-    for _ in range(3):
+    for _ in range(3 if args.full else 0):
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
         for _ in range(10):
             eng.match(s0, s1, mcfg, out=out, corrmap=corr)
         torch.cuda.synchronize(dev)
         serial.append((time.perf_counter() - t1) / 10 * 1e3)
-    ms_serial = sorted(serial)[1]
+    ms_serial = sorted(serial)[1] if args.full else None
 
     # (--kernel-reps 0: no back-to-back kernel loops -- the PMC passes use it, so every
     # dispatch they count is an in-frame one)
     roof = kernel_roofline(args, C, torch, dev, eng, mcfg, s0, s1, rows, W, n, words, world,
-                           ms_per_step, frames_px) if args.kernel_reps > 0 else None
+                           ms_per_step, frames_px) if args.full and args.kernel_reps > 0 else None
 
     # The CPU baseline runs at N = 1 only (one rank, after its GPU work is done, so every
     # host core is the baseline's); N > 1 lines carry null.
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(C, args.cpu_seconds)
     hp = None
-    if rank == 0 and world == 1 and not args.no_host_path:
+    if args.full and rank == 0 and world == 1 and not args.no_host_path:
         hp = host_path(C, mcfg, reps=5)
 
     if rank == 0:
@@ -845,7 +917,8 @@ def main():
             "warmup_ms": round(warm_ms, 1),
             "ms_per_step": round(ms_per_step, 4),
             "frames_in_flight": F,
-            "ms_per_match_one_at_a_time": round(ms_serial, 4),
+            "full": bool(args.full),
+            "ms_per_match_one_at_a_time": round(ms_serial, 4) if args.full else None,
             "higher_is_better": True,
             "scaling": args.scaling,
             "vs_baseline": None,
@@ -884,7 +957,7 @@ def main():
             "cpu_baseline": cpu,
             "host_path": hp,
         }
-        if "published" in C:
+        if "published" in C and args.full:
             pub = C["published"]
             # the published figures are one match at a time, so the speedup is
             # taken against our one-at-a-time latency; the pipelined throughput is beside it

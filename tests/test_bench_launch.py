@@ -53,7 +53,7 @@ def test_two_rank_gloo_line_has_every_field(gather):
     oracle's whole-frame hash, and a "gloo rehearsal" label (the CPU baseline is an N = 1
     field, null here). gather=dma: the copy-engine gather (rank 1 maps rank 0's receive
     slots through IPC and copies its band into them with hipMemcpyAsync), the same check."""
-    p = _run(["--gpus", "2", "--backend", "gloo", "--gather", gather, "--steps", "3",
+    p = _run(["--gpus", "2", "--backend", "gloo", "--gather", gather, "--steps", "3", "--full",
               "--warmup", "1", "--cpu-seconds", "2", "--kernel-reps", "2", "--no-host-path"],
              timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -90,7 +90,7 @@ def test_rccl_gather_rehearsal(config):
     async RCCL gather issued from the frames' streams, the int16 landing on rank 0, the
     gather timed with HIP events, and every gathered slot verified against the oracle's
     whole-frame hash. What it cannot cover is the transport between distinct GPUs."""
-    p = _run(["--config", config, "--gather-rehearsal", "--steps", "3", "--warmup", "1",
+    p = _run(["--config", config, "--gather-rehearsal", "--steps", "3", "--warmup", "1", "--full",
               "--spinup-ms", "0", "--no-cpu-baseline", "--kernel-reps", "0", "--no-host-path"],
              timeout=110)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -105,3 +105,36 @@ def test_rccl_gather_rehearsal(config):
     v = d["verify_gather"]
     assert v["ok"] and v["slots"] >= 2 and v["bands"] == 1
     assert "frames.json" in v["check"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_frame(tmp_path):
+    """A plain run times its steps and nothing else (the keys --full fills are null), and
+    --dump-outputs writes the maps of the last timed step: cfg1's whole frame, whose sha256
+    the oracle's fixture holds (tests/golden/frames.json). The files are finite: the
+    corrmap's NaN (pixels without a correlation) are written as -2, put back here before
+    hashing; cfg1's disparity map marks invalid pixels with -32768 and has no NaN."""
+    import hashlib
+    import numpy as np
+    out = tmp_path / "dump"
+    p = _run(["--gpus", "1", "--config", "cfg1", "--steps", "3", "--warmup", "1",
+              "--spinup-ms", "0", "--dump-outputs", str(out)], timeout=110)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["full"] is False
+    assert d["unit"] == "Mpix/s" and d["higher_is_better"] is True and d["dtype"] == "u8"
+    for k in ("roofline", "cpu_baseline", "host_path", "ms_per_match_one_at_a_time"):
+        assert d[k] is None, k
+    fx = json.load(open(os.path.join(ROOT, "tests", "golden", "frames.json")))["cfg1"]
+    assert sorted(os.listdir(out)) == ["corrmap.npy", "disparity.npy"]
+    for name in ("disparity", "corrmap"):
+        a = np.load(out / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (fx["H"], fx["W"])
+        assert np.isfinite(a).all(), name
+        if name == "disparity":  # without subpixel (float) of the int16 map: -32768 = invalid
+            assert abs((a != -32768.0).mean() - fx["valid_fraction"]) < 1e-6
+        else:
+            a = np.where(a == -2.0, np.float32(np.nan), a)
+        assert hashlib.sha256(a.tobytes()).hexdigest() == fx[name + "_sha256"], name

@@ -93,3 +93,34 @@ def test_scale_model_prediction_rule(tmp_path):
     o = by[("rccl", 153.0)]
     assert o["predicted_Mpix_s"] == round(1536 * 2048 / (0.072e-3) / 1e6, 0)
     assert o["x_vs_N1"] == round(o["predicted_Mpix_s"] / 8000.0, 2)
+
+
+def test_dump_outputs_writes_float32_and_samples_above_the_limit(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every map as <name>.npy in float32 (int16 disparities widened,
+    float64 kept); above the byte limit every array is cut to the same seeded sample, the same
+    elements in every run, in their order."""
+    d = np.arange(-5, 19, dtype=np.int16).reshape(4, 6)
+    c = np.linspace(0, 1, 24, dtype=np.float32).reshape(4, 6)
+    bench.dump_outputs(str(tmp_path / "a"), {"disparity": d, "corrmap": c, "absent": None}, np)
+    got = np.load(tmp_path / "a" / "disparity.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, d.astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "corrmap.npy"), c)
+    assert not (tmp_path / "a" / "absent.npy").exists()
+    # finite numbers only: NaN -> the map's invalid value, infinities -> the largest finite
+    bad = np.array([[np.nan, 1.0, np.inf, -np.inf]], np.float32)
+    bench.dump_outputs(str(tmp_path / "n"), {"disparity": bad, "corrmap": bad}, np)
+    fmax = np.finfo(np.float32).max
+    assert np.array_equal(np.load(tmp_path / "n" / "disparity.npy"), [[-32768.0, 1.0, fmax, -fmax]])
+    assert np.array_equal(np.load(tmp_path / "n" / "corrmap.npy"), [[-2.0, 1.0, fmax, -fmax]])
+    c64 = c.astype(np.float64)
+    bench.dump_outputs(str(tmp_path / "d"), {"corrmap": c64}, np)
+    assert np.load(tmp_path / "d" / "corrmap.npy").dtype == np.float64
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 96)  # half of the 2 x 96 bytes
+    for name in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / name), {"disparity": d, "corrmap": c}, np)
+    sd, sc = np.load(tmp_path / "b" / "disparity.npy"), np.load(tmp_path / "b" / "corrmap.npy")
+    assert sd.shape == sc.shape == (12,) and sd.nbytes + sc.nbytes <= 96
+    assert np.array_equal(sd, np.load(tmp_path / "c" / "disparity.npy"))
+    assert np.all(np.diff(sd) > 0) and set(sd) <= set(d.astype(np.float32).ravel())
+    idx = (sd + 5).astype(int)  # d is its own flat index - 5
+    assert np.array_equal(sc, c.ravel()[idx])

@@ -94,22 +94,77 @@ def test_pybicos_errors_without_gpu():
         pybicos.match(z, z)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/pybicos"), reason="reference not mounted")
+# A foreign ctypes wrapper in the style of the reference's pybicos/__init__.py, written here
+# from include/bicos_c.h alone: it finds the library as pybicos_c.so beside its own file,
+# declares its own copy of the config struct and only the restypes it needs, and keeps the
+# config behind the pointer BICOS_CreateDefaultConfig returns.
+_FOREIGN_WRAPPER = '''
+import ctypes, enum, os
+import numpy as np
+
+_lib = ctypes.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "pybicos_c.so"))
+
+
+class Precision(enum.Enum):
+    SINGLE = 0
+    DOUBLE = 1
+
+
+class _C(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in ("nxcorr_threshold", "subpixel_step", "min_variance")] + \\
+               [(n, ctypes.c_int) for n in ("mode", "precision", "variant_type", "max_lr_diff", "no_dupes")]
+
+
+_lib.BICOS_CreateDefaultConfig.restype = ctypes.POINTER(_C)
+_lib.BICOS_FreeConfig.argtypes = [ctypes.POINTER(_C)]
+_lib.BICOS_InvalidDisparityFloat.restype = ctypes.c_float
+_lib.BICOS_InvalidDisparityInt16.restype = ctypes.c_int16
+
+
+class Config:
+    def __init__(self):
+        self._c = _lib.BICOS_CreateDefaultConfig()
+
+    def __del__(self):
+        if getattr(self, "_c", None):
+            _lib.BICOS_FreeConfig(self._c)
+
+    nxcorr_threshold = property(lambda self: self._c.contents.nxcorr_threshold)
+    precision = property(lambda self: Precision(self._c.contents.precision))
+
+    @property
+    def variant(self):
+        c = self._c.contents
+        if c.variant_type == 0:
+            return "NoDuplicates"
+        return {"type": "Consistency", "max_lr_diff": c.max_lr_diff, "no_dupes": bool(c.no_dupes)}
+
+    def set_consistency(self, max_lr_diff=1, no_dupes=False):
+        c = self._c.contents
+        c.variant_type, c.max_lr_diff, c.no_dupes = 1, max_lr_diff, 1 if no_dupes else 0
+
+
+def invalid_disparity(dtype):
+    return (_lib.BICOS_InvalidDisparityFloat() if dtype == np.float32
+            else _lib.BICOS_InvalidDisparityInt16())
+'''
+
+
 def test_reference_python_wrapper_drives_our_abi(tmp_path, blib):
-    """The reference's own pybicos/__init__.py, unmodified, loads libbicos_amd.so as its
-    pybicos_c.so and drives the config ABI (the struct layout it assumes is ours)."""
+    """A wrapper written the way the reference's pybicos/__init__.py is (_FOREIGN_WRAPPER)
+    loads libbicos_amd.so as its pybicos_c.so and drives the config ABI (the struct layout
+    it assumes is ours)."""
     pkg = tmp_path / "refpybicos"
     pkg.mkdir()
-    os.symlink("/root/reference/pybicos/__init__.py", pkg / "__init__.py")
+    (pkg / "__init__.py").write_text(_FOREIGN_WRAPPER)
     from libbicos_amd import _lib
     os.symlink(_lib.LIB_PATH, pkg / "pybicos_c.so")
     spec = importlib.util.spec_from_file_location("refpybicos", str(pkg / "__init__.py"),
                                                   submodule_search_locations=[str(pkg)])
     mod = importlib.util.module_from_spec(spec)
-    # the reference locates its library next to abspath(__file__) -- the symlink dir
-    mod.__file__ = str(pkg / "__init__.py")
     spec.loader.exec_module(mod)
     c = mod.Config()
+    assert c.variant == "NoDuplicates"
     c.set_consistency(max_lr_diff=4, no_dupes=True)
     assert c.variant == {"type": "Consistency", "max_lr_diff": 4, "no_dupes": True}
     assert c.precision == mod.Precision.SINGLE and c.nxcorr_threshold == 0.5

@@ -10,7 +10,7 @@ for spec in ${LIBS:-cur head}; do
   # a lib may carry one environment setting: name:VAR=value
   l=${spec%%:*}; ev=; [ "$spec" != "$l" ] && ev=${spec#*:}
   cp build/$l.so libbicos_amd/libbicos_amd.so
-  env $ev timeout -k 10 240 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline --no-host-path \
+  env $ev timeout -k 10 240 python bench.py --full --config $c --steps 20 --warmup 3 --no-cpu-baseline --no-host-path \
     > gpurun_out/abb_${c}_${spec//[:=]/_}_${k}.txt 2>&1 || { cp build/cur.so libbicos_amd/libbicos_amd.so; tail -5 gpurun_out/abb_${c}_${spec//[:=]/_}_${k}.txt; exit 1; }
   python - "$spec" "$c" gpurun_out/abb_${c}_${spec//[:=]/_}_${k}.txt <<'PY'
 import json, sys

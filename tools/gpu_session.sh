@@ -27,17 +27,17 @@ for step in "$@"; do
         smoke) run smoke 400 python -c "import __graft_entry__ as g; g.smoke()" ;;
         pytest) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread ;;
         pytestk) run pytest_gpu 900 python -m pytest tests -m gpu -q ;;
-        bench) run bench 600 python bench.py --steps 20 --warmup 3 ;;
-        benchf) run benchf 600 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-host-path ;;
-        bench3) run bench3 600 python bench.py --config cfg3 --steps 10 --warmup 2 --no-cpu-baseline --no-host-path ;;
+        bench) run bench 600 python bench.py --full --steps 20 --warmup 3 ;;
+        benchf) run benchf 600 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-host-path ;;
+        bench3) run bench3 600 python bench.py --full --config cfg3 --steps 10 --warmup 2 --no-cpu-baseline --no-host-path ;;
         ab1|ab3|ab2|ab4)  # A/B on one box: current lib vs build/alt.so (same bench, interleaved twice)
             c=cfg${step#ab}
             cp libbicos_amd/libbicos_amd.so build/cur.so
             for k in 1 2; do
                 cp build/cur.so libbicos_amd/libbicos_amd.so
-                run ${step}_cur$k 300 python bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline
+                run ${step}_cur$k 300 python bench.py --full --config $c --steps 10 --warmup 2 --no-cpu-baseline
                 cp build/alt.so libbicos_amd/libbicos_amd.so
-                run ${step}_alt$k 300 python bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline
+                run ${step}_alt$k 300 python bench.py --full --config $c --steps 10 --warmup 2 --no-cpu-baseline
             done
             cp build/cur.so libbicos_amd/libbicos_amd.so ;;
         subpix) run subpix 300 python tools/subpix_bench.py ;;
@@ -78,12 +78,12 @@ for step in "$@"; do
             done
             cp build/cur.so libbicos_amd/libbicos_amd.so ;;
         subpix16) run subpix16 300 python tools/subpix_bench.py --depth 2 --ns 8,16,24,33 ;;
-        bench4) run bench4 600 python bench.py --config cfg4 --steps 10 --warmup 2 --no-cpu-baseline --no-host-path ;;
+        bench4) run bench4 600 python bench.py --full --config cfg4 --steps 10 --warmup 2 --no-cpu-baseline --no-host-path ;;
         stagekib)
             for c in cfg5 cfg4f; do for k in 0 40 32; do
-                BICOS_SEARCH_STAGE_KIB=$k run stage_${c}_$k 300 python bench.py --config $c --steps 8 --warmup 2 --no-cpu-baseline --no-host-path
+                BICOS_SEARCH_STAGE_KIB=$k run stage_${c}_$k 300 python bench.py --full --config $c --steps 8 --warmup 2 --no-cpu-baseline --no-host-path
             done; done ;;
-        bench5) run bench5 600 python bench.py --config cfg5 --steps 10 --warmup 2 --no-cpu-baseline --no-host-path ;;
+        bench5) run bench5 600 python bench.py --full --config cfg5 --steps 10 --warmup 2 --no-cpu-baseline --no-host-path ;;
         sweepv) run sweepv_${SC:-cfg2}_${SROWS:-all} 600 python tools/search_sweep.py --config ${SC:-cfg2} ${SROWS:+--rows $SROWS} --variants $SV ;;
         pmcmx) run pmcmx 120 timeout -s KILL 100 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE -d gpurun_out/pmcmx -o run --output-format csv -- python tools/search_sweep.py --rounds 1 --reps 2 --variants ${SV:-64:8:8} ;;
         pmcclk) for c in ${CLKCFG:-cfg2 cfg4}; do
@@ -100,18 +100,18 @@ for step in "$@"; do
         sweep8) run sweep8 600 python tools/search_sweep.py --rows 192 --variants 0:0:0:0,16:2:8:4,16:2:8:8,16:4:8:8 ;;
         sweep48) run sweep48 600 python tools/search_sweep.py --rows 384 --variants 0:0:0:0,16:2:8:2,16:2:8:4,16:2:8:8 && python tools/search_sweep.py --rows 768 --variants 0:0:0:0,16:2:8:1,16:2:8:2,16:2:8:4 && python tools/search_sweep.py --config cfg5 --rows 270 --variants 0:0:0:0,16:2:8:4,16:2:8:8 ;;
         sweep5) run sweep5 600 python tools/search_sweep.py --config cfg5 --rows 270 --variants 0:0:0:0,16:2:8:1,16:2:8:2,16:2:8:4 ;;
-        rehearse2) run rehearse2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --backend gloo --steps 5 --warmup 1 --no-cpu-baseline --no-host-path ;;
+        rehearse2) run rehearse2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --backend gloo --steps 5 --warmup 1 --no-cpu-baseline --no-host-path ;;
         pmcsub) run pmcsub 600 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY GRBM_GUI_ACTIVE -d gpurun_out/pmcsub -o run --output-format csv -- python bench.py --config cfg3 --steps 2 --warmup 1 --no-cpu-baseline --kernel-reps 1 ;;
         prof) run prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-host-path ;;
         pmcf) run pmcf 600 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmcf -o run --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-path --kernel-reps 2 ;;
         pmcw) run pmcw 600 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmcw -o run --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-path --kernel-reps 2 ;;
         pmcs) run pmcs 600 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE -d gpurun_out/pmcs -o run --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-path --kernel-reps 2 ;;
         pmcl) run pmcl 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_ANY SQ_INSTS_VALU_INT32 TCC_HIT_sum TCC_MISS_sum -d gpurun_out/pmcl -o run --output-format csv -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-path --kernel-reps 2 ;;
-        selflaunch2) run selflaunch2 600 python bench.py --gpus 2 --backend gloo --steps 5 --warmup 1 --no-cpu-baseline --no-host-path ;;
+        selflaunch2) run selflaunch2 600 python bench.py --full --gpus 2 --backend gloo --steps 5 --warmup 1 --no-cpu-baseline --no-host-path ;;
         benchcfgs)  # one bench line per BASELINE config at N=1 (cfg2 with the CPU baseline)
-            run bench_cfg2 600 python bench.py --config cfg2 --steps 20 --warmup 3
+            run bench_cfg2 600 python bench.py --full --config cfg2 --steps 20 --warmup 3
             for c in cfg3 cfg4 cfg5 cfg1; do
-                run bench_$c 600 python bench.py --config $c --steps 20 --warmup 3 --no-host-path --cpu-seconds 8
+                run bench_$c 600 python bench.py --full --config $c --steps 20 --warmup 3 --no-host-path --cpu-seconds 8
             done ;;
         profcfg)  # rocprofv3 kernel stats of one config (SC=cfgN)
             run prof_${SC:-cfg2} 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_${SC:-cfg2} -o run --output-format csv -- python bench.py --config ${SC:-cfg2} --steps 10 --warmup 2 --no-cpu-baseline --no-host-path ;;
@@ -134,7 +134,7 @@ for step in "$@"; do
                 for l in cur alt; do
                     cp build/$l.so libbicos_amd/libbicos_amd.so
                     run abtf_${l}$k 300 python tools/ref_kernel_bench.py --stages transform --reps 40
-                    run abtfb_${l}$k 300 python bench.py --config ${SC:-readme} --steps 10 --warmup 2 --no-cpu-baseline --no-host-path
+                    run abtfb_${l}$k 300 python bench.py --full --config ${SC:-readme} --steps 10 --warmup 2 --no-cpu-baseline --no-host-path
                 done
             done
             cp build/cur.so libbicos_amd/libbicos_amd.so ;;
@@ -144,7 +144,7 @@ for step in "$@"; do
                 for c in ${SCS:-cfg2}; do
                     for l in ${LIBS}; do
                         cp build/$l.so libbicos_amd/libbicos_amd.so
-                        run abb_${c}_${l}_$k 300 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline --no-host-path
+                        run abb_${c}_${l}_$k 300 python bench.py --full --config $c --steps 20 --warmup 3 --no-cpu-baseline --no-host-path
                     done
                 done
             done
@@ -168,11 +168,11 @@ for step in "$@"; do
                 run pmc_${c}_b${nb}_mem 150 timeout -s KILL 140 rocprofv3 --pmc TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCP_TA_DATA_STALL_CYCLES_sum TCC_HIT_sum TCC_MISS_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum TD_TC_STALL_sum TD_SPI_STALL_sum GRBM_GUI_ACTIVE SQ_WAVES -d gpurun_out/pmc/${c}__b${nb}__mem -o run --output-format csv -- python bench.py --config $c --band-of $nb --steps 3 --warmup 1 --spinup-ms 0 --kernel-reps 0 --inflight 1 --no-cpu-baseline --no-host-path
             done ;;
         dmag)  # the copy-engine gather rehearsed with gloo ranks sharing the one GPU (IPC-mapped slots, hipMemcpyAsync), 2 and 3 ranks, + the rccl-form rehearsal
-            run dmag2 600 python bench.py --gpus 2 --backend gloo --gather dma --steps 5 --warmup 1 --no-cpu-baseline --no-host-path
-            run dmag3 600 python bench.py --gpus 3 --backend gloo --gather dma --config cfg3 --steps 5 --warmup 1 --no-cpu-baseline --no-host-path
-            run rcclg2 600 python bench.py --gpus 2 --backend gloo --gather rccl --steps 5 --warmup 1 --no-cpu-baseline --no-host-path ;;
+            run dmag2 600 python bench.py --full --gpus 2 --backend gloo --gather dma --steps 5 --warmup 1 --no-cpu-baseline --no-host-path
+            run dmag3 600 python bench.py --full --gpus 3 --backend gloo --gather dma --config cfg3 --steps 5 --warmup 1 --no-cpu-baseline --no-host-path
+            run rcclg2 600 python bench.py --full --gpus 2 --backend gloo --gather rccl --steps 5 --warmup 1 --no-cpu-baseline --no-host-path ;;
         benchg2)  # the N=2 path rehearsed with gloo ranks sharing the one GPU (all line fields)
-            run benchg2 600 python bench.py --gpus 2 --backend gloo --steps 5 --warmup 1 --cpu-seconds 4 ;;
+            run benchg2 600 python bench.py --full --gpus 2 --backend gloo --steps 5 --warmup 1 --cpu-seconds 4 ;;
         tunepipe)  # search geometries that leave wave slots for the other frames' HBM stages
             run tunepipe 600 python tools/frame_pipe_bench.py --ns 1 --streams 1,2,3 --rounds 2 --reps 40 --tunes ${TUNES:-0:0:0:0,64:4:4:48,64:4:4:40,64:4:6:64,64:2:8:64,64:4:8:64} ;;
         refk) run refk 600 python tools/ref_kernel_bench.py --out gpurun_out/ref_kernel_bench.jsonl ;;
@@ -186,7 +186,7 @@ for step in "$@"; do
                         proxy*) extra="--root-load proxy --root-load-wgs ${m#proxy}" ;;
                         *) extra="--root-load $m" ;;
                     esac
-                    run rl_${c}_${RLN:-8}_${m}$k 300 python bench.py --config $c --band-of ${RLN:-8} --inflight ${INFL:-3} --steps 400 --warmup 10 --no-cpu-baseline --no-host-path --kernel-reps 0 $extra
+                    run rl_${c}_${RLN:-8}_${m}$k 300 python bench.py --full --config $c --band-of ${RLN:-8} --inflight ${INFL:-3} --steps 400 --warmup 10 --no-cpu-baseline --no-host-path --kernel-reps 0 $extra
                 done
             done; done ;;
         revprof)  # kernel trace of the random-descriptor searches: kept col1 / full reverse
@@ -196,8 +196,8 @@ for step in "$@"; do
         fuseab)  # agree fused into the search launch vs separate (BICOS_FUSE_AGREE=0), SCS configs, interleaved REPS times
             for k in $(seq ${REPS:-2}); do
                 for c in ${SCS:-cfg2}; do
-                    run fuse_${c}_on$k 300 python bench.py --config $c --steps 40 --warmup 3 --no-cpu-baseline --no-host-path ${BARGS:-}
-                    BICOS_FUSE_AGREE=0 run fuse_${c}_off$k 300 python bench.py --config $c --steps 40 --warmup 3 --no-cpu-baseline --no-host-path ${BARGS:-}
+                    run fuse_${c}_on$k 300 python bench.py --full --config $c --steps 40 --warmup 3 --no-cpu-baseline --no-host-path ${BARGS:-}
+                    BICOS_FUSE_AGREE=0 run fuse_${c}_off$k 300 python bench.py --full --config $c --steps 40 --warmup 3 --no-cpu-baseline --no-host-path ${BARGS:-}
                 done
             done
             run fuseprof 300 rocprofv3 --kernel-trace --stats -d gpurun_out/fuseprof -o run --output-format csv -- python bench.py --config ${SC:-cfg2} --steps 10 --warmup 2 --inflight 1 --no-cpu-baseline --no-host-path --kernel-reps 0 ;;
@@ -206,7 +206,7 @@ for step in "$@"; do
                 for c in ${SCS:-cfg2 cfg5}; do
                     for b in ${BANDS:-8 4}; do
                         for f in ${FLS:-3 4 6}; do
-                            run bandfl_${c}_${b}_f${f}_$k 300 python bench.py --config $c --band-of $b --inflight $f --steps 100 --warmup 5 --no-cpu-baseline --no-host-path --kernel-reps 0
+                            run bandfl_${c}_${b}_f${f}_$k 300 python bench.py --full --config $c --band-of $b --inflight $f --steps 100 --warmup 5 --no-cpu-baseline --no-host-path --kernel-reps 0
                         done
                     done
                 done
@@ -224,8 +224,8 @@ for step in "$@"; do
             run revrand_kept 600 python tools/random_search_bench.py --words 1,2,4 --out gpurun_out/random_search_kept.jsonl
             BICOS_REV_FULL=1 run revrand_full 600 python tools/random_search_bench.py --words 1,2,4 --out gpurun_out/random_search_full.jsonl
             for k in 1 2; do
-                run bench4_kept$k 300 python bench.py --config cfg4 --steps 20 --warmup 3 --no-cpu-baseline --no-host-path
-                BICOS_REV_FULL=1 run bench4_full$k 300 python bench.py --config cfg4 --steps 20 --warmup 3 --no-cpu-baseline --no-host-path
+                run bench4_kept$k 300 python bench.py --full --config cfg4 --steps 20 --warmup 3 --no-cpu-baseline --no-host-path
+                BICOS_REV_FULL=1 run bench4_full$k 300 python bench.py --full --config cfg4 --steps 20 --warmup 3 --no-cpu-baseline --no-host-path
             done ;;
         revprof4)  # cfg4 kernel stats one frame at a time: compacted reverse, full reverse
             run revprof4_kept 300 rocprofv3 --kernel-trace --stats -d gpurun_out/revprof4_kept -o run --output-format csv -- python bench.py --config cfg4 --steps 10 --warmup 2 --inflight 1 --no-cpu-baseline --no-host-path --kernel-reps 0
@@ -234,13 +234,13 @@ for step in "$@"; do
             run randsearch_kept 600 python tools/random_search_bench.py --words 1,2,4 --out gpurun_out/random_search_kept.jsonl
             BICOS_REV_FULL=1 run randsearch_full 600 python tools/random_search_bench.py --words 1,2,4 --out gpurun_out/random_search_full.jsonl
             for k in 1 2; do
-                run bench4_kept$k 300 python bench.py --config cfg4 --steps 20 --warmup 3 --no-cpu-baseline --no-host-path
-                BICOS_REV_FULL=1 run bench4_full$k 300 python bench.py --config cfg4 --steps 20 --warmup 3 --no-cpu-baseline --no-host-path
+                run bench4_kept$k 300 python bench.py --full --config cfg4 --steps 20 --warmup 3 --no-cpu-baseline --no-host-path
+                BICOS_REV_FULL=1 run bench4_full$k 300 python bench.py --full --config cfg4 --steps 20 --warmup 3 --no-cpu-baseline --no-host-path
             done ;;
         benchall)  # one bench line per BASELINE config + the README shape (cfg2 with host path)
-            run bench_cfg2 300 python bench.py --config cfg2 --steps 20 --warmup 3
+            run bench_cfg2 300 python bench.py --full --config cfg2 --steps 20 --warmup 3
             for c in cfg3 cfg4 cfg5 readme cfg1; do
-                run bench_$c 300 python bench.py --config $c --steps 20 --warmup 3 --no-host-path --cpu-seconds 8
+                run bench_$c 300 python bench.py --full --config $c --steps 20 --warmup 3 --no-host-path --cpu-seconds 8
             done ;;
         *) echo "unknown step $step" ;;
     esac

@@ -9,7 +9,7 @@ for r in $(seq ${ROUNDS:-2}); do
   for c in ${SCS:-cfg1 cfg2 cfg3 cfg4 cfg5}; do
     for steps in ${STEPSLIST:-20 200}; do
       for f in ${FLS:-1 2 3}; do
-        timeout -k 10 120 python bench.py --config $c --inflight $f --steps $steps --warmup 3 \
+        timeout -k 10 120 python bench.py --full --config $c --inflight $f --steps $steps --warmup 3 \
             --no-cpu-baseline --no-host-path --kernel-reps 0 > gpurun_out/ifl.txt 2> gpurun_out/ifl.err
         rc=$?
         if [ $rc -ne 0 ]; then echo "STOP rc=$rc ($c F=$f)"; tail -5 gpurun_out/ifl.err; exit $rc; fi

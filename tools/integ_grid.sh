@@ -11,7 +11,7 @@ NS=${*:-6 8 12 16}
 for n in $NS; do
   for s in "" -s25 -s20 -s15 -s10; do
     c=integ-n$n$s
-    timeout -k 10 300 python bench.py --config $c --no-host-path --cpu-seconds 4 \
+    timeout -k 10 300 python bench.py --full --config $c --no-host-path --cpu-seconds 4 \
       > gpurun_out/integ_$c.txt 2>&1 || { tail -5 gpurun_out/integ_$c.txt; exit 1; }
     tail -1 gpurun_out/integ_$c.txt >> "$OUT"
     python - "$c" gpurun_out/integ_$c.txt <<'EOF'

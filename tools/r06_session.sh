@@ -42,7 +42,7 @@ for line in open("gpurun_out/abpk_rand.txt"):
         d = json.loads(line); d["build"], d["round"] = sys.argv[1], int(sys.argv[2]); print(json.dumps(d))
 PY
         for c in cfg1 integ-n6 integ-n8; do
-          timeout -k 10 200 python bench.py --config $c --steps 20 --warmup 3 --no-cpu-baseline --no-host-path \
+          timeout -k 10 200 python bench.py --full --config $c --steps 20 --warmup 3 --no-cpu-baseline --no-host-path \
             --kernel-reps 5 2> gpurun_out/abpk.err | python tools/jl.py gpurun_out/abpk_r06.jsonl build=$l round=$k \
             || { tail gpurun_out/abpk.err; cp build/cur.so libbicos_amd/libbicos_amd.so; exit 1; }
         done
@@ -65,7 +65,7 @@ PY
     abcons2)  # the dense-row criterion (ascending col1) on cfg4 and the random / planted searches
       for k in 1 2; do for v in on nodense; do
         case $v in on) e="";; nodense) e="BICOS_DENSE_ROWS=0";; esac
-        env $e timeout -k 10 200 python bench.py --config cfg4 --steps 40 --warmup 3 --no-cpu-baseline --no-host-path \
+        env $e timeout -k 10 200 python bench.py --full --config cfg4 --steps 40 --warmup 3 --no-cpu-baseline --no-host-path \
           --kernel-reps 10 2> gpurun_out/abcons.err | python tools/jl.py gpurun_out/abcons2_r06.jsonl variant=$v round=$k \
           || { tail gpurun_out/abcons.err; exit 1; }
         env $e timeout -k 10 300 python tools/random_search_bench.py --words 4 --inputs planted_stereo_n33,random_u128 \
@@ -83,18 +83,18 @@ PY
       for k in 1 2; do for v in pk mx; do
         case $v in pk) e="";; mx) e="BICOS_PK128=0";; esac
         for c in cfg2 cfg5 cfg3 readme; do
-          env $e timeout -k 10 200 python bench.py --config $c --steps 40 --warmup 3 --no-cpu-baseline --no-host-path \
+          env $e timeout -k 10 200 python bench.py --full --config $c --steps 40 --warmup 3 --no-cpu-baseline --no-host-path \
             --kernel-reps 10 2> gpurun_out/abpk128.err | python tools/jl.py gpurun_out/abpk128_r06.jsonl variant=$v round=$k \
             || { tail gpurun_out/abpk128.err; exit 1; }
         done
-        env $e timeout -k 10 200 python bench.py --config cfg2 --band-of 8 --steps 200 --warmup 5 --no-cpu-baseline --no-host-path \
+        env $e timeout -k 10 200 python bench.py --full --config cfg2 --band-of 8 --steps 200 --warmup 5 --no-cpu-baseline --no-host-path \
           --kernel-reps 10 2> gpurun_out/abpk128.err | python tools/jl.py gpurun_out/abpk128_r06.jsonl variant=$v round=$k band_of=8 \
           || { tail gpurun_out/abpk128.err; exit 1; }
       done; done ;;
     abcons)  # cfg4: Consistency check in the agree / dense-row reverse search, each switched off
       for k in 1 2; do for v in on nocons nodense off; do
         case $v in on) e="";; nocons) e="BICOS_FUSE_CONS=0";; nodense) e="BICOS_DENSE_ROWS=0";; off) e="BICOS_FUSE_CONS=0 BICOS_DENSE_ROWS=0";; esac
-        env $e timeout -k 10 200 python bench.py --config cfg4 --steps 40 --warmup 3 --no-cpu-baseline --no-host-path \
+        env $e timeout -k 10 200 python bench.py --full --config cfg4 --steps 40 --warmup 3 --no-cpu-baseline --no-host-path \
           --kernel-reps 10 2> gpurun_out/abcons.err | python tools/jl.py gpurun_out/abcons_r06.jsonl variant=$v round=$k \
           || { tail gpurun_out/abcons.err; exit 1; }
       done; done
