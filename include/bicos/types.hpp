@@ -58,6 +58,12 @@ struct Consistency {
 
 using SearchVariant = std::variant<Variant::NoDuplicates, Variant::Consistency>;
 
+// Inclusive disparity window of the search, disparity = left column - right column (the
+// sign of the maps). See Config::disparity_range.
+struct DisparityRange {
+    int min, max;
+};
+
 // The reference's CUDA-build layout (common.hpp:73-82): `precision` sits between `mode` and
 // `variant` and is always declared here (the library is compiled with it, and Config crosses
 // the API by value). A caller written for the reference's CPU build that aggregate-initialises
@@ -71,6 +77,11 @@ struct Config {
     TransformMode mode = TransformMode::LIMITED;
     Precision precision = Precision::SINGLE;
     SearchVariant variant = Variant::NoDuplicates{};
+    // Not in the reference (trailing, so the reference's initialisers still compile): search
+    // only the right columns with min <= col0 - col1 <= max. NoDuplicates then rejects only
+    // minima that repeat inside the window, pixels without a candidate are invalid, and
+    // Consistency's reverse search uses the same window. min > max throws BICOS::Exception.
+    std::optional<DisparityRange> disparity_range = std::nullopt;
 };
 
 class Exception : public std::exception {

@@ -170,6 +170,39 @@ int bicos_match_host(bicos_engine* e, const void* const* stack0, const void* con
                      int rows, int cols, size_t step, int depth, const BicosConfig* cfg,
                      int has_nxcorr, void* disparity, void* corrmap);
 
+/* ------------------------------------------------------- disparity range */
+/* The search restricted to a disparity window (no reference counterpart; BicosConfig is the
+ * reference's ctypes layout and does not grow, so the window is two extra arguments):
+ * min_disparity <= max_disparity, inclusive, disparity = col0 - col1 (left column minus
+ * right column, the sign of the maps). Any pair of ints with min <= max is legal, negative
+ * values included; the window is clamped to the disparities a row holds, [-(cols-1), cols-1],
+ * and one that no pixel can satisfy yields an all-invalid map, not an error. min > max is
+ * BICOS_E_ARG, detected before any HIP call.
+ *   candidates  of the left pixel col0: C(col0) = { col1 : 0 <= col1 < cols and
+ *               min_disparity <= col0 - col1 <= max_disparity }
+ *   search      the reference's bicos_search (include/impl/cpu/bicos.hpp:50-76) over C(col0)
+ *               in ascending col1: the first minimum wins; NoDuplicates invalidates the
+ *               pixel if the minimum cost occurs more than once WITHIN C(col0); an empty
+ *               C(col0) gives an invalid pixel
+ *   consistency the reverse search for col1 runs over { col0 : min_disparity <= col0 - col1
+ *               <= max_disparity } in ascending col0 (the same search with the descriptor
+ *               sets swapped and the window [-max_disparity, -min_disparity]); the
+ *               max_lr_diff check and (col0 + reverse_col0) / 2 - best_col1 are unchanged
+ *               (bicos.hpp:94-106)
+ * The agree / subpixel / min-variance / corrmap stages consume the integer map as always. A
+ * window covering [-(cols-1), cols-1] gives the unrestricted call's maps byte for byte.
+ * These calls always run the windowed matrix-core search (search_range.hip) followed by
+ * separate consistency / agree launches: BICOS_SEARCH=valu and the fused or compacted plans
+ * of bicos_match_plan do not apply to them. Otherwise exactly their unranged twins. */
+int bicos_match_device_range(bicos_engine* e, const void* stack0, const void* stack1, int n,
+                             int rows, int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                             const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                             int max_disparity, void* disparity, void* corrmap, void* stream);
+int bicos_match_host_range(bicos_engine* e, const void* const* stack0, const void* const* stack1,
+                           int n, int rows, int cols, size_t step, int depth,
+                           const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                           int max_disparity, void* disparity, void* corrmap);
+
 /* ------------------------------------------------ single-process multi-GPU */
 /* One frame matched on several GPUs from one process (the reference has
  * no multi-GPU API -- these extend bicos_match_host / bicos_match_device, whose conventions
@@ -219,6 +252,12 @@ int bicos_transform_device(const void* stack, int n, int rows, int cols, size_t 
 int bicos_search_device(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1, int rows,
                         int cols, int words, int flags, int max_lr_diff, int16_t* out,
                         void* stream);
+/* bicos_search_device over a disparity window (see "disparity range" above): the same flags,
+ * the used-bits hint in bits 16-24 included. With flags & 2 it needs an engine for the two
+ * maps (NULL: BICOS_E_ARG). */
+int bicos_search_device_range(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1,
+                              int rows, int cols, int words, int flags, int max_lr_diff,
+                              int min_disparity, int max_disparity, int16_t* out, void* stream);
 /* agree: raw int16 disparity -> float32 disparity (+ corrmap); minvar already x n */
 int bicos_agree_device(const int16_t* raw, const void* stack0, const void* stack1, int n, int rows,
                        int cols, size_t row_pitch, size_t plane_pitch, int depth, float threshold,

@@ -60,6 +60,7 @@ EXPORTS = (
     "bicos_desc_pitch", "bicos_transform_device", "bicos_search_device",
     "bicos_agree_device", "bicos_subpixel_device", "bicos_agree_stage_device", "bicos_build_info",
     "bicos_match_plan", "bicos_search_agree_device",
+    "bicos_match_device_range", "bicos_match_host_range", "bicos_search_device_range",
 )
 
 # bicos_match_plan bits (include/bicos_c.h)
@@ -158,10 +159,38 @@ def lib() -> ctypes.CDLL:
     L.bicos_search_agree_device.argtypes = [P, P, P, P, P, I, I, I, Z, Z, I,
                                             ctypes.POINTER(BicosConfig), I, P, P, P]
     L.bicos_search_agree_device.restype = I
+    L.bicos_match_device_range.argtypes = [P, P, P, I, I, I, Z, Z, I, ctypes.POINTER(BicosConfig),
+                                           I, I, I, P, P, P]
+    L.bicos_match_device_range.restype = I
+    L.bicos_match_host_range.argtypes = [P, PP, PP, I, I, I, Z, I, ctypes.POINTER(BicosConfig), I,
+                                         I, I, P, P]
+    L.bicos_match_host_range.restype = I
+    L.bicos_search_device_range.argtypes = [P, P, P, I, I, I, I, I, I, I, P, P]
+    L.bicos_search_device_range.restype = I
     L.bicos_build_info.restype = ctypes.c_char_p
     L.bicos_build_info.argtypes = []
     _lib = L
     return L
+
+
+def check_disparity_range(rng):
+    """None, or (lo, hi) as two ints with lo <= hi (ValueError otherwise): the inclusive
+    disparity window of the *_range entry points (include/bicos_c.h)."""
+    if rng is None:
+        return None
+    try:
+        lo, hi = rng
+    except (TypeError, ValueError):
+        raise ValueError("disparity_range must be None or a pair (lo, hi)") from None
+    for v in (lo, hi):
+        if isinstance(v, bool) or not hasattr(v, "__index__"):
+            raise ValueError("disparity_range bounds must be integers, got %r" % (v,))
+    lo, hi = int(lo), int(hi)
+    if lo > hi:
+        raise ValueError("disparity_range: lo %d exceeds hi %d" % (lo, hi))
+    if not (-2 ** 31 <= lo and hi < 2 ** 31):
+        raise ValueError("disparity_range bounds must fit a C int")
+    return lo, hi
 
 
 def check(rc: int, what: str = "bicos") -> None:

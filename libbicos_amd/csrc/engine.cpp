@@ -130,7 +130,9 @@ static bool fuse_consistency() {
 
 // Search implementation: the matrix-core search (search_mx.hip) unless the engine is tuned
 // to the VALU search (bicos_engine_tune variant 16) or BICOS_SEARCH=valu;
-// BICOS_SEARCH=mx forces it. Results are identical either way.
+// BICOS_SEARCH=mx forces it. Results are identical either way. Neither switch applies to a
+// call with a disparity range: the windowed search exists on the matrix cores only
+// (search_range.hip).
 bool use_mx(const bicos_engine* e) {
     static const int env = [] {
         const char* v = std::getenv("BICOS_SEARCH");
@@ -170,6 +172,14 @@ int subpixel_steps(float step) {
     for (float x = -1.f; x <= 1.f; x += step)
         if (++count > MAX_SUBPIXEL_STEPS) return 0;
     return count;
+}
+
+int check_range(int min_disparity, int max_disparity) {
+    if (min_disparity <= max_disparity) return BICOS_OK;
+    std::ostringstream os;
+    os << "disparity range: min_disparity " << min_disparity << " exceeds max_disparity "
+       << max_disparity;
+    return fail(BICOS_E_ARG, os.str());
 }
 
 static int required_bits(int n, int mode) { return mode ? n * n - 2 * n + 3 : 4 * n - 7; }
@@ -235,7 +245,7 @@ static int stack_span(int n, int rows, int cols, size_t row_pitch, size_t plane_
 // kernels after the transform. Valid configurations only (match_device validates first).
 int match_plan(const bicos_engine* e, int n, int rows, int cols, size_t row_pitch,
                size_t plane_pitch, int depth, const BicosConfig& cfg, bool has_nxcorr,
-               const void* s0, const void* s1) {
+               const void* s0, const void* s1, bool ranged) {
     const int mode = cfg.mode == 0 ? 0 : 1;
     const int words = descriptor_words(n, mode);
     if (words < 0 || rows <= 0 || cols <= 0) return 0;
@@ -243,11 +253,19 @@ int match_plan(const bicos_engine* e, int n, int rows, int cols, size_t row_pitc
     const bool nodupes = consistency ? cfg.no_dupes != 0 : true;
     const bool has_step = has_nxcorr && cfg.subpixel_step >= 0;
     const bool dbl = cfg.precision != 0;
-    const bool mx = use_mx(e);
+    const bool mx = ranged || use_mx(e);
     // the LDS-staged agree kernels read the left planes with dword loads
     const bool aligned4 = ((row_pitch * depth | plane_pitch * depth) & 3) == 0 &&
                           (((uintptr_t)s0 | (uintptr_t)s1) & 3) == 0;
     int plan = 0;
+    if (ranged) {
+        // the windowed search (search_range.hip) and separate launches: the fused and
+        // compacted plans are specialised to the full-row kernels' shapes
+        plan |= BICOS_PLAN_MATRIX_CORES;
+        if (consistency && has_nxcorr && !has_step && aligned4 && n <= 65 && fuse_consistency())
+            plan |= BICOS_PLAN_CONSISTENCY_IN_AGREE;
+        return plan;
+    }
     if (mx) {
         plan |= BICOS_PLAN_MATRIX_CORES;
         const bicos_hip::MxGeometry g = mx_geometry(e, rows, cols, words, used_bits(n, mode));
@@ -273,7 +291,10 @@ int match_plan(const bicos_engine* e, int n, int rows, int cols, size_t row_pitc
 int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int rows, int cols,
                  size_t row_pitch, size_t plane_pitch, int depth, const BicosConfig& cfg,
                  bool has_nxcorr, float threshold, void* disp, void* corr, hipStream_t st,
-                 bool disp_i16, const uint32_t* ext_d0, const uint32_t* ext_d1) {
+                 bool disp_i16, const uint32_t* ext_d0, const uint32_t* ext_d1,
+                 const DispRange* range) {
+    if (range)
+        if (int rc0 = check_range(range->min, range->max)) return rc0;
     if (!e) return fail(BICOS_E_ARG, "null engine");
     if (n < 2) return fail(BICOS_E_ARG, "need at least two images");
     if (depth != 1 && depth != 2)
@@ -310,7 +331,7 @@ int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int row
     const bool mx = use_mx(e);
 
     const int plan = match_plan(e, n, rows, cols, row_pitch, plane_pitch, depth, cfg, has_nxcorr,
-                                s0, s1);
+                                s0, s1, range != nullptr);
     // workspace: desc0 | desc1 | raw int16 | fwd | rev (Consistency); the descriptors are the
     // caller's when given (bicos_search_agree_device: the match past its transform)
     const size_t dpitch = bicos_desc_pitch(cols, words);
@@ -356,12 +377,24 @@ int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int row
     // over only the col1 the forward search kept (reverse_search), then the left-right check
     auto search = [&](const uint32_t* a0, const uint32_t* a1, int16_t* out, int out_mode,
                       bool nd, const char* what, const int16_t* keep = nullptr,
-                      uint8_t* row_valid = nullptr) {
+                      uint8_t* row_valid = nullptr, bool reverse = false) {
         bicos_hip::SearchArgs sa{a0, a1, out, rows, cols, dpitch, (size_t)cols, out_mode, 0, 0, 0};
         sa.keep = keep;
         sa.keep_pitch = (size_t)cols;
         sa.row_valid = row_valid;
         sa.valid_pitch = vpitch;
+        if (range) {
+            // bounds beyond +-cols are equivalent to +-cols (and safe to negate); the reverse
+            // search swaps the roles of the columns: its window is [-max, -min]
+            const int lo = std::min(std::max(range->min, -cols), cols);
+            const int hi = std::min(std::max(range->max, -cols), cols);
+            const bool tuned = e->tune_variant >= 64;
+            return check_hip(bicos_hip::launch_search_range(
+                                 sa, reverse ? -hi : lo, reverse ? -lo : hi, words, nd,
+                                 used_bits(n, mode), e->cus, st, tuned ? e->tune_R : 0,
+                                 tuned ? e->tune_waves : 0),
+                             what);
+        }
         if (mx)
             return check_hip(bicos_hip::launch_search_mx(
                                  sa, mx_geometry(e, rows, cols, words, used_bits(n, mode)), words, nd, st),
@@ -410,7 +443,7 @@ int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int row
         rc = search(d0, d1, fwd, 1, nodupes, "search launch", nullptr, valid);
         if (!rc)
             rc = search(d1, d0, rev, 1, nodupes, "reverse search launch",
-                        (plan & BICOS_PLAN_REVERSE_COMPACTED) ? fwd : nullptr, valid);
+                        (plan & BICOS_PLAN_REVERSE_COMPACTED) ? fwd : nullptr, valid, true);
         if (rc) return rc;
         if (plan & BICOS_PLAN_CONSISTENCY_IN_AGREE) {
             // the left-right check runs inside the agree (kernels.hip agree_lds_kernel CONS)
@@ -489,7 +522,9 @@ void HostPool::run(int tasks, const std::function<void(int)>& f) {
 int match_host(bicos_engine* e, const void* const* p0, const size_t* steps0,
                const void* const* p1, const size_t* steps1, int n, int rows, int cols,
                int depth, const BicosConfig& cfg, bool has_nxcorr, float threshold, void* disp,
-               void* corr) {
+               void* corr, const DispRange* range) {
+    if (range)
+        if (int rc0 = check_range(range->min, range->max)) return rc0;
     if (!e) return fail(BICOS_E_ARG, "null engine");
     if (n < 2) return fail(BICOS_E_ARG, "need at least two images");
     if (depth != 1 && depth != 2)
@@ -499,7 +534,7 @@ int match_host(bicos_engine* e, const void* const* p0, const size_t* steps0,
     if (rows == 0 || cols == 0)  // validates the configuration, no work
         return match_device(e, nullptr, nullptr, n, rows, cols, (size_t)cols,
                             (size_t)rows * cols, depth, cfg, has_nxcorr, threshold, disp, corr,
-                            cs);
+                            cs, false, nullptr, nullptr, range);
     if (!p0 || !p1 || !disp) return fail(BICOS_E_ARG, "null buffer");
     const size_t row_bytes = (size_t)cols * depth;
     for (int t = 0; t < n; ++t) {
@@ -679,7 +714,8 @@ int match_host(bicos_engine* e, const void* const* p0, const size_t* steps0,
             rc = match_device(e, band, band + (size_t)n * plane, n, br, cols, (size_t)cols,
                               (size_t)br * cols, depth, cfg, has_nxcorr, threshold,
                               dev_disp + (size_t)r0 * cols * dsz,
-                              dev_corr ? dev_corr + (size_t)r0 * cols * csz : nullptr, cs);
+                              dev_corr ? dev_corr + (size_t)r0 * cols * csz : nullptr, cs, false,
+                              nullptr, nullptr, range);
         if (!rc && dl_bands) {  // this band's rows of the maps, as soon as they are matched
             hipStream_t ds = e->dl_stream;
             const size_t od = (size_t)r0 * cols * dsz, oc = (size_t)r0 * cols * csz;
@@ -902,7 +938,9 @@ namespace {
 int match_device_entry(bicos_engine* e, const void* stack0, const void* stack1, int n, int rows,
                        int cols, size_t row_pitch, size_t plane_pitch, int depth,
                        const BicosConfig* cfg, int has_nxcorr, void* disparity, void* corrmap,
-                       void* stream, bool disp_i16) {
+                       void* stream, bool disp_i16, const DispRange* range = nullptr) {
+    if (range)
+        if (int rc0 = check_range(range->min, range->max)) return rc0;
     if (!cfg) return fail(BICOS_E_ARG, "null config");
     if (!e) return fail(BICOS_E_ARG, "null engine");
     try {
@@ -912,7 +950,8 @@ int match_device_entry(bicos_engine* e, const void* stack0, const void* stack1, 
         // reference src/pybicos_c.cpp:59-61: a negative threshold keeps the default 0.5
         const float thr = cfg->nxcorr_threshold >= 0 ? cfg->nxcorr_threshold : 0.5f;
         return match_device(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth, *cfg,
-                            has_nxcorr != 0, thr, disparity, corrmap, (hipStream_t)stream, disp_i16);
+                            has_nxcorr != 0, thr, disparity, corrmap, (hipStream_t)stream, disp_i16,
+                            nullptr, nullptr, range);
     } catch (const std::exception& ex) {
         return fail(BICOS_E_INTERNAL, ex.what());
     } catch (...) {
@@ -927,6 +966,15 @@ int bicos_match_device(bicos_engine* e, const void* stack0, const void* stack1, 
                        void* stream) {
     return match_device_entry(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth, cfg,
                               has_nxcorr, disparity, corrmap, stream, false);
+}
+
+int bicos_match_device_range(bicos_engine* e, const void* stack0, const void* stack1, int n,
+                             int rows, int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                             const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                             int max_disparity, void* disparity, void* corrmap, void* stream) {
+    const DispRange range{min_disparity, max_disparity};
+    return match_device_entry(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth, cfg,
+                              has_nxcorr, disparity, corrmap, stream, false, &range);
 }
 
 int bicos_match_device_i16(bicos_engine* e, const void* stack0, const void* stack1, int n, int rows,
@@ -969,9 +1017,12 @@ int bicos_search_agree_device(bicos_engine* e, const uint32_t* desc0, const uint
     }
 }
 
-int bicos_match_host(bicos_engine* e, const void* const* stack0, const void* const* stack1, int n,
+namespace {
+int match_host_entry(bicos_engine* e, const void* const* stack0, const void* const* stack1, int n,
                      int rows, int cols, size_t step, int depth, const BicosConfig* cfg,
-                     int has_nxcorr, void* disparity, void* corrmap) {
+                     int has_nxcorr, void* disparity, void* corrmap, const DispRange* range) {
+    if (range)
+        if (int rc0 = check_range(range->min, range->max)) return rc0;
     if (!cfg) return fail(BICOS_E_ARG, "null config");
     if (n < 0) return fail(BICOS_E_ARG, "negative stack size");
     try {
@@ -987,12 +1038,29 @@ int bicos_match_host(bicos_engine* e, const void* const* stack0, const void* con
         const float thr = cfg->nxcorr_threshold >= 0 ? cfg->nxcorr_threshold : 0.5f;
         const std::vector<size_t> steps((size_t)n, step ? step : (size_t)(cols > 0 ? cols : 0) * depth);
         return match_host(e, stack0, steps.data(), stack1, steps.data(), n, rows, cols, depth, *cfg,
-                          has_nxcorr != 0, thr, disparity, corrmap);
+                          has_nxcorr != 0, thr, disparity, corrmap, range);
     } catch (const std::exception& ex) {
         return fail(BICOS_E_INTERNAL, ex.what());
     } catch (...) {
         return fail(BICOS_E_INTERNAL, "unknown exception");
     }
+}
+}  // namespace
+
+int bicos_match_host(bicos_engine* e, const void* const* stack0, const void* const* stack1, int n,
+                     int rows, int cols, size_t step, int depth, const BicosConfig* cfg,
+                     int has_nxcorr, void* disparity, void* corrmap) {
+    return match_host_entry(e, stack0, stack1, n, rows, cols, step, depth, cfg, has_nxcorr,
+                            disparity, corrmap, nullptr);
+}
+
+int bicos_match_host_range(bicos_engine* e, const void* const* stack0, const void* const* stack1,
+                           int n, int rows, int cols, size_t step, int depth,
+                           const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                           int max_disparity, void* disparity, void* corrmap) {
+    const DispRange range{min_disparity, max_disparity};
+    return match_host_entry(e, stack0, stack1, n, rows, cols, step, depth, cfg, has_nxcorr,
+                            disparity, corrmap, &range);
 }
 
 int bicos_transform_device(const void* stack, int n, int rows, int cols, size_t row_pitch,
@@ -1075,6 +1143,60 @@ int bicos_search_device(bicos_engine* e, const uint32_t* desc0, const uint32_t* 
         if (rc) return rc;
         rc = check_hip(bicos_hip::launch_search(ra, g, words, nodupes, st), "reverse search launch");
     }
+    if (rc) return rc;
+    bicos_hip::ConsistencyArgs ca{fwd, rev, out, rows, cols, (size_t)cols, max_lr_diff};
+    return check_hip(bicos_hip::launch_consistency(ca, st), "consistency launch");
+}
+
+int bicos_search_device_range(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1,
+                              int rows, int cols, int words, int flags, int max_lr_diff,
+                              int min_disparity, int max_disparity, int16_t* out, void* stream) {
+    if (int rc0 = check_range(min_disparity, max_disparity)) return rc0;
+    if (words != 1 && words != 2 && words != 4 && words != 8)
+        return fail(BICOS_E_ARG, "words must be 1, 2, 4 or 8");
+    if (cols > 32767) return fail(BICOS_E_ARG, "image width exceeds 32767");
+    if ((flags & 2) && !e) return fail(BICOS_E_ARG, "consistency search needs an engine workspace");
+    if (rows <= 0 || cols <= 0) return BICOS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t dpitch = bicos_desc_pitch(cols, words);
+    const bool nodupes = (flags & 1) != 0;
+    const int bits = (flags >> 16) & 0x1FF;  // 0 = all descriptor bits may be set
+    const int cus = e ? e->cus : 256;
+    const bool tuned = e && e->tune_variant >= 64;
+    const int tiles = tuned ? e->tune_R : 0, waves = tuned ? e->tune_waves : 0;
+    // bounds beyond +-cols are equivalent to +-cols (and safe to negate)
+    const int lo = std::min(std::max(min_disparity, -cols), cols);
+    const int hi = std::min(std::max(max_disparity, -cols), cols);
+    if (!(flags & 2)) {
+        bicos_hip::SearchArgs sa{desc0, desc1, out, rows, cols, dpitch, (size_t)cols, 0, 0, 0};
+        return check_hip(bicos_hip::launch_search_range(sa, lo, hi, words, nodupes, bits, cus, st,
+                                                        tiles, waves),
+                         "windowed search launch");
+    }
+    std::lock_guard<std::mutex> lk(e->lock);  // the workspace may be shared (default engine)
+    const size_t map16 = align_up((size_t)rows * cols * 2);
+    int rc = reserve(e->ws, e->ws_bytes, 2 * map16, e->device, st, e->ws_ready);
+    if (rc) return rc;
+    rc = check_hip(hipStreamWaitEvent(st, e->ws_ready, 0), "hipStreamWaitEvent");
+    if (rc) return rc;
+    struct MarkUse {
+        hipEvent_t ev;
+        hipStream_t st;
+        ~MarkUse() { (void)hipEventRecord(ev, st); }
+    } mark{e->ws_ready, st};
+    int16_t* fwd = (int16_t*)e->ws;
+    int16_t* rev = (int16_t*)((char*)e->ws + map16);
+    // forward over [lo, hi]; the reverse search is the same search with the descriptor sets
+    // swapped and the window [-hi, -lo], over every col1 (reference bicos.hpp:94-106)
+    bicos_hip::SearchArgs fa{desc0, desc1, fwd, rows, cols, dpitch, (size_t)cols, 1, 0, 0};
+    bicos_hip::SearchArgs ra{desc1, desc0, rev, rows, cols, dpitch, (size_t)cols, 1, 0, 0};
+    rc = check_hip(bicos_hip::launch_search_range(fa, lo, hi, words, nodupes, bits, cus, st, tiles,
+                                                  waves),
+                   "windowed search launch");
+    if (rc) return rc;
+    rc = check_hip(bicos_hip::launch_search_range(ra, -hi, -lo, words, nodupes, bits, cus, st,
+                                                  tiles, waves),
+                   "windowed reverse search launch");
     if (rc) return rc;
     bicos_hip::ConsistencyArgs ca{fwd, rev, out, rows, cols, (size_t)cols, max_lr_diff};
     return check_hip(bicos_hip::launch_consistency(ca, st), "consistency launch");
@@ -1247,6 +1369,12 @@ void impl::hip::match(const std::vector<Image>& stack0, const std::vector<Image>
     }
     if (cfg.subpixel_step && !(*cfg.subpixel_step > 0))
         throw Exception("subpixel_step must be a positive finite number");
+    bicos_impl::DispRange range{0, 0};
+    if (cfg.disparity_range) {
+        range = {cfg.disparity_range->min, cfg.disparity_range->max};
+        throw_rc(bicos_impl::check_range(range.min, range.max));
+    }
+    const bicos_impl::DispRange* rg = cfg.disparity_range ? &range : nullptr;
     if (cfg.min_variance && *cfg.min_variance < 0) c.min_variance = -1.f;
 
     int dev = 0;
@@ -1273,7 +1401,8 @@ void impl::hip::match(const std::vector<Image>& stack0, const std::vector<Image>
         if (want_corr) corrmap->create(rows, cols, dbl ? F64 : F32, Memory::Host);
         throw_rc(bicos_impl::match_host(e, p0.data(), st0.data(), p1.data(), st1.data(), (int)n,
                                         rows, cols, depth, c, has_nxcorr, c.nxcorr_threshold,
-                                        disparity.data(), want_corr ? corrmap->data() : nullptr));
+                                        disparity.data(), want_corr ? corrmap->data() : nullptr,
+                                        rg));
         return;
     }
 
@@ -1331,7 +1460,8 @@ void impl::hip::match(const std::vector<Image>& stack0, const std::vector<Image>
     if (want_corr) corrmap->create(rows, cols, dbl ? F64 : F32, Memory::Device);
     throw_rc(bicos_impl::match_device(e, s0, s1, (int)n, rows, cols, row_pitch, plane_pitch, depth,
                                       c, has_nxcorr, c.nxcorr_threshold, disparity.data(),
-                                      want_corr ? corrmap->data() : nullptr, st));
+                                      want_corr ? corrmap->data() : nullptr, st, false, nullptr,
+                                      nullptr, rg));
 }
 
 }  // namespace BICOS

@@ -105,20 +105,27 @@ int descriptor_words(int n, int mode);
 
 bicos_hip::SearchGeometry geometry(const bicos_engine* e, int rows, int cols, int words);
 
+// An inclusive disparity window min <= col0 - col1 <= max (bicos_c.h, the *_range entries)
+struct DispRange {
+    int min, max;
+};
+
 // Full match on device buffers (validated arguments). corr may be null. disp_i16: the
 // disparity map is int16 even with the NXC stage (no subpixel; bicos_match_device_i16).
 // ext_d0 / ext_d1: the two stacks' descriptors (transform output, bicos_desc_pitch rows)
 // already computed -- the match then runs from its search on (bicos_search_agree_device).
+// range: the search's disparity window (nullptr: the whole row) -- the windowed matrix-core
+// search (search_range.hip), none of the fused or compacted plans.
 int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int rows, int cols,
                  size_t row_pitch, size_t plane_pitch, int depth, const BicosConfig& cfg,
                  bool has_nxcorr, float threshold, void* disp, void* corr, hipStream_t st,
                  bool disp_i16 = false, const uint32_t* ext_d0 = nullptr,
-                 const uint32_t* ext_d1 = nullptr);
+                 const uint32_t* ext_d1 = nullptr, const DispRange* range = nullptr);
 
 // BICOS_PLAN_* bits of what match_device runs after the transform (bicos_match_plan)
 int match_plan(const bicos_engine* e, int n, int rows, int cols, size_t row_pitch,
                size_t plane_pitch, int depth, const BicosConfig& cfg, bool has_nxcorr,
-               const void* s0, const void* s1);
+               const void* s0, const void* s1, bool ranged = false);
 
 // Host buffers in and out (the reference's cv::Mat path, src/impl/cpu.cpp:100-159): the
 // stacks are uploaded in row bands through pinned slots on a copy stream while earlier
@@ -128,7 +135,10 @@ int match_plan(const bicos_engine* e, int n, int rows, int cols, size_t row_pitc
 int match_host(bicos_engine* e, const void* const* p0, const size_t* steps0,
                const void* const* p1, const size_t* steps1, int n, int rows, int cols,
                int depth, const BicosConfig& cfg, bool has_nxcorr, float threshold, void* disp,
-               void* corr);
+               void* corr, const DispRange* range = nullptr);
+
+// BICOS_E_ARG (with a message) for a window whose min exceeds its max; no HIP call
+int check_range(int min_disparity, int max_disparity);
 
 // Process-wide engine for `device` (created on first use).
 bicos_engine* default_engine(int device);

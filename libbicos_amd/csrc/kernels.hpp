@@ -83,6 +83,14 @@ struct SearchAgreeArgs {
     AgreeArgs ag;
 };
 
+// launch_search_range: the search restricted to the disparity window dmin <= col0 - col1 <=
+// dmax (both within [-cols, cols]). Only the windowed kernels take the two bounds; every
+// other search launch keeps SearchArgs as it is
+struct SearchRangeArgs {
+    SearchArgs s;
+    int dmin, dmax;
+};
+
 struct SearchGeometry {
     int chunk;              // col1 columns per LDS fill
     int waves;              // waves per workgroup
@@ -159,6 +167,16 @@ hipError_t launch_search_mx_agree(SearchArgs a, const AgreeArgs& ag, const MxGeo
 // bits above must be zero) and rows of at most 2048 columns: search_lr_eligible.
 bool search_lr_eligible(int words, int bits, int cols);
 hipError_t launch_search_lr(SearchArgs a, int words, int bits, int max_lr_diff, hipStream_t st);
+// Windowed matrix-core search (search_range.hip): launch_search_mx's outputs (a.out,
+// a.out_mode) with the candidates of col0 restricted to the col1 with dmin <= col0 - col1 <=
+// dmax (inclusive, any dmin <= dmax; clamped to the row's disparities). The first minimum in
+// ascending col1 wins; NoDuplicates rejects a minimum that repeats WITHIN the window; a pixel
+// without candidates is invalid. a.keep / a.row_valid must be null (no compacted col0).
+// bits: as search_mx_geometry's. tiles / waves_wg: 32-col0 tiles per wave (2|4) and waves
+// per workgroup (1..8), 0 = chosen from the shape.
+hipError_t launch_search_range(SearchArgs a, int dmin, int dmax, int words, bool nodupes,
+                               int bits, int cus, hipStream_t st, int tiles = 0,
+                               int waves_wg = 0);
 hipError_t launch_agree(const AgreeArgs& a, int depth, bool dbl, hipStream_t st);
 hipError_t launch_subpixel(const AgreeArgs& a, int depth, bool dbl, hipStream_t st);
 // n > 40 (subpixel_wide.hip); launch_subpixel dispatches to it

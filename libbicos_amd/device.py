@@ -32,8 +32,12 @@ class MatchConfig:
     variant: int = 0           # 0 NoDuplicates, 1 Consistency
     max_lr_diff: int = 1
     no_dupes: bool = False
+    # (lo, hi): search only right columns with lo <= col0 - col1 <= hi (inclusive; bicos_c.h
+    # "disparity range"). Not part of BicosConfig: match() passes it to bicos_match_device_range.
+    disparity_range: Optional[Tuple[int, int]] = None
 
     def to_c(self) -> Tuple[_lib.BicosConfig, int]:
+        _lib.check_disparity_range(self.disparity_range)
         thr = self.nxcorr_threshold
         if thr is not None and not thr >= 0:
             raise ValueError("device API: nxcorr_threshold must be >= 0 or None "
@@ -157,6 +161,16 @@ class Engine:
             corrmap = None
         if corrmap is not None:
             _check_out(corrmap, "corrmap", (rows, cols), (corr_dtype,), dev)
+        rng = _lib.check_disparity_range(cfg.disparity_range)
+        if rng is not None and i16:
+            raise ValueError("disparity_range is not supported with an int16 `out` map")
+        if rng is not None:
+            rc = self._L.bicos_match_device_range(
+                self._h, stack0.data_ptr(), stack1.data_ptr(), n, rows, cols, rp, pp,
+                _depth(stack0), ctypes.byref(c), has_nxcorr, rng[0], rng[1], out.data_ptr(),
+                corrmap.data_ptr() if corrmap is not None else None, _stream(dev, stream))
+            _lib.check(rc, "bicos_match_device_range")
+            return out, corrmap
         entry = self._L.bicos_match_device_i16 if i16 else self._L.bicos_match_device
         rc = entry(
             self._h, stack0.data_ptr(), stack1.data_ptr(), n, rows, cols, rp, pp, _depth(stack0),
@@ -235,9 +249,13 @@ class Engine:
 
     def search(self, desc0: torch.Tensor, desc1: torch.Tensor, cols: int, words: int,
                flags: int = 1, max_lr_diff: int = -1, out: Optional[torch.Tensor] = None,
-               stream=None, bits: int = 0) -> torch.Tensor:
+               stream=None, bits: int = 0,
+               disparity_range: Optional[Tuple[int, int]] = None) -> torch.Tensor:
         """bits: how many low descriptor bits may be set (0 = all; see used_bits) -- the
-        matrix-core search skips the K-steps above them (bicos_c.h flags bits 16-24)."""
+        matrix-core search skips the K-steps above them (bicos_c.h flags bits 16-24).
+        disparity_range: (lo, hi), search only col1 with lo <= col0 - col1 <= hi
+        (bicos_search_device_range)."""
+        rng = _lib.check_disparity_range(disparity_range)
         if not 0 <= bits <= 256:
             raise ValueError("bits must be in [0, 256]")
         flags = (flags & 0xFFFF) | (bits << 16)
@@ -251,6 +269,12 @@ class Engine:
         if out is None:
             out = torch.empty((rows, cols), dtype=torch.int16, device=desc0.device)
         _check_out(out, "out", (rows, cols), (torch.int16,), desc0.device)
+        if rng is not None:
+            rc = self._L.bicos_search_device_range(
+                self._h, desc0.data_ptr(), desc1.data_ptr(), rows, cols, words, flags, max_lr_diff,
+                rng[0], rng[1], out.data_ptr(), _stream(desc0.device, stream))
+            _lib.check(rc, "bicos_search_device_range")
+            return out
         rc = self._L.bicos_search_device(self._h, desc0.data_ptr(), desc1.data_ptr(), rows, cols,
                                          words, flags, max_lr_diff, out.data_ptr(),
                                          _stream(desc0.device, stream))
@@ -315,6 +339,8 @@ def match_bands(bands0: Sequence[torch.Tensor], bands1: Sequence[torch.Tensor],
     corrmap) on bands0[0]'s device, gathered there by peer copies. Synchronous: the work
     queued on every band device's current stream is finished first."""
     cfg = cfg or MatchConfig()
+    if cfg.disparity_range is not None:
+        raise ValueError("disparity_range is not supported with several GPUs yet")
     if len(bands0) == 0 or len(bands0) != len(bands1):
         raise ValueError("need the same number (>= 1) of left and right bands")
     k = len(bands0)

@@ -69,6 +69,7 @@ class Config:
     def __init__(self):
         self._L = _lib.lib()
         self._c_config = self._L.BICOS_CreateDefaultConfig()
+        self._disparity_range = None
 
     def __del__(self):
         if getattr(self, "_c_config", None):
@@ -118,6 +119,17 @@ class Config:
         self._c_config.contents.precision = value.value if isinstance(value, Precision) else value
 
     @property
+    def disparity_range(self):
+        """An extension (the reference scans whole rows): None, or (lo, hi) -- search only the
+        right columns with lo <= left column - right column <= hi, inclusive (include/bicos_c.h
+        "disparity range"). Kept beside the C struct, whose layout is the reference's."""
+        return self._disparity_range
+
+    @disparity_range.setter
+    def disparity_range(self, value):
+        self._disparity_range = _lib.check_disparity_range(value)
+
+    @property
     def variant(self):
         if self._c_config.contents.variant_type == VariantType.NO_DUPLICATES.value:
             return "NoDuplicates"
@@ -144,6 +156,7 @@ class Config:
             f"  mode={self.mode.name}",
             f"  precision={self.precision.name}",
             f"  variant={self.variant}",
+        ] + ([f"  disparity_range={self.disparity_range}"] if self.disparity_range else []) + [
             ")",
         ]
         return "\n".join(parts)
@@ -198,7 +211,16 @@ def match(stack0, stack1, cfg=None, devices=None):
     cdtype = np.float64 if cfg._c_config.contents.precision else np.float32
     disparity = np.empty((rows, cols), ddtype)
     corrmap = np.empty((rows, cols), cdtype)
-    if devices is None:
+    rng = getattr(cfg, "disparity_range", None)
+    if rng is not None and devices is not None and len(list(devices)) > 1:
+        raise ValueError("disparity_range is not supported with several GPUs yet")
+    if rng is not None:
+        if devices is not None and len(list(devices)) == 1:
+            raise ValueError("disparity_range runs on the current device: leave devices unset")
+        rc = L.bicos_match_host_range(None, d0, d1, len(k0), rows, cols, 0, f.dtype.itemsize,
+                                      cfg._c_config, 1, rng[0], rng[1], disparity.ctypes.data,
+                                      corrmap.ctypes.data)
+    elif devices is None:
         rc = L.bicos_match_host(None, d0, d1, len(k0), rows, cols, 0, f.dtype.itemsize,
                                 cfg._c_config, 1, disparity.ctypes.data, corrmap.ctypes.data)
     else:

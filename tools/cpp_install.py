@@ -24,3 +24,14 @@ def install_and_build_consumer(prefix, bdir, quiet=True):
                     "-DCMAKE_PREFIX_PATH=" + prefix], **kw)
     subprocess.run(["cmake", "--build", bdir], **kw)
     return os.path.join(bdir, "ref_style")
+
+
+def build_range_consumer(prefix, bdir, quiet=True):
+    """Configure and build tests/cpp/range_consumer (tests/cpp/range_style.cpp, a caller that
+    sets Config::disparity_range) in `bdir` against the tree installed in `prefix` (see
+    install_and_build_consumer)."""
+    kw = dict(check=True, capture_output=quiet)
+    subprocess.run(["cmake", "-S", os.path.join(ROOT, "tests", "cpp", "range_consumer"), "-B", bdir,
+                    "-DCMAKE_PREFIX_PATH=" + prefix], **kw)
+    subprocess.run(["cmake", "--build", bdir], **kw)
+    return os.path.join(bdir, "range_style")
