@@ -7,13 +7,18 @@
  * HIP engine in libbicos_amd/ and the "port" CPU baseline timed by bench.py.
  * Nothing in the product path links, loads or calls this code.
  *
- * Parity status: UNPINNED against the reference binary. The reference ships no
- * tests, golden vectors or known-answer fixtures and its CPU
- * path cannot be built in this image without stand-ins for OpenCV headers,
- * which this project does not write. The restatement is instead cross-checked
- * against an independent numpy restatement (oracle/ref_numpy.py), hand-derived
- * known-answer cases and the reference behaviours recorded in SURVEY.md
- * Appendix A (tests/test_oracle.py).
+ * Parity status: pinned to the reference's own CPU code. `make ref` compiles the
+ * reference's src/impl/cpu.cpp and include/impl/cpu/ headers unchanged from a
+ * reference tree (ref_driver.cpp; cv:: storage and threading are the stand-in of
+ * ref_shim/, the arithmetic is all the reference's) into _ref/, which is never
+ * committed, and tests/test_reference_parity.py demands byte-identical results
+ * from every function below and the reference's: whole matches, each stage, the
+ * error kinds, and every committed fixture. Not covered, for want of a reference
+ * CPU counterpart: Precision::DOUBLE and the disparity range, which this file
+ * does not restate either. The restatement is also cross-checked against an
+ * independent numpy restatement (oracle/ref_numpy.py), hand-derived known-answer
+ * cases and the reference behaviours recorded in SURVEY.md Appendix A
+ * (tests/test_oracle.py).
  *
  * Data layout (matches what BICOS::match receives: a vector of n planar images):
  *   stack  : n planes, plane t at stack + t*rows*cols elements, row-major,

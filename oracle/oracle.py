@@ -4,7 +4,9 @@ bicos_oracle.c (the parity checker and the "port" CPU baseline).
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import
 this module. The product path (libbicos_amd) never does.
 
-Parity status: UNPINNED against the reference binary (see bicos_oracle.h).
+Parity status: pinned byte for byte to the reference's own CPU code, compiled unchanged
+behind a storage / threading stand-in (oracle/reference.py, tests/test_reference_parity.py;
+see bicos_oracle.h for the limits).
 """
 from __future__ import annotations
 

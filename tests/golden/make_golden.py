@@ -1,9 +1,11 @@
 """Generate tests/golden/golden.npz -- regression vectors for the BICOS hot path.
 
-The reference ships no golden vectors and cannot be built here, so these
-are produced by the C oracle (oracle/bicos_oracle.c, cross-checked against the numpy
-restatement at generation time). Inputs are regenerated from the seeded synthetic
-generator; their sha256 is stored so a generator change is caught.
+The reference ships no golden vectors, so these are produced by the C oracle
+(oracle/bicos_oracle.c, cross-checked against the numpy restatement at generation time).
+The reference's own CPU code, compiled unchanged, reproduces every array
+(tests/test_reference_parity.py::test_reference_reproduces_golden_npz). Inputs are
+regenerated from the seeded synthetic generator; their sha256 is stored so a generator
+change is caught.
 
   python tests/golden/make_golden.py
 """

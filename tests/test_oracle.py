@@ -1,8 +1,8 @@
 """CPU tests of the parity oracle (oracle/bicos_oracle.c).
 
-The reference ships no tests or golden vectors and its CPU path cannot be built
-here without OpenCV stand-ins (parity UNPINNED). The oracle is
-pinned instead by (1) an independent numpy restatement (oracle/ref_numpy.py),
+The reference ships no tests or golden vectors. tests/test_reference_parity.py
+pins the oracle to the reference's own CPU code, compiled unchanged (DESIGN.md
+s3); here it is pinned by (1) an independent numpy restatement (oracle/ref_numpy.py),
 (2) known-answer descriptors derived by hand from the reference source, and
 (3) the reference behaviours SURVEY.md Appendix A recorded from the reference
 binary in the survey session.
