@@ -238,8 +238,13 @@ size_t bicos_desc_pitch(int cols, int words);
 int bicos_transform_device(const void* stack, int n, int rows, int cols, size_t row_pitch,
                            size_t plane_pitch, int depth, int mode, int words, uint32_t* desc,
                            void* stream);
-/* flags: 1 = NODUPES, 2 = CONSISTENCY (reference impl/common.hpp:46-47). Consistency needs
- * the engine's workspace; out is int16 rows x cols (dense).
+/* flags: 1 = NODUPES, 2 = CONSISTENCY (reference impl/common.hpp:46-47); out is int16 rows x
+ * cols (dense). The engine may be NULL (the search is then planned for 256 compute units,
+ * untuned) wherever the search needs no workspace: without CONSISTENCY, and for CONSISTENCY
+ * without NODUPES in its one-launch form (BICOS_PLAN_CONSISTENCY_ONE_PASS: 256-bit
+ * descriptors with 129..154 used bits given in B below, at most 2048 columns, the
+ * matrix-core search, BICOS_LR_ONE_PASS not 0). Every other CONSISTENCY search runs as two
+ * searches and a check and needs the engine's workspace for its two maps (NULL: BICOS_E_ARG).
  * flags bits 16-24 (optional): B = (flags >> 16) & 0x1FF, the number of low descriptor bits
  * that may be set (0 = all). The caller promises bits B..32*words-1 are zero in both
  * descriptor sets (true of transform output with B >= the transform's bit count: LIMITED

@@ -1,0 +1,209 @@
+// cxxapi.cpp -- the C++ API (include/bicos/*.hpp) over bicos_impl (engine.hpp):
+//
+//   BICOS::match   <- reference BICOS::match (src/lib.cpp:31-49) and the backend entry
+//                     impl::cpu::match (src/impl/cpu.cpp:100-159)
+#include "engine.hpp"
+
+#include <cstdlib>
+#include <memory>
+#include <vector>
+
+#include "../../include/bicos/common.hpp"
+#include "../../include/bicos/match.hpp"
+#include "../../include/bicos/hip.hpp"
+
+using bicos_impl::check_hip;
+
+namespace BICOS {
+
+size_t HipImage::elem_size(int type) {
+    switch (type) {
+        case U8: return 1;
+        case U16:
+        case S16: return 2;
+        case F32: return 4;
+        case F64: return 8;
+    }
+    throw Exception("unsupported image type " + std::to_string(type));
+}
+
+HipImage::HipImage(int rows, int cols, int type, void* data, size_t step, Memory mem)
+    : _data(data), _rows(rows), _cols(cols), _type(type), _mem(mem) {
+    _step = step ? step : (size_t)cols * elem_size(type);
+}
+
+void HipImage::create(int rows, int cols, int type, Memory mem) {
+    // like cv::Mat::create: a no-op when the header already describes a dense buffer of this
+    // size and type (owned or a view of the caller's memory), so results can be written
+    // straight into caller-provided buffers
+    if (_data && _rows == rows && _cols == cols && _type == type && _mem == mem &&
+        _step == (size_t)cols * elem_size(type))
+        return;
+    const size_t step = (size_t)cols * elem_size(type);
+    const size_t bytes = step * rows;
+    void* p = nullptr;
+    if (mem == Memory::Host) {
+        p = std::malloc(bytes ? bytes : 1);
+        if (!p) throw Exception("out of host memory");
+        _owner = std::shared_ptr<void>(p, [](void* q) { std::free(q); });
+    } else {
+        if (hipMalloc(&p, bytes ? bytes : 1) != hipSuccess) throw Exception("hipMalloc failed");
+        _owner = std::shared_ptr<void>(p, [](void* q) { (void)hipFree(q); });
+    }
+    _data = p;
+    _rows = rows;
+    _cols = cols;
+    _type = type;
+    _step = step;
+    _mem = mem;
+}
+
+HipImage HipImage::download() const {
+    if (_mem == Memory::Host) return *this;
+    Image h = allocate(_rows, _cols, _type, Memory::Host);
+    if (!empty() &&
+        hipMemcpy2D(h._data, h._step, _data, _step, (size_t)_cols * elemSize(), _rows,
+                    hipMemcpyDeviceToHost) != hipSuccess)
+        throw Exception("download failed");
+    return h;
+}
+
+static void throw_rc(int rc) {
+    if (rc != BICOS_OK) throw Exception(bicos_impl::last_error());
+}
+
+// reference src/impl/cpu.cpp:100-159 (validation, dispatch) + src/lib.cpp:31-49
+void match(const std::vector<Image>& stack0, const std::vector<Image>& stack1, Image& disparity,
+           Config cfg, Image* corrmap, hipStream_t stream) {
+    impl::hip::match(stack0, stack1, disparity, cfg, corrmap, stream);
+}
+
+// the backend seam (bicos/hip.hpp; reference include/cpu.hpp:27-33, include/cuda.hpp:27-34)
+void impl::hip::match(const std::vector<Image>& stack0, const std::vector<Image>& stack1,
+                      Image& disparity, Config cfg, Image* corrmap, hipStream_t stream) {
+    const size_t n = stack0.size();
+    if (n < 2) throw Exception("need at least two images");
+    if (stack1.size() != n) throw Exception("stacks differ in length");
+    const Image& f = stack0.front();
+    if (f.type() != U8 && f.type() != U16)
+        throw Exception("bad input depths, only CV_8UC1 and CV_16UC1 are supported");
+    const Memory mem = f.memory();
+    for (const auto* s : {&stack0, &stack1})
+        for (const Image& im : *s)
+            if (im.rows() != f.rows() || im.cols() != f.cols() || im.type() != f.type() ||
+                im.memory() != mem)
+                throw Exception("all images must share size, type and memory");
+    const int rows = f.rows(), cols = f.cols();
+    const int depth = (int)f.elemSize();
+
+    BicosConfig c{};
+    const bool has_nxcorr = cfg.nxcorr_threshold.has_value();
+    c.nxcorr_threshold = has_nxcorr ? *cfg.nxcorr_threshold : 0.5f;
+    c.subpixel_step = cfg.subpixel_step ? *cfg.subpixel_step : -1.f;
+    c.min_variance = cfg.min_variance ? *cfg.min_variance : -1.f;
+    c.mode = cfg.mode == TransformMode::FULL ? 1 : 0;
+    c.precision = cfg.precision == Precision::DOUBLE ? 1 : 0;
+    if (auto* cons = std::get_if<Variant::Consistency>(&cfg.variant)) {
+        c.variant_type = 1;
+        c.max_lr_diff = cons->max_lr_diff;
+        c.no_dupes = cons->no_dupes;
+    }
+    if (cfg.subpixel_step && !(*cfg.subpixel_step > 0))
+        throw Exception("subpixel_step must be a positive finite number");
+    bicos_impl::DispRange range{0, 0};
+    if (cfg.disparity_range) {
+        range = {cfg.disparity_range->min, cfg.disparity_range->max};
+        throw_rc(bicos_impl::check_range(range.min, range.max));
+    }
+    const bicos_impl::DispRange* rg = cfg.disparity_range ? &range : nullptr;
+    if (cfg.min_variance && *cfg.min_variance < 0) c.min_variance = -1.f;
+
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    bicos_engine* e = bicos_impl::default_engine(dev);
+    if (!e) throw Exception(bicos_impl::last_error());
+    std::lock_guard<std::mutex> g(e->lock);
+    hipStream_t st = mem == Memory::Host ? e->own_stream : stream;
+    const int dtype = has_nxcorr ? F32 : S16;
+    const bool dbl = c.precision != 0;
+    const bool want_corr = corrmap && has_nxcorr;
+
+    if (mem == Memory::Host) {
+        // banded, pipelined upload -> match -> download (bicos_impl::match_host)
+        std::vector<const void*> p0(n), p1(n);
+        std::vector<size_t> st0(n), st1(n);
+        for (size_t t = 0; t < n; ++t) {
+            p0[t] = stack0[t].data();
+            p1[t] = stack1[t].data();
+            st0[t] = stack0[t].step();
+            st1[t] = stack1[t].step();
+        }
+        disparity.create(rows, cols, dtype, Memory::Host);
+        if (want_corr) corrmap->create(rows, cols, dbl ? F64 : F32, Memory::Host);
+        throw_rc(bicos_impl::match_host(e, p0.data(), st0.data(), p1.data(), st1.data(), (int)n,
+                                        rows, cols, depth, c, has_nxcorr, c.nxcorr_threshold,
+                                        disparity.data(), want_corr ? corrmap->data() : nullptr,
+                                        rg));
+        return;
+    }
+
+    // the planar device stacks the kernels read
+    const size_t elem = (size_t)depth;
+    const void* s0 = nullptr;
+    const void* s1 = nullptr;
+    size_t row_pitch = (size_t)cols, plane_pitch = (size_t)rows * cols;
+    auto uniform = [&](const std::vector<Image>& s, size_t& rp, size_t& pp) {
+        // zero-copy when the images already form one planar buffer with a common pitch
+        if (s[0].step() % elem) return false;
+        rp = s[0].step() / elem;
+        const char* b = (const char*)s[0].data();
+        if (n < 2) return false;
+        const ptrdiff_t d = (const char*)s[1].data() - b;
+        if (d <= 0 || d % (ptrdiff_t)elem) return false;
+        for (size_t t = 0; t < n; ++t)
+            if (s[t].step() != s[0].step() || (const char*)s[t].data() != b + (ptrdiff_t)t * d)
+                return false;
+        pp = (size_t)d / elem;
+        return pp >= (size_t)rows * rp;
+    };
+    size_t rp0 = 0, pp0 = 0, rp1 = 0, pp1 = 0;
+    // staged rows start 64-byte aligned: no two copies share a dword and the pitches suit
+    // the aligned (LDS-staged) agree kernel
+    const size_t stage_row = ((size_t)cols * elem + 63) & ~(size_t)63;
+    const size_t plane_bytes = (size_t)rows * stage_row;
+    bicos_impl::Lease stage(e, e->stage, e->stage_bytes, st);  // held until the match is queued
+    if (uniform(stack0, rp0, pp0) && uniform(stack1, rp1, pp1) && rp0 == rp1 && pp0 == pp1) {
+        s0 = stack0[0].data();
+        s1 = stack1[0].data();
+        row_pitch = rp0;
+        plane_pitch = pp0;
+    } else if (rows > 0 && cols > 0) {
+        stage.take(2 * n * plane_bytes);
+        throw_rc(stage.acquire());
+        char* dst = stage.take(2 * n * plane_bytes);
+        const hipMemcpyKind kind = hipMemcpyDeviceToDevice;
+        for (size_t t = 0; t < n; ++t) {
+            throw_rc(check_hip(hipMemcpy2DAsync(dst + t * plane_bytes, stage_row,
+                                                stack0[t].data(), stack0[t].step(), cols * elem,
+                                                rows, kind, st),
+                               "stack upload"));
+            throw_rc(check_hip(hipMemcpy2DAsync(dst + (n + t) * plane_bytes, stage_row,
+                                                stack1[t].data(), stack1[t].step(), cols * elem,
+                                                rows, kind, st),
+                               "stack upload"));
+        }
+        s0 = dst;
+        s1 = dst + n * plane_bytes;
+        row_pitch = stage_row / elem;
+        plane_pitch = plane_bytes / elem;
+    }
+
+    disparity.create(rows, cols, dtype, Memory::Device);
+    if (want_corr) corrmap->create(rows, cols, dbl ? F64 : F32, Memory::Device);
+    throw_rc(bicos_impl::match_device(e, s0, s1, (int)n, rows, cols, row_pitch, plane_pitch, depth,
+                                      c, has_nxcorr, c.nxcorr_threshold, disparity.data(),
+                                      want_corr ? corrmap->data() : nullptr, st, false, nullptr,
+                                      nullptr, rg));
+}
+
+}  // namespace BICOS

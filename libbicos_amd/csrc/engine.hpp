@@ -3,11 +3,19 @@
 // Plays the role of the reference's match_impl (src/impl/cpu.cpp:35-98,
 // src/impl/cuda.cu:56-463): transform both stacks, search, optional consistency,
 // optional agree / subpixel. All launches are asynchronous on one HIP stream.
+//
+//   engine.cpp  errors, the workspace lease, engine resources, the plans, the search driver
+//               and match_device
+//   host.cpp    the banded host-buffer pipeline (HostPool, match_host)
+//   entries.cpp the bicos_* extern "C" entries (bicos_c.h) but the multi-GPU ones
+//   multi.cpp   bicos_match_host_multi, bicos_match_bands_device
+//   cxxapi.cpp  namespace BICOS (HipImage, match)
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <condition_variable>
+#include <exception>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -38,6 +46,12 @@ class HostPool {
     unsigned gen_ = 0;
     bool stop_ = false;
 };
+
+// pinned host memory, grown on demand (grow_pinned)
+struct PinnedBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
 }  // namespace bicos_impl
 
 struct bicos_engine {
@@ -52,7 +66,7 @@ struct bicos_engine {
 
     // workspace (grown on demand, never shrunk). ws_ready is recorded after every use of
     // ws / stage on the caller's stream and waited on before the next: calls on different
-    // streams are ordered, never racing on the shared buffers.
+    // streams are ordered, never racing on the shared buffers (bicos_impl::Lease).
     hipEvent_t ws_ready = nullptr;
     void* ws = nullptr;
     size_t ws_bytes = 0;
@@ -61,15 +75,13 @@ struct bicos_engine {
     size_t stage_bytes = 0;
     // host-buffer pipeline (match_host): copy stream, pinned band slots, band events
     hipStream_t copy_stream = nullptr;
-    void* pinned = nullptr;  // K input band slots
-    size_t pinned_bytes = 0;
+    bicos_impl::PinnedBuf pinned;  // K input band slots
     std::vector<hipEvent_t> events;
     std::unique_ptr<bicos_impl::HostPool> pool;
     // host-staged multi-GPU gather (multi.cpp bicos_match_bands_device): its own pinned
     // buffer and events, grown only (sharing match_host's slots reallocated the
     // pinned memory whenever the two paths alternated)
-    void* gather_pinned = nullptr;
-    size_t gather_pinned_bytes = 0;
+    bicos_impl::PinnedBuf gather_pinned;
     std::vector<hipEvent_t> gather_events;
     // host-buffer pipeline, maps downloaded band by band on their own stream (so a copy
     // engine other than the uploads' can take them: PCIe is full duplex) into pinned memory,
@@ -78,37 +90,141 @@ struct bicos_engine {
     // a second upload stream: each band's upload split in two halves (BICOS_HOST_UPLOAD_STREAMS)
     hipStream_t copy_stream2 = nullptr;
     std::vector<hipEvent_t> events2;
-    void* pinned_out = nullptr;
-    size_t pinned_out_bytes = 0;
+    bicos_impl::PinnedBuf pinned_out;
     std::vector<hipEvent_t> dl_events;
 };
 
 namespace bicos_impl {
-
-struct Status {
-    int code = BICOS_OK;
-    std::string msg;
-    bool ok() const { return code == BICOS_OK; }
-};
 
 void set_error(int code, const std::string& msg);
 int fail(int code, const std::string& msg);
 const char* last_error();  // this thread's last message
 int check_hip(hipError_t e, const char* what);
 
+// The boundary of every extern "C" entry: f's code, or BICOS_E_INTERNAL for what it throws
+template <class F>
+int guarded(F&& f) {
+    try {
+        return f();
+    } catch (const std::exception& ex) {
+        return fail(BICOS_E_INTERNAL, ex.what());
+    } catch (...) {
+        return fail(BICOS_E_INTERNAL, "unknown exception");
+    }
+}
+
+// n >= 2 images of depth 1 or 2 bytes, no negative size: BICOS_OK or BICOS_E_ARG
+int check_stack_shape(int n, int depth, int rows, int cols);
+
+// reference src/pybicos_c.cpp:59-61: a negative threshold keeps the default 0.5
+inline float nxc_threshold(const BicosConfig& cfg) {
+    return cfg.nxcorr_threshold >= 0 ? cfg.nxcorr_threshold : 0.5f;
+}
+
 // Reserve `bytes` of engine workspace (device), stream-ordered on `st`: a buffer that
 // must grow is freed on `st` after `ready` (every earlier use) and the new one allocated
 // there (hipFreeAsync / hipMallocAsync). Returns BICOS_OK or an error code.
 int reserve(void*& buf, size_t& have, size_t bytes, int device, hipStream_t st, hipEvent_t ready);
 
-int descriptor_words(int n, int mode);
+constexpr size_t ALIGN = 256;
+inline size_t align_up(size_t x) { return (x + ALIGN - 1) / ALIGN * ALIGN; }
 
-bicos_hip::SearchGeometry geometry(const bicos_engine* e, int rows, int cols, int words);
+// One use of an engine buffer (ws or stage) on one stream, and the rule that keeps two
+// streams from racing on it: acquire() reserves the bytes, makes `st` wait for ws_ready
+// (every earlier use, on any stream), and from then on release() -- at the latest the
+// destructor, on every exit path -- records ws_ready on `st`.
+// The layout is a sequence of take() calls that the user walks twice with the same code:
+// before acquire() the calls only add up the bytes (and return nullptr), after it they hand
+// out the 256-byte aligned sub-buffers in the same order, so a size cannot disagree with
+// its layout.
+class Lease {
+  public:
+    Lease(bicos_engine* e, void*& buf, size_t& have, hipStream_t st)
+        : e_(e), buf_(buf), have_(have), st_(st) {}
+    Lease(const Lease&) = delete;
+    ~Lease() { release(); }
+
+    template <class T = char>
+    T* take(size_t count) {
+        const size_t at = off_;
+        off_ += align_up(count * sizeof(T));
+        return held_ ? (T*)((char*)buf_ + at) : nullptr;
+    }
+    int acquire();
+    void release();
+    char* base() const { return (char*)buf_; }
+    size_t needed() const { return off_; }  // bytes taken so far
+
+  private:
+    bicos_engine* e_;
+    void*& buf_;
+    size_t& have_;
+    hipStream_t st_;
+    size_t off_ = 0;
+    bool held_ = false;
+};
+
+// Engine resources, each grown on demand and freed by free_resources (bicos_engine_destroy)
+int grow_pinned(PinnedBuf& b, size_t bytes, const char* what);  // failure: null, 0 bytes
+int grow_events(std::vector<hipEvent_t>& v, int count);
+int ensure_stream(hipStream_t& s);  // a non-blocking stream, created on first use
+void free_resources(bicos_engine* e);  // streams, events, pinned buffers; not ws / stage
+
+int descriptor_words(int n, int mode);
 
 // An inclusive disparity window min <= col0 - col1 <= max (bicos_c.h, the *_range entries)
 struct DispRange {
     int min, max;
 };
+
+// What the search stage runs (the search's BICOS_PLAN_* bits: MATRIX_CORES, PACKED_KEYS,
+// CONSISTENCY_ONE_PASS, REVERSE_COMPACTED, DENSE_ROWS) and what it runs it with
+struct SearchPlan {
+    int bits = 0;
+    bool two_pass = false;       // Consistency as forward search, reverse search and a check:
+                                 // the one form that needs workspace (SearchBuffers)
+    bicos_hip::MxGeometry mx{};  // of the full-row matrix-core search (MATRIX_CORES, no range)
+};
+// e may be NULL (256 CUs, untuned). used_bits: the K-step hint, written_bits: the exact count
+// one-pass Consistency is eligible by (0 = unknown); a stage entry has one hint for both.
+SearchPlan search_plan(const bicos_engine* e, int rows, int cols, int words, int used_bits,
+                       int written_bits, bool nodupes, bool consistency, bool ranged);
+
+// the maps of a two-pass Consistency search, taken from a lease in this order
+struct SearchBuffers {
+    int16_t* fwd = nullptr;
+    int16_t* rev = nullptr;
+    uint8_t* valid = nullptr;  // per-tile valid counts (DENSE_ROWS)
+};
+SearchBuffers search_buffers(Lease& ws, const SearchPlan& p, int rows, int cols);
+
+struct SearchJob {
+    const uint32_t* d0;  // descriptors (bicos_desc_pitch rows) of the matched side
+    const uint32_t* d1;  // ... and of the searched side
+    int rows, cols, words;
+    int used_bits, written_bits;  // as search_plan's
+    bool nodupes;
+    int max_lr_diff;
+    const DispRange* range;  // nullptr: the whole row
+};
+// The search stage of `p` on `st`: the final int16 map into `out`; with out == nullptr
+// (two-pass Consistency whose check runs inside the agree) only b.fwd and b.rev.
+// fused_agree (BICOS_PLAN_AGREE_IN_SEARCH): the agree to run inside the search launch.
+int run_search(const bicos_engine* e, const SearchPlan& p, const SearchBuffers& b,
+               const SearchJob& j, int16_t* out, hipStream_t st,
+               const bicos_hip::AgreeArgs* fused_agree = nullptr);
+
+// Bytes the kernels may address from a stack base (32-bit buffer offsets): BICOS_E_ARG past 4 GiB
+int stack_span(int n, int rows, int cols, size_t row_pitch, size_t plane_pitch, int depth,
+               uint32_t* out);
+int subpixel_steps(float step);  // 0: more than the kernels accept
+
+// The agree / subpixel launch arguments; minvar_scaled: min_variance * n (cpu.cpp:127)
+bicos_hip::AgreeArgs agree_args(const int16_t* raw, const void* s0, const void* s1, int n,
+                                int rows, int cols, size_t row_pitch, size_t plane_pitch,
+                                uint32_t span, float threshold, float step, int nsteps,
+                                int has_minvar, float minvar_scaled, void* out, bool out_f32,
+                                void* corr);
 
 // Full match on device buffers (validated arguments). corr may be null. disp_i16: the
 // disparity map is int16 even with the NXC stage (no subpixel; bicos_match_device_i16).
@@ -122,10 +238,16 @@ int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int row
                  bool disp_i16 = false, const uint32_t* ext_d0 = nullptr,
                  const uint32_t* ext_d1 = nullptr, const DispRange* range = nullptr);
 
-// BICOS_PLAN_* bits of what match_device runs after the transform (bicos_match_plan)
-int match_plan(const bicos_engine* e, int n, int rows, int cols, size_t row_pitch,
-               size_t plane_pitch, int depth, const BicosConfig& cfg, bool has_nxcorr,
-               const void* s0, const void* s1, bool ranged = false);
+// What match_device runs after the transform (bicos_match_plan: bits()): the search's part
+// and the agree's (BICOS_PLAN_AGREE_IN_SEARCH, BICOS_PLAN_CONSISTENCY_IN_AGREE)
+struct MatchPlan {
+    SearchPlan search;
+    int agree = 0;
+    int bits() const { return search.bits | agree; }
+};
+MatchPlan match_plan(const bicos_engine* e, int n, int rows, int cols, size_t row_pitch,
+                     size_t plane_pitch, int depth, const BicosConfig& cfg, bool has_nxcorr,
+                     const void* s0, const void* s1, bool ranged = false);
 
 // Host buffers in and out (the reference's cv::Mat path, src/impl/cpu.cpp:100-159): the
 // stacks are uploaded in row bands through pinned slots on a copy stream while earlier

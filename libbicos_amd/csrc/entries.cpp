@@ -1,0 +1,337 @@
+// entries.cpp -- the bicos_* extern "C" entries of include/bicos_c.h over bicos_impl
+// (engine.hpp); the multi-GPU entries are multi.cpp, the reference's ctypes ABI capi.cpp.
+#include "engine.hpp"
+
+#include <cmath>
+#include <vector>
+
+using namespace bicos_impl;
+
+namespace {
+
+int check_words(int words) {
+    if (words == 1 || words == 2 || words == 4 || words == 8) return BICOS_OK;
+    return fail(BICOS_E_ARG, "words must be 1, 2, 4 or 8");
+}
+
+int match_device_entry(bicos_engine* e, const void* stack0, const void* stack1, int n, int rows,
+                       int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                       const BicosConfig* cfg, int has_nxcorr, void* disparity, void* corrmap,
+                       void* stream, bool disp_i16, const DispRange* range = nullptr,
+                       const uint32_t* desc0 = nullptr, const uint32_t* desc1 = nullptr) {
+    if (range)
+        if (int rc0 = check_range(range->min, range->max)) return rc0;
+    if (!cfg) return fail(BICOS_E_ARG, "null config");
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    return guarded([&]() -> int {
+        // the engine's workspace may be shared with other threads (the default engine is):
+        // enqueueing is serialised per engine, the GPU work is ordered through ws_ready
+        std::lock_guard<std::mutex> g(e->lock);
+        return match_device(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth, *cfg,
+                            has_nxcorr != 0, nxc_threshold(*cfg), disparity, corrmap,
+                            (hipStream_t)stream, disp_i16, desc0, desc1, range);
+    });
+}
+
+int match_host_entry(bicos_engine* e, const void* const* stack0, const void* const* stack1, int n,
+                     int rows, int cols, size_t step, int depth, const BicosConfig* cfg,
+                     int has_nxcorr, void* disparity, void* corrmap, const DispRange* range) {
+    if (range)
+        if (int rc0 = check_range(range->min, range->max)) return rc0;
+    if (!cfg) return fail(BICOS_E_ARG, "null config");
+    if (n < 0) return fail(BICOS_E_ARG, "negative stack size");
+    return guarded([&]() -> int {
+        if (!e) {
+            int dev = 0;
+            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
+            if (rc) return rc;
+            e = default_engine(dev);
+            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        }
+        std::lock_guard<std::mutex> g(e->lock);
+        const std::vector<size_t> steps((size_t)n, step ? step : (size_t)(cols > 0 ? cols : 0) * depth);
+        return match_host(e, stack0, steps.data(), stack1, steps.data(), n, rows, cols, depth, *cfg,
+                          has_nxcorr != 0, nxc_threshold(*cfg), disparity, corrmap, range);
+    });
+}
+
+// bicos_search_device[_range]: the search stage of a match (search_plan, run_search) over the
+// caller's descriptors. Only two-pass Consistency needs the engine, for its two maps.
+int search_entry(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1, int rows, int cols,
+                 int words, int flags, int max_lr_diff, const DispRange* range, int16_t* out,
+                 void* stream) {
+    if (int rc0 = check_words(words)) return rc0;
+    if (cols > 32767) return fail(BICOS_E_ARG, "image width exceeds 32767");
+    const bool empty = rows <= 0 || cols <= 0;
+    if (empty && !range) return BICOS_OK;
+    const int bits = (flags >> 16) & 0x1FF;  // 0 = all descriptor bits may be set
+    const SearchPlan plan = search_plan(e, rows, cols, words, bits, bits, (flags & 1) != 0,
+                                        (flags & 2) != 0, range != nullptr);
+    if (plan.two_pass && !e)
+        return fail(BICOS_E_ARG, "consistency search needs an engine workspace");
+    if (empty) return BICOS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const SearchJob job{desc0, desc1, rows, cols, words, bits, bits, (flags & 1) != 0,
+                        max_lr_diff, range};
+    if (!plan.two_pass) return run_search(e, plan, SearchBuffers{}, job, out, st);
+    std::lock_guard<std::mutex> lk(e->lock);  // the workspace may be shared (default engine)
+    Lease ws(e, e->ws, e->ws_bytes, st);
+    search_buffers(ws, plan, rows, cols);
+    if (int rc = ws.acquire()) return rc;
+    return run_search(e, plan, search_buffers(ws, plan, rows, cols), job, out, st);
+}
+
+int agree_common(bool sub, const int16_t* raw, const void* stack0, const void* stack1, int n,
+                 int rows, int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                 float threshold, float step, int has_minvar, float minvar_scaled, float* out,
+                 void* corrmap, void* stream, bool dbl = false) {
+    if (n > 65 && sub) return fail(BICOS_E_ARG, "subpixel supports n <= 65");
+    if (int rc0 = check_stack_shape(n, depth, 0, 0)) return rc0;
+    if (sub && !(step > 0 && std::isfinite(step)))
+        return fail(BICOS_E_ARG, "subpixel_step must be a positive finite number");
+    const int nsteps = sub ? subpixel_steps(step) : 0;
+    if (sub && !nsteps)
+        return fail(BICOS_E_ARG, "subpixel_step too small (more than 65536 interpolation steps)");
+    uint32_t span = 0;
+    if (int rc0 = stack_span(n, rows, cols, row_pitch, plane_pitch, depth, &span)) return rc0;
+    const bicos_hip::AgreeArgs aa =
+        agree_args(raw, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, span, threshold,
+                   step, nsteps, has_minvar, minvar_scaled, out, true, corrmap);
+    hipStream_t st = (hipStream_t)stream;
+    return sub ? check_hip(bicos_hip::launch_subpixel(aa, depth, dbl, st), "subpixel launch")
+               : check_hip(bicos_hip::launch_agree(aa, depth, dbl, st), "agree launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* bicos_last_error(void) { return bicos_impl::last_error(); }
+
+int bicos_engine_create(int device, bicos_engine** out) {
+    if (!out) return fail(BICOS_E_ARG, "null out");
+    *out = nullptr;
+    int count = 0;
+    int rc = check_hip(hipGetDeviceCount(&count), "hipGetDeviceCount");
+    if (rc) return rc;
+    if (device < 0 || device >= count) return fail(BICOS_E_ARG, "no such HIP device");
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(device);
+    auto* e = new bicos_engine();
+    e->device = device;
+    int lds = 0;
+    if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) ==
+            hipSuccess &&
+        lds > 0) {
+        // keep the per-workgroup right-row stage <= 64 KiB so >= 2 workgroups fit per CU
+        e->max_lds = lds < 64 * 1024 ? lds : 64 * 1024;
+        e->lds_limit = lds;
+    }
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
+        cus > 0)
+        e->cus = cus;
+    rc = ensure_stream(e->own_stream);
+    if (!rc) rc = ensure_stream(e->copy_stream);
+    if (!rc)
+        rc = check_hip(hipEventCreateWithFlags(&e->ws_ready, hipEventDisableTiming),
+                       "hipEventCreate");
+    (void)hipSetDevice(cur);
+    if (rc) {
+        free_resources(e);
+        delete e;
+        return rc;
+    }
+    *out = e;
+    return BICOS_OK;
+}
+
+bicos_engine* bicos_engine_default(int device) { return default_engine(device); }
+
+void bicos_engine_destroy(bicos_engine* e) {
+    if (!e) return;
+    if (is_default_engine(e)) return;  // the process-wide engines live until exit
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    (void)hipSetDevice(e->device);
+    (void)hipDeviceSynchronize();
+    // workspaces come from the stream-ordered allocator (reserve)
+    if (e->ws) (void)hipFreeAsync(e->ws, e->own_stream);
+    if (e->stage) (void)hipFreeAsync(e->stage, e->own_stream);
+    (void)hipStreamSynchronize(e->own_stream);
+    free_resources(e);
+    (void)hipSetDevice(cur);
+    delete e;
+}
+
+int bicos_engine_tune(bicos_engine* e, int variant, int col0_per_lane, int waves, int split) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    if (variant >= 64 && variant <= 68) {
+        // matrix-core search (64 auto keys, 65 one product + xor keys, 66 two products, 67
+        // xor keys for first-minimum searches too, no FK keys, 68 packed keys where they
+        // apply -- the automatic choice);
+        // col0_per_lane = 32-column tiles per wave
+        if (col0_per_lane != 0 && col0_per_lane != 2 && col0_per_lane != 4 && col0_per_lane != 8)
+            return fail(BICOS_E_ARG, "variant 64-68: tiles per wave 2|4|8");
+        if (waves < 0 || waves > 8) return fail(BICOS_E_ARG, "waves 1..8");
+        if (split < 0 || split > 160) return fail(BICOS_E_ARG, "variant 64-68: split = LDS KiB 0..160");
+    } else {
+        if (variant != 0 && variant != 16) return fail(BICOS_E_ARG, "variant 0|16|64..68");
+        if (col0_per_lane != 0 && col0_per_lane != 2 && col0_per_lane != 4)
+            return fail(BICOS_E_ARG, "col0_per_lane: 2|4 (variant 16)");
+        if (waves < 0 || waves > 8) return fail(BICOS_E_ARG, "waves 1..8");
+        if (split != 0 && split != 1 && split != 2 && split != 4 && split != 8)
+            return fail(BICOS_E_ARG, "split 1|2|4|8");
+        if (split > 1 && (waves ? waves : 8) % split)
+            return fail(BICOS_E_ARG, "split needs waves divisible by split");
+    }
+    e->tune_variant = variant;
+    e->tune_R = col0_per_lane;
+    e->tune_waves = waves;
+    e->tune_split = split;
+    return BICOS_OK;
+}
+
+int bicos_descriptor_words(int n, int mode) {
+    if (n < 2) return fail(BICOS_E_ARG, "need at least two images");
+    const int w = descriptor_words(n, mode ? 1 : 0);
+    if (w < 0) return fail(BICOS_E_BITS, "input stacks too large");
+    return w;
+}
+
+int bicos_output_type(const BicosConfig* cfg, int has_nxcorr) {
+    (void)cfg;
+    return has_nxcorr ? BICOS_CV_32F : BICOS_CV_16S;
+}
+
+size_t bicos_desc_pitch(int cols, int words) {
+    return ((size_t)cols * words + 3) / 4 * 4;
+}
+
+int bicos_match_device(bicos_engine* e, const void* stack0, const void* stack1, int n, int rows,
+                       int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                       const BicosConfig* cfg, int has_nxcorr, void* disparity, void* corrmap,
+                       void* stream) {
+    return match_device_entry(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth, cfg,
+                              has_nxcorr, disparity, corrmap, stream, false);
+}
+
+int bicos_match_device_range(bicos_engine* e, const void* stack0, const void* stack1, int n,
+                             int rows, int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                             const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                             int max_disparity, void* disparity, void* corrmap, void* stream) {
+    const DispRange range{min_disparity, max_disparity};
+    return match_device_entry(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth, cfg,
+                              has_nxcorr, disparity, corrmap, stream, false, &range);
+}
+
+int bicos_match_device_i16(bicos_engine* e, const void* stack0, const void* stack1, int n, int rows,
+                           int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                           const BicosConfig* cfg, int has_nxcorr, void* disparity, void* corrmap,
+                           void* stream) {
+    return match_device_entry(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth, cfg,
+                              has_nxcorr, disparity, corrmap, stream, true);
+}
+
+int bicos_match_plan(bicos_engine* e, const void* stack0, const void* stack1, int n, int rows,
+                     int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                     const BicosConfig* cfg, int has_nxcorr) {
+    if (!cfg) return fail(BICOS_E_ARG, "null config");
+    if (int rc0 = check_stack_shape(n, depth, 0, 0)) return rc0;  // (any rows / cols plan)
+    if (descriptor_words(n, cfg->mode ? 1 : 0) < 0) return fail(BICOS_E_BITS, "input stacks too large");
+    return match_plan(e, n, rows, cols, row_pitch, plane_pitch, depth, *cfg, has_nxcorr != 0,
+                      stack0, stack1).bits();
+}
+
+int bicos_search_agree_device(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1,
+                              const void* stack0, const void* stack1, int n, int rows, int cols,
+                              size_t row_pitch, size_t plane_pitch, int depth,
+                              const BicosConfig* cfg, int has_nxcorr, void* disparity,
+                              void* corrmap, void* stream) {
+    if (!cfg) return fail(BICOS_E_ARG, "null config");
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    if (rows > 0 && cols > 0 && (!desc0 || !desc1)) return fail(BICOS_E_ARG, "null descriptors");
+    return match_device_entry(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth, cfg,
+                              has_nxcorr, disparity, corrmap, stream, false, nullptr, desc0, desc1);
+}
+
+int bicos_match_host(bicos_engine* e, const void* const* stack0, const void* const* stack1, int n,
+                     int rows, int cols, size_t step, int depth, const BicosConfig* cfg,
+                     int has_nxcorr, void* disparity, void* corrmap) {
+    return match_host_entry(e, stack0, stack1, n, rows, cols, step, depth, cfg, has_nxcorr,
+                            disparity, corrmap, nullptr);
+}
+
+int bicos_match_host_range(bicos_engine* e, const void* const* stack0, const void* const* stack1,
+                           int n, int rows, int cols, size_t step, int depth,
+                           const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                           int max_disparity, void* disparity, void* corrmap) {
+    const DispRange range{min_disparity, max_disparity};
+    return match_host_entry(e, stack0, stack1, n, rows, cols, step, depth, cfg, has_nxcorr,
+                            disparity, corrmap, &range);
+}
+
+int bicos_transform_device(const void* stack, int n, int rows, int cols, size_t row_pitch,
+                           size_t plane_pitch, int depth, int mode, int words, uint32_t* desc,
+                           void* stream) {
+    if (int rc0 = check_stack_shape(n, depth, 0, 0)) return rc0;
+    if (int rc0 = check_words(words)) return rc0;
+    const int need = descriptor_words(n, mode ? 1 : 0);
+    if (need < 0 || need > words) return fail(BICOS_E_BITS, "descriptor too narrow for n");
+    uint32_t span = 0;
+    if (int rc0 = stack_span(n, rows, cols, row_pitch, plane_pitch, depth, &span)) return rc0;
+    bicos_hip::TransformArgs ta{stack, nullptr, desc, nullptr, n, rows, cols,
+                                row_pitch, plane_pitch, bicos_desc_pitch(cols, words), 0, span};
+    return check_hip(bicos_hip::launch_transform(ta, depth, mode ? 1 : 0, words, (hipStream_t)stream),
+                     "transform launch");
+}
+
+int bicos_search_device(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1, int rows,
+                        int cols, int words, int flags, int max_lr_diff, int16_t* out,
+                        void* stream) {
+    return search_entry(e, desc0, desc1, rows, cols, words, flags, max_lr_diff, nullptr, out,
+                        stream);
+}
+
+int bicos_search_device_range(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1,
+                              int rows, int cols, int words, int flags, int max_lr_diff,
+                              int min_disparity, int max_disparity, int16_t* out, void* stream) {
+    if (int rc0 = check_range(min_disparity, max_disparity)) return rc0;
+    const DispRange range{min_disparity, max_disparity};
+    return search_entry(e, desc0, desc1, rows, cols, words, flags, max_lr_diff, &range, out,
+                        stream);
+}
+
+int bicos_agree_stage_device(const int16_t* raw, const void* stack0, const void* stack1, int n,
+                             int rows, int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                             float threshold, float step, int has_minvar, float minvar_scaled,
+                             int precision, float* out, void* corrmap, void* stream) {
+    return agree_common(step > 0, raw, stack0, stack1, n, rows, cols, row_pitch, plane_pitch,
+                        depth, threshold, step, has_minvar, minvar_scaled, out, corrmap, stream,
+                        precision != 0);
+}
+
+int bicos_agree_device(const int16_t* raw, const void* stack0, const void* stack1, int n, int rows,
+                       int cols, size_t row_pitch, size_t plane_pitch, int depth, float threshold,
+                       int has_minvar, float minvar_scaled, float* out, float* corrmap,
+                       void* stream) {
+    return agree_common(false, raw, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth,
+                        threshold, 0.f, has_minvar, minvar_scaled, out, corrmap, stream);
+}
+
+int bicos_subpixel_device(const int16_t* raw, const void* stack0, const void* stack1, int n,
+                          int rows, int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                          float threshold, float step, int has_minvar, float minvar_scaled,
+                          float* out, float* corrmap, void* stream) {
+    return agree_common(true, raw, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth,
+                        threshold, step, has_minvar, minvar_scaled, out, corrmap, stream);
+}
+
+const char* bicos_build_info(void) {
+    return "libbicos_amd: gfx950 HIP kernels (transform, mx search: FP4 MFMA Hamming products "
+           "with argmin keys in the accumulator [default], LDS-broadcast popcount/argmin VALU "
+           "search, NXC agree/subpixel), -O3 -ffp-contract=off";
+}
+
+}  // extern "C"

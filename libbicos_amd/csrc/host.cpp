@@ -1,0 +1,365 @@
+// host.cpp -- the banded host-buffer pipeline: bicos_impl::match_host and its thread pool
+// (the reference's cv::Mat path, src/impl/cpu.cpp:100-159).
+#include "engine.hpp"
+
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+
+namespace bicos_impl {
+
+HostPool::HostPool(int threads) {
+    for (int i = 1; i < threads; ++i) workers_.emplace_back([this] { loop(); });
+}
+
+HostPool::~HostPool() {
+    {
+        std::lock_guard<std::mutex> g(m_);
+        stop_ = true;
+    }
+    cv_.notify_all();
+    for (auto& t : workers_) t.join();
+}
+
+void HostPool::loop() {
+    unsigned seen = 0;
+    std::unique_lock<std::mutex> lk(m_);
+    for (;;) {
+        cv_.wait(lk, [&] { return stop_ || gen_ != seen; });
+        if (stop_) return;
+        seen = gen_;
+        ++active_;
+        while (next_ < tasks_) {
+            const int i = next_++;
+            const std::function<void(int)>* f = job_;
+            lk.unlock();
+            (*f)(i);
+            lk.lock();
+        }
+        if (--active_ == 0) done_.notify_all();
+    }
+}
+
+void HostPool::run(int tasks, const std::function<void(int)>& f) {
+    std::unique_lock<std::mutex> lk(m_);
+    job_ = &f;
+    tasks_ = tasks;
+    next_ = 0;
+    ++gen_;
+    cv_.notify_all();
+    ++active_;
+    while (next_ < tasks_) {
+        const int i = next_++;
+        lk.unlock();
+        f(i);
+        lk.lock();
+    }
+    --active_;
+    done_.wait(lk, [&] { return active_ == 0; });
+    job_ = nullptr;
+    tasks_ = 0;
+}
+
+namespace {
+
+// Transfers (measured, tools/host_bench.py): a thread pool gathers each band of the
+// caller's images into a pinned slot and one DMA per band uploads it (5-7 ms per cfg2
+// match, PCIe-bound: 207 MB at 35-42 GB/s while the gathers run; pageable
+// hipMemcpy2DAsync per band and plane: ~11 ms).
+// Round 6 (profiles/host_path_r06.jsonl, host_trace_r06*.txt): each band's
+// upload is split over two copy streams, and the maps come down band by band on a third
+// stream into pinned memory as each band's match ends, then into the caller's buffers by
+// the pool -- 4.40-4.52 ms per cfg2 match against 5.45-5.79 with one upload stream and one
+// download at the end (two rounds interleaved on one box; either change alone was not
+// consistent: 4.86-7.29 / 4.98-5.41 ms). BICOS_HOST_UPLOAD_STREAMS=1 / BICOS_HOST_DL=once:
+// the round-5 pipeline.
+bool download_by_band() {
+    static const bool on = [] {
+        const char* v = std::getenv("BICOS_HOST_DL");
+        return !(v && !std::strcmp(v, "once"));
+    }();
+    return on;
+}
+int upload_streams() {
+    static const int k = [] {
+        const char* v = std::getenv("BICOS_HOST_UPLOAD_STREAMS");
+        return v && std::atoi(v) == 1 ? 1 : 2;
+    }();
+    return k;
+}
+bool host_trace() {
+    static const bool on = std::getenv("BICOS_HOST_TRACE") != nullptr;
+    return on;
+}
+
+// One match_host call: its arguments, the band plan, the buffers, and the steps in the
+// order match_host runs them.
+struct HostMatch {
+    bicos_engine* e;
+    const void* const* p0;
+    const size_t* steps0;
+    const void* const* p1;
+    const size_t* steps1;
+    int n, rows, cols, depth;
+    const BicosConfig& cfg;
+    bool has_nxcorr;
+    float threshold;
+    void* disp;
+    void* corr;
+    const DispRange* range;
+
+    hipStream_t cs, ks;  // compute, copy
+    const bool dl_bands = download_by_band();
+    const int up_streams = upload_streams();
+    // the band plan (plan_bands)
+    size_t row_bytes = 0, band_bytes = 0, dsz = 0, csz = 0, disp_bytes = 0, corr_bytes = 0;
+    int band_rows = 0, B = 0, K = 0;
+    // the stage: band-major stacks | disparity | corrmap (carve)
+    char *dev = nullptr, *dev_disp = nullptr, *dev_corr = nullptr;
+    char *hout_d = nullptr, *hout_c = nullptr;  // pinned maps (dl_bands)
+
+    // BICOS_HOST_TRACE=1: per-phase host timestamps on stderr (tools/host_bench.py)
+    const bool trace = host_trace();
+    const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> dma_ev;
+    void stamp(const char* what, int b) const {
+        if (!trace) return;
+        const double us = std::chrono::duration<double, std::micro>(
+                              std::chrono::steady_clock::now() - t_start).count();
+        std::fprintf(stderr, "[bicos host] %8.1f us  %s %d\n", us, what, b);
+    }
+
+    // Row bands (every stage is row-local): upload of band b+1 overlaps the
+    // match of band b; ~8 bands keep the pipeline tail short without starving the search.
+    void plan_bands() {
+        const int want = rows >= 1024 ? 8 : rows >= 256 ? 4 : rows >= 64 ? 2 : 1;
+        band_rows = (rows + want - 1) / want;
+        B = (rows + band_rows - 1) / band_rows;
+        K = B > 1 ? 3 : 1;  // pinned slots in flight
+        row_bytes = (size_t)cols * depth;
+        band_bytes = 2 * (size_t)n * band_rows * row_bytes;
+        dsz = has_nxcorr ? 4 : 2;
+        csz = cfg.precision ? 8 : 4;
+        disp_bytes = (size_t)rows * cols * dsz;
+        corr_bytes = corr ? (size_t)rows * cols * csz : 0;
+    }
+    int band_height(int b) const { return std::min(band_rows, rows - b * band_rows); }
+
+    void carve(Lease& stage) {
+        dev = stage.take((size_t)B * band_bytes);
+        dev_disp = stage.take(disp_bytes);
+        dev_corr = corr ? stage.take(corr_bytes) : nullptr;
+    }
+
+    // pinned slots, events, streams and the pool, each on first use / grown only
+    int ensure_resources() {
+        int rc = grow_pinned(e->pinned, (size_t)K * band_bytes, "hipHostMalloc(staging)");
+        if (!rc) rc = grow_events(e->events, B);
+        if (rc) return rc;
+        if (!e->pool) {
+            // gather threads (BICOS_HOST_THREADS, default 8): the gathers compete with the DMA
+            // for host memory bandwidth; 16 threads measured slower than 3-8 (tools/host_bench.py)
+            const unsigned hw = std::thread::hardware_concurrency();
+            const char* th = std::getenv("BICOS_HOST_THREADS");
+            const unsigned cap = th ? (unsigned)std::max(1, std::atoi(th)) : 8u;
+            e->pool.reset(new HostPool((int)std::max(1u, std::min(cap, hw ? hw : 1u))));
+        }
+        if (up_streams == 2) {
+            rc = ensure_stream(e->copy_stream2);
+            if (!rc) rc = grow_events(e->events2, B);
+            // earlier calls (possibly on other streams) may still read the stage / workspace
+            if (!rc)
+                rc = check_hip(hipStreamWaitEvent(e->copy_stream2, e->ws_ready, 0),
+                               "hipStreamWaitEvent");
+            if (rc) return rc;
+        }
+        if (dl_bands) {
+            rc = ensure_stream(e->dl_stream);
+            if (!rc)
+                rc = grow_pinned(e->pinned_out, align_up(disp_bytes) + corr_bytes,
+                                 "hipHostMalloc(map staging)");
+            if (!rc) rc = grow_events(e->dl_events, 2 * B);
+            if (rc) return rc;
+            hout_d = (char*)e->pinned_out.p;
+            hout_c = corr ? hout_d + align_up(disp_bytes) : nullptr;
+        }
+        return BICOS_OK;
+    }
+
+    // band b: gather its 2n planes into a pinned slot, upload the slot, match it
+    int upload_and_match(int b) {
+        const int r0 = b * band_rows, br = band_height(b);
+        const size_t plane = (size_t)br * row_bytes;
+        char* slot = (char*)e->pinned.p + (size_t)(b % K) * band_bytes;
+        int rc = BICOS_OK;
+        if (b >= K) {
+            rc = check_hip(hipEventSynchronize(e->events[b - K]), "hipEventSynchronize");
+            if (!rc && up_streams == 2)
+                rc = check_hip(hipEventSynchronize(e->events2[b - K]), "hipEventSynchronize");
+            if (rc) return rc;
+        }
+        char* band = dev + (size_t)b * band_bytes;
+        // 2n planes -> slot [2n][br][cols], dense
+        const std::function<void(int)> copy = [&](int i) {
+            const bool right = i >= n;
+            const int t = right ? i - n : i;
+            const size_t step = right ? (steps1 ? steps1[t] : row_bytes)
+                                      : (steps0 ? steps0[t] : row_bytes);
+            const char* src = (const char*)(right ? p1[t] : p0[t]) + (size_t)r0 * step;
+            char* dst = slot + (size_t)i * plane;
+            if (step == row_bytes) {
+                std::memcpy(dst, src, plane);
+            } else {
+                for (int r = 0; r < br; ++r)
+                    std::memcpy(dst + (size_t)r * row_bytes, src + (size_t)r * step, row_bytes);
+            }
+        };
+        stamp("slot free", b);
+        e->pool->run(2 * n, copy);
+        stamp("gathered", b);
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        if (trace) {
+            (void)hipEventCreate(&t0);
+            (void)hipEventCreate(&t1);
+            (void)hipEventRecord(t0, ks);
+        }
+        const size_t up = 2 * (size_t)n * plane;
+        const size_t first = up_streams == 2 ? (up / 2 + 4095) / 4096 * 4096 : up;
+        rc = check_hip(hipMemcpyAsync(band, slot, first, hipMemcpyHostToDevice, ks), "stack upload");
+        if (!rc && first < up) {
+            rc = check_hip(hipMemcpyAsync(band + first, slot + first, up - first,
+                                          hipMemcpyHostToDevice, e->copy_stream2), "stack upload");
+            if (!rc) rc = check_hip(hipEventRecord(e->events2[b], e->copy_stream2), "hipEventRecord");
+            if (!rc) rc = check_hip(hipStreamWaitEvent(cs, e->events2[b], 0), "hipStreamWaitEvent");
+        }
+        if (trace) {
+            (void)hipEventRecord(t1, ks);
+            dma_ev.push_back({t0, t1});
+        }
+        if (!rc) rc = check_hip(hipEventRecord(e->events[b], ks), "hipEventRecord");
+        if (!rc) rc = check_hip(hipStreamWaitEvent(cs, e->events[b], 0), "hipStreamWaitEvent");
+        if (rc) return rc;
+        return match_device(e, band, band + (size_t)n * plane, n, br, cols, (size_t)cols,
+                            (size_t)br * cols, depth, cfg, has_nxcorr, threshold,
+                            dev_disp + (size_t)r0 * cols * dsz,
+                            dev_corr ? dev_corr + (size_t)r0 * cols * csz : nullptr, cs, false,
+                            nullptr, nullptr, range);
+    }
+
+    // band b's rows of the maps into pinned memory, as soon as they are matched (dl_bands)
+    int download_band(int b) {
+        const int r0 = b * band_rows, br = band_height(b);
+        hipStream_t ds = e->dl_stream;
+        const size_t od = (size_t)r0 * cols * dsz, oc = (size_t)r0 * cols * csz;
+        int rc = check_hip(hipEventRecord(e->dl_events[2 * b], cs), "hipEventRecord");
+        if (!rc) rc = check_hip(hipStreamWaitEvent(ds, e->dl_events[2 * b], 0), "hipStreamWaitEvent");
+        if (!rc)
+            rc = check_hip(hipMemcpyAsync(hout_d + od, dev_disp + od, (size_t)br * cols * dsz,
+                                          hipMemcpyDeviceToHost, ds), "download");
+        if (!rc && corr)
+            rc = check_hip(hipMemcpyAsync(hout_c + oc, dev_corr + oc, (size_t)br * cols * csz,
+                                          hipMemcpyDeviceToHost, ds), "download");
+        if (!rc) rc = check_hip(hipEventRecord(e->dl_events[2 * b + 1], ds), "hipEventRecord");
+        return rc;
+    }
+
+    // band b from pinned memory into the caller's buffers once it has landed (the pool: row
+    // chunks of both maps)
+    int deliver_band(int b) {
+        int rc = check_hip(hipEventSynchronize(e->dl_events[2 * b + 1]), "hipEventSynchronize");
+        if (rc) return rc;
+        const int r0 = b * band_rows, br = band_height(b);
+        const int parts = 8;
+        const std::function<void(int)> out = [&](int i) {
+            const bool c = i >= parts;
+            if (c && !corr) return;
+            const size_t esz = c ? csz : dsz;
+            const size_t bytes = (size_t)br * cols * esz;
+            const size_t chunk = (bytes / parts + 63) / 64 * 64;
+            const size_t o = (size_t)(i % parts) * chunk;
+            if (o >= bytes) return;
+            const size_t base = (size_t)r0 * cols * esz + o;
+            std::memcpy((char*)(c ? corr : disp) + base, (c ? hout_c : hout_d) + base,
+                        std::min(chunk, bytes - o));
+        };
+        e->pool->run(2 * parts, out);
+        return BICOS_OK;
+    }
+
+    // both maps in one copy each at the end (BICOS_HOST_DL=once)
+    int download_once() {
+        int rc = check_hip(hipMemcpyAsync(disp, dev_disp, disp_bytes, hipMemcpyDeviceToHost, cs),
+                           "download");
+        if (!rc && corr)
+            rc = check_hip(hipMemcpyAsync(corr, dev_corr, corr_bytes, hipMemcpyDeviceToHost, cs),
+                           "download");
+        return rc;
+    }
+
+    // drain every stream whatever happened: the slots and the stage are reused next call
+    int drain(int rc) {
+        const int r1 = check_hip(hipStreamSynchronize(ks), "hipStreamSynchronize");
+        if (up_streams == 2) (void)hipStreamSynchronize(e->copy_stream2);
+        const int r2 = check_hip(hipStreamSynchronize(cs), "hipStreamSynchronize");
+        const int r3 = dl_bands ? check_hip(hipStreamSynchronize(e->dl_stream), "hipStreamSynchronize")
+                                : BICOS_OK;
+        stamp("downloaded", B);
+        for (size_t i = 0; i < dma_ev.size(); ++i) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, dma_ev[i].first, dma_ev[i].second);
+            std::fprintf(stderr, "[bicos host] dma %zu: %.3f ms = %.1f GB/s\n", i, ms,
+                         band_bytes / (ms * 1e6));
+            (void)hipEventDestroy(dma_ev[i].first);
+            (void)hipEventDestroy(dma_ev[i].second);
+        }
+        return rc ? rc : (r1 ? r1 : (r2 ? r2 : r3));
+    }
+};
+
+}  // namespace
+
+int match_host(bicos_engine* e, const void* const* p0, const size_t* steps0,
+               const void* const* p1, const size_t* steps1, int n, int rows, int cols,
+               int depth, const BicosConfig& cfg, bool has_nxcorr, float threshold, void* disp,
+               void* corr, const DispRange* range) {
+    if (range)
+        if (int rc0 = check_range(range->min, range->max)) return rc0;
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    if (int rc0 = check_stack_shape(n, depth, rows, cols)) return rc0;
+    if (rows == 0 || cols == 0)  // validates the configuration, no work
+        return match_device(e, nullptr, nullptr, n, rows, cols, (size_t)cols,
+                            (size_t)rows * cols, depth, cfg, has_nxcorr, threshold, disp, corr,
+                            e->own_stream, false, nullptr, nullptr, range);
+    if (!p0 || !p1 || !disp) return fail(BICOS_E_ARG, "null buffer");
+    for (int t = 0; t < n; ++t) {
+        if (!p0[t] || !p1[t]) return fail(BICOS_E_ARG, "null image");
+        if ((steps0 && steps0[t] < (size_t)cols * depth) || (steps1 && steps1[t] < (size_t)cols * depth))
+            return fail(BICOS_E_ARG, "image step smaller than a row");
+    }
+    // (the compute stream is the engine's own, the first upload stream its copy stream)
+    HostMatch m{e, p0, steps0, p1, steps1, n, rows, cols, depth, cfg, has_nxcorr, threshold,
+                disp, corr, range, e->own_stream, e->copy_stream};
+    m.plan_bands();
+    Lease stage(e, e->stage, e->stage_bytes, m.ks);
+    m.carve(stage);
+    int rc = stage.acquire();
+    if (!rc) rc = m.ensure_resources();
+    if (rc) return rc;
+    m.carve(stage);
+    for (int b = 0; b < m.B && !rc; ++b) {
+        rc = m.upload_and_match(b);
+        if (!rc && m.dl_bands) rc = m.download_band(b);
+    }
+    m.stamp("bands queued", m.B);
+    if (m.trace) {
+        (void)hipStreamSynchronize(m.cs);
+        m.stamp("bands matched", m.B);
+    }
+    for (int b = 0; b < m.B && !rc && m.dl_bands; ++b) rc = m.deliver_band(b);
+    if (!rc && !m.dl_bands) rc = m.download_once();
+    return m.drain(rc);
+}
+
+}  // namespace bicos_impl

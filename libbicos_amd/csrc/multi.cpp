@@ -64,19 +64,14 @@ struct FirstError {
     int raise() { return code == BICOS_OK ? BICOS_OK : fail(code, msg); }
 };
 
-// Stage slots of one band's maps, appended at `off` (which advances past them): the
-// disparity map, then (csz != 0) the corrmap, each 256-byte aligned with 256 bytes of slack.
-// The reservation and the enqueue loop of bicos_match_bands_device both walk the bands with
-// this one function, so the bytes reserved always cover the offsets written.
-void band_stage_offsets(size_t& off, int rows, int cols, size_t dsz, size_t csz, size_t* od,
-                        size_t* oc) {
-    auto slot = [&](size_t bytes) {
-        const size_t at = off;
-        off = (off + bytes + 256 + 255) / 256 * 256;
-        return at;
-    };
-    *od = slot((size_t)rows * cols * dsz);
-    *oc = csz ? slot((size_t)rows * cols * csz) : 0;
+// Stage slots of one band's maps, taken from its device's lease: the disparity map, then
+// (csz != 0) the corrmap, each with 256 bytes of slack. The reservation and the enqueue loop
+// of bicos_match_bands_device both walk the bands with this one function, so the bytes
+// reserved always cover the slots written.
+void band_stage_slots(Lease& stage, int rows, int cols, size_t dsz, size_t csz, char** sd,
+                      char** sc) {
+    *sd = stage.take((size_t)rows * cols * dsz + 256);
+    *sc = csz ? stage.take((size_t)rows * cols * csz + 256) : nullptr;
 }
 
 // Let `peer` read and write memory of `owner`'s default stream-ordered pool (hipMallocAsync,
@@ -112,11 +107,6 @@ bool enable_peer_path(int dev, int root) {
     return ok;
 }
 
-float nxc_threshold(const BicosConfig& cfg) {
-    // reference src/pybicos_c.cpp:59-61: a negative threshold keeps the default 0.5
-    return cfg.nxcorr_threshold >= 0 ? cfg.nxcorr_threshold : 0.5f;
-}
-
 }  // namespace
 }  // namespace bicos_impl
 
@@ -127,11 +117,8 @@ extern "C" int bicos_match_host_multi(const int* devices, int ndev, const void* 
                                       size_t step, int depth, const BicosConfig* cfg,
                                       int has_nxcorr, void* disparity, void* corrmap) {
     if (!cfg) return fail(BICOS_E_ARG, "null config");
-    if (n < 2) return fail(BICOS_E_ARG, "need at least two images");
-    if (depth != 1 && depth != 2)
-        return fail(BICOS_E_ARG, "bad input depths, only CV_8UC1 and CV_16UC1 are supported");
-    if (rows < 0 || cols < 0) return fail(BICOS_E_ARG, "negative image size");
-    try {
+    if (int rc0 = check_stack_shape(n, depth, rows, cols)) return rc0;
+    return guarded([&]() -> int {
         int rc = check_devices(devices, ndev);
         if (rc) return rc;
         const int bands = std::max(1, std::min(ndev, rows));
@@ -141,11 +128,11 @@ extern "C" int bicos_match_host_multi(const int* devices, int ndev, const void* 
         const float thr = nxc_threshold(*cfg);
         FirstError err;
         auto run = [&](int b) {
-            try {
+            err.note(guarded([&]() -> int {
                 int r0 = 0, r1 = rows;
                 if (rows > 0) band_range(rows, bands, b, r0, r1);
                 bicos_engine* e = default_engine(devices[b]);
-                if (!e) return err.note(BICOS_E_HIP);
+                if (!e) return BICOS_E_HIP;
                 std::vector<const void*> p0((size_t)n), p1((size_t)n);
                 for (int t = 0; t < n; ++t) {
                     p0[t] = stack0 && stack0[t] ? (const char*)stack0[t] + (size_t)r0 * pitch : nullptr;
@@ -162,10 +149,8 @@ extern "C" int bicos_match_host_multi(const int* devices, int ndev, const void* 
                     r = match_host(e, p0.data(), steps.data(), p1.data(), steps.data(), n, r1 - r0,
                                    cols, depth, *cfg, has_nxcorr != 0, thr, d, c);
                 (void)hipSetDevice(cur);
-                err.note(r);
-            } catch (const std::exception& ex) {
-                err.note(fail(BICOS_E_INTERNAL, ex.what()));
-            }
+                return r;
+            }));
         };
         if (bands == 1) {
             run(0);
@@ -176,11 +161,7 @@ extern "C" int bicos_match_host_multi(const int* devices, int ndev, const void* 
             for (auto& t : th) t.join();
         }
         return err.raise();
-    } catch (const std::exception& ex) {
-        return fail(BICOS_E_INTERNAL, ex.what());
-    } catch (...) {
-        return fail(BICOS_E_INTERNAL, "unknown exception");
-    }
+    });
 }
 
 extern "C" int bicos_match_bands_device(const int* devices, int ndev, const void* const* stack0,
@@ -189,12 +170,10 @@ extern "C" int bicos_match_bands_device(const int* devices, int ndev, const void
                                         int n, int cols, int depth, const BicosConfig* cfg,
                                         int has_nxcorr, void* disparity, void* corrmap) {
     if (!cfg) return fail(BICOS_E_ARG, "null config");
-    if (n < 2) return fail(BICOS_E_ARG, "need at least two images");
-    if (depth != 1 && depth != 2) return fail(BICOS_E_ARG, "bad input depth");
-    if (cols < 0) return fail(BICOS_E_ARG, "negative image size");
+    if (int rc0 = check_stack_shape(n, depth, 0, cols)) return rc0;  // (rows: band_rows below)
     if (!stack0 || !stack1 || !band_rows || !row_pitch || !plane_pitch)
         return fail(BICOS_E_ARG, "null band array");
-    try {
+    return guarded([&]() -> int {
         int rc = check_devices(devices, ndev);
         if (rc) return rc;
         long rows = 0;
@@ -223,14 +202,16 @@ extern "C" int bicos_match_bands_device(const int* devices, int ndev, const void
         // band 0 (on the root) writes straight into the maps; every other band's maps go to
         // its engine's stage and are peer-copied (a band placed on the root again -- devices
         // may repeat -- takes the same path with a device-local copy)
-        // stage layout per device: the same offsets the enqueue loop below takes
-        // (band_stage_offsets), so the reservation covers the last byte written
-        std::map<int, size_t> stage_need;
+        // one lease of the stage per device: sized by the same slots the enqueue loop below
+        // takes (band_stage_slots), so the reservation covers the last byte written
+        std::map<int, Lease> stages;
         std::map<int, int> copies;  // bands per device (host-staged copies: one event each)
+        char *sd = nullptr, *sc = nullptr;
         for (int b = 1; b < ndev; ++b) {
-            size_t sd = 0, sc = 0;
-            band_stage_offsets(stage_need[devices[b]], band_rows[b], cols, dsz, corrmap ? csz : 0,
-                               &sd, &sc);
+            bicos_engine* e = engines[devices[b]];
+            Lease& stage = stages.try_emplace(e->device, e, e->stage, e->stage_bytes, e->own_stream)
+                               .first->second;
+            band_stage_slots(stage, band_rows[b], cols, dsz, corrmap ? csz : 0, &sd, &sc);
             ++copies[devices[b]];
         }
         // per device: true = direct peer DMA into the root's maps (or a device-local copy on
@@ -240,28 +221,17 @@ extern "C" int bicos_match_bands_device(const int* devices, int ndev, const void
         // one-GPU test of that path, tests/test_multi_gpu.py)
         const bool force_host = std::getenv("BICOS_GATHER_HOST") != nullptr;
         std::map<int, bool> direct;
-        for (auto& kv : stage_need) {
+        for (auto& kv : stages) {
             bicos_engine* e = engines[kv.first];
-            rc = reserve(e->stage, e->stage_bytes, kv.second, e->device, e->own_stream, e->ws_ready);
-            if (!rc) rc = check_hip(hipSetDevice(e->device), "hipSetDevice");
-            if (!rc) rc = check_hip(hipStreamWaitEvent(e->own_stream, e->ws_ready, 0), "hipStreamWaitEvent");
+            const size_t need = kv.second.needed();
+            rc = check_hip(hipSetDevice(e->device), "hipSetDevice");
+            if (!rc) rc = kv.second.acquire();
             direct[e->device] = !force_host && (e->device == root || (!rc && enable_peer_path(e->device, root)));
             if (!rc && !direct[e->device]) {
                 // the host-staged gather: the stage layout mirrored in this engine's pinned
                 // buffer, one event per band for the root's stream to wait on
-                if (e->gather_pinned_bytes < kv.second) {
-                    if (e->gather_pinned) (void)hipHostFree(e->gather_pinned);
-                    e->gather_pinned = nullptr;
-                    e->gather_pinned_bytes = 0;
-                    rc = check_hip(hipHostMalloc(&e->gather_pinned, kv.second, hipHostMallocDefault),
-                                   "hipHostMalloc(gather staging)");
-                    if (!rc) e->gather_pinned_bytes = kv.second;
-                }
-                while (!rc && (int)e->gather_events.size() < copies[e->device]) {
-                    hipEvent_t ev;
-                    rc = check_hip(hipEventCreateWithFlags(&ev, hipEventDisableTiming), "hipEventCreate");
-                    if (!rc) e->gather_events.push_back(ev);
-                }
+                rc = grow_pinned(e->gather_pinned, need, "hipHostMalloc(gather staging)");
+                if (!rc) rc = grow_events(e->gather_events, copies[e->device]);
             }
             if (rc) {
                 (void)hipSetDevice(cur);
@@ -271,7 +241,6 @@ extern "C" int bicos_match_bands_device(const int* devices, int ndev, const void
         bicos_engine* re = engines[root];
         std::map<int, int> ev_used;
         // enqueue every band (asynchronous per device), then drain
-        std::map<int, size_t> used;
         long r0 = 0;
         for (int b = 0; b < ndev && rc == BICOS_OK; ++b) {
             const int br = band_rows[b];
@@ -291,10 +260,8 @@ extern "C" int bicos_match_bands_device(const int* devices, int ndev, const void
                                   depth, *cfg, has_nxcorr != 0, thr, dst_d, dst_c, e->own_stream);
                 continue;
             }
-            size_t od = 0, oc = 0;
-            band_stage_offsets(used[devices[b]], br, cols, dsz, corrmap ? csz : 0, &od, &oc);
-            char* sd = (char*)e->stage + od;
-            char* sc = corrmap ? (char*)e->stage + oc : nullptr;
+            Lease& stage = stages.at(e->device);
+            band_stage_slots(stage, br, cols, dsz, corrmap ? csz : 0, &sd, &sc);
             rc = match_device(e, stack0[b], stack1[b], n, br, cols, row_pitch[b], plane_pitch[b],
                               depth, *cfg, has_nxcorr != 0, thr, sd, sc, e->own_stream);
             const size_t bd = (size_t)br * cols * dsz, bc = (size_t)br * cols * csz;
@@ -308,8 +275,8 @@ extern "C" int bicos_match_bands_device(const int* devices, int ndev, const void
                 continue;
             }
             // host-staged: down on the band's stream, up on the root's once that is done
-            char* hd = (char*)e->gather_pinned + od;
-            char* hc = corrmap ? (char*)e->gather_pinned + oc : nullptr;
+            char* hd = (char*)e->gather_pinned.p + (sd - stage.base());
+            char* hc = corrmap ? (char*)e->gather_pinned.p + (sc - stage.base()) : nullptr;
             hipEvent_t ev = e->gather_events[ev_used[e->device]++];
             if (!rc) rc = check_hip(hipMemcpyAsync(hd, sd, bd, hipMemcpyDeviceToHost, e->own_stream), "gather (download)");
             if (!rc && corrmap)
@@ -325,15 +292,11 @@ extern "C" int bicos_match_bands_device(const int* devices, int ndev, const void
         for (auto& kv : engines) {
             bicos_engine* e = kv.second;
             (void)hipSetDevice(e->device);
-            (void)hipEventRecord(e->ws_ready, e->own_stream);
+            if (stages.count(e->device)) stages.at(e->device).release();
             const int r = check_hip(hipStreamSynchronize(e->own_stream), "hipStreamSynchronize");
             if (!rc) rc = r;
         }
         (void)hipSetDevice(cur);
         return rc;
-    } catch (const std::exception& ex) {
-        return fail(BICOS_E_INTERNAL, ex.what());
-    } catch (...) {
-        return fail(BICOS_E_INTERNAL, "unknown exception");
-    }
+    });
 }

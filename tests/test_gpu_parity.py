@@ -1094,6 +1094,44 @@ def test_one_engine_alternating_streams(gpu, oracle):
         same(host(c), refs[f][1])
 
 
+def test_one_engine_rotating_entries_and_streams(oracle):
+    """One fresh engine, no host synchronisation in between: matches, the Consistency search
+    entry and the ranged search entry rotate over three streams, the workspace growing in the
+    middle (the 33-image match). Every user of the workspace takes the same lease
+    (engine.hpp Lease), so each call waits for the one before it whatever its stream."""
+    import torch
+    from libbicos_amd import device
+    from tests.test_range_api import rolled_descriptors, search_range
+    cfg = dict(nxcorr_threshold=0.9)
+    small, big = stereo_stack(8, 48, 640, seed=31), stereo_stack(33, 40, 1300, seed=32)
+    a0, a1 = rolled_descriptors(16, 200, 4, period=97)
+    b0, b1 = rolled_descriptors(24, 700, 8)
+    want = {"small": oracle.match(*small, oracle.OracleConfig(**cfg)),
+            "big": oracle.match(*big, oracle.OracleConfig(**cfg)),
+            "search": oracle.search(a0, a1, 3, 2),
+            "ranged": search_range(b0, b1, 2, -30, 25, 1)}
+    ds, db = [dev(x) for x in small], [dev(x) for x in big]
+    ga, gb = [dev(_pack(x)) for x in (a0, a1)], [dev(_pack(x)) for x in (b0, b1)]
+    eng = device.Engine()
+    calls = {"small": lambda: eng.match(ds[0], ds[1], device.MatchConfig(**cfg)),
+             "big": lambda: eng.match(db[0], db[1], device.MatchConfig(**cfg)),
+             "search": lambda: eng.search(ga[0], ga[1], 200, 4, 3, 2),
+             "ranged": lambda: eng.search(gb[0], gb[1], 700, 8, 2, 1, disparity_range=(-30, 25))}
+    streams = [torch.cuda.current_stream(), torch.cuda.Stream(), torch.cuda.Stream()]
+    outs = []
+    torch.cuda.synchronize()
+    for k, name in enumerate(["small", "search", "ranged", "big", "small", "search", "ranged"]):
+        with torch.cuda.stream(streams[k % 3]):
+            outs.append((name, calls[name]()))
+    torch.cuda.synchronize()
+    for name, out in outs:
+        if isinstance(out, tuple):
+            same(host(out[0]), want[name][0])
+            same(host(out[1]), want[name][1])
+        else:
+            same(host(out), want[name])
+
+
 def test_device_outputs_are_validated(gpu):
     import torch
     from libbicos_amd.device import MatchConfig

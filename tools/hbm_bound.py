@@ -73,7 +73,7 @@ def main():
     AC = [torch.empty(P, dtype=torch.float32, device="cuda") for _ in range(K)]
     sink = torch.zeros(1 << 20, dtype=torch.int32, device="cuda")
 
-    # the product kernels through the C-ABI stage entries directly (engine.cpp), arguments
+    # the product kernels through the C-ABI stage entries directly (entries.cpp), arguments
     # precomputed: the Python wrappers' checks would make the loop host-bound
     Lb = eng._L
     sv = st.cuda_stream

@@ -1,6 +1,6 @@
 """How fast do pageable host buffers move over PCIe through hipMemcpyAsync, and does the
 call block the host? (the host path's breakdown.) The banded host pipeline
-(engine.cpp match_host) gathers the caller's images into pinned slots first; this probe
+(host.cpp match_host) gathers the caller's images into pinned slots first; this probe
 times the alternative -- the DMA straight from the caller's (pageable) images.
 
   python tools/host_dma_probe.py [--config cfg2] [--reps 5]
