@@ -177,6 +177,12 @@ static bool fuse_agree() {
     static const bool on = env_on("BICOS_FUSE_AGREE");
     return on;
 }
+// The right row streamed through LDS in half-chunk stages by the 128-bit NoDuplicates search
+// (search_mx.hip search_mx_kernel ST; BICOS_MX_STREAM=0: the chunk loop; read once)
+static bool stream_search() {
+    static const bool on = env_on("BICOS_MX_STREAM");
+    return on;
+}
 // Consistency's left-right check inside the agree launch (kernels.hip agree_lds_kernel CONS;
 // BICOS_FUSE_CONS=0: consistency_kernel + the agree; read once)
 static bool fuse_consistency() {
@@ -213,9 +219,11 @@ static bicos_hip::MxGeometry mx_geometry(const bicos_engine* e, int rows, int co
     const bool tuned = e && e->tune_variant >= 64;
     // tuned: split = LDS stage KiB (0 = 64)
     const int lds = tuned && e->tune_split > 0 ? e->tune_split * 1024 : 64 * 1024;
-    return bicos_hip::search_mx_geometry(rows, cols, words, lds, tuned ? e->tune_R : 0,
-                                         tuned ? e->tune_waves : 0, e ? e->cus : 256,
-                                         tuned ? e->tune_variant - 64 : 0, bits);
+    bicos_hip::MxGeometry g = bicos_hip::search_mx_geometry(
+        rows, cols, words, lds, tuned ? e->tune_R : 0, tuned ? e->tune_waves : 0, e ? e->cus : 256,
+        tuned ? e->tune_variant - 64 : 0, bits);
+    g.stream = stream_search() ? 1 : 0;
+    return g;
 }
 
 // Number of x the reference's subpixel loop visits: for (float x = -1.f; x <= 1.f; x += step)

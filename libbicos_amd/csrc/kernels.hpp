@@ -143,6 +143,10 @@ struct MxGeometry {
     int pk_chunk;
     int pk_tiles_per_row;
     int pk_tail_col0;       // cols: no tail; else one workgroup per row of 1 wide tile per wave
+    // 1 (search_mx_geometry's default): the 128-bit any-order NoDuplicates search streams the
+    // row's chunks after a workgroup's own through LDS in half-chunk stages where its shape
+    // allows (search_mx.hip search_mx_kernel ST); 0: the chunk loop
+    int stream;
 };
 // bits: highest used descriptor bit + 1 when the bits above are known to be zero (0 =
 // all of them)

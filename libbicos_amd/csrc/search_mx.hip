@@ -404,10 +404,29 @@ template <> struct SearchKArgs<true> { using type = SearchAgreeArgs; };
 __device__ __forceinline__ const SearchArgs& search_part(const SearchArgs& k) { return k; }
 __device__ __forceinline__ const SearchArgs& search_part(const SearchAgreeArgs& k) { return k.s; }
 
-template <int WORDS, int KSU, bool NODUPES, int T, int KEYS, bool TAIL, bool LIST, bool AG = false>
+// ST (streamed right row; KEYS 2, 128-bit descriptors in 2 K-steps, every col0 of the row, no
+// tail; the launcher guarantees chunk = 2 * blockDim.x and cols > chunk). The workgroup's own
+// chunk is expanded whole, as without ST, and every wave scans it from its own col0. The rest
+// of the row then comes in stages of half a chunk = one col1 per thread, alternating between
+// the two halves of the chunk region:
+//  * the raw descriptor of a thread's column of the NEXT stage is requested before the block
+//    loop over the current one and held in four VGPRs, so its latency runs under that loop
+//    (the own chunk's loads go out ahead of the left B-fragment loads);
+//  * a wave that is done with stage s expands its columns of stage s + 1 into the other half
+//    at once -- every wave left that half's previous stage before the barrier that published
+//    s -- and ONE barrier then publishes s + 1 and retires s. Only the step from the own chunk
+//    (which fills both halves) to the first stage takes two.
+// Without ST every chunk costs barrier -> loads -> expansion -> barrier with no wave of the
+// workgroup multiplying. The stages run downwards from the own chunk (wrapping), upper half
+// first; any order gives the same minima (KEYS 2).
+template <int WORDS, int KSU, bool NODUPES, int T, int KEYS, bool TAIL, bool LIST, bool AG = false,
+          bool ST = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(KSU >= 4 ? 3 : 4)))
 void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
     const SearchArgs& a = search_part(ka);
+    constexpr bool STREAM = ST;
+    static_assert(!ST || (KEYS == 2 && T % 2 == 0 && WORDS == 4 && KSU == 2 && !TAIL && !LIST),
+                  "ST: the 128-bit any-order NoDuplicates search over every col0");
     constexpr bool FK = KEYS == 3;
     static_assert(!FK || !NODUPES, "FK keys: first minimum only");
     constexpr bool XK = KEYS == 1 || KEYS == 2;
@@ -471,6 +490,34 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
 
     const uint32_t* __restrict__ row0 = a.desc0 + (size_t)row * a.desc_pitch;
     const uint32_t* __restrict__ row1 = a.desc1 + (size_t)row * a.desc_pitch;
+
+    // ST: the raw right descriptor of col1 (zero past the image), and the own chunk's two
+    // columns of this thread, requested ahead of the B-fragment loads below
+    auto raw_col = [&](int c1) {
+        v4i x = {0, 0, 0, 0};
+        if (c1 < cols) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) x[w] = (int)row1[(size_t)c1 * WORDS + w];
+        }
+        return x;
+    };
+    auto put_col = [&](int c, const v4i& x) {  // LDS column c of the chunk region
+#pragma unroll
+        for (int w = 0; w < 4; ++w) lds_mx[w * chunk + c] = expand_bits((uint32_t)x[w], LUT_A);
+    };
+    // this thread's index, recomputed where it is used (a register less across the block loops)
+    auto thread_index = [&]() {
+        int l;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        return 64 * wave + l;
+    };
+    const int half = chunk >> 1;
+    const int own_chunk = (min(cols, c0_base + (tile + 1) * waves * T * 32) - 1) / chunk;
+    v4i raw = {0, 0, 0, 0}, raw_hi = {0, 0, 0, 0};
+    if constexpr (STREAM) {
+        raw = raw_col(own_chunk * chunk + (int)threadIdx.x);
+        raw_hi = raw_col(own_chunk * chunk + half + (int)threadIdx.x);
+    }
 
     // B fragments: +1 (0x2) where the left bit is 0, -1 (0xA) where it is 1
     v4i bf[T][KS];
@@ -626,32 +673,67 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
     // FREE: chunks downwards from the one holding the workgroup's highest col0
     int cstart = 0;
     if constexpr (FREE) cstart = start_col(c0_base + (tile + 1) * waves * T * 32, REV_AHEAD_CHUNK) / chunk;
-    for (int k = 0; k < nchunks; ++k) {
-        int ci = FREE ? cstart - k : k;
+    // ST: streamed stage s (after the own chunk) starts at col1 stage_base(s) and lives in
+    // half s & 1 of the chunk region; 2 (nchunks - 1) of them, the last chunk's possibly
+    // short or empty (they still take their barrier: workgroup-uniform)
+    auto stage_base = [&](int s) {
+        int ci = own_chunk - 1 - (s >> 1);
         if (ci < 0) ci += nchunks;
-        const int base = ci * chunk;
-        const int ncols = min(chunk, cols - base);
+        return ci * chunk + ((s & 1) ? 0 : half);
+    };
+    const int nstages = STREAM ? 2 * (nchunks - 1) : 0;
+    const int nsteps = STREAM ? 1 + nstages : nchunks;
+    if constexpr (STREAM) {
+        put_col((int)threadIdx.x, raw);
+        put_col(half + (int)threadIdx.x, raw_hi);
+    }
+    for (int k = 0; k < nsteps; ++k) {
+        // this step's columns: col1 base + c for LDS column c, from LDS block b0, ncols of them
+        int base, ncols, b0 = 0;
 #if defined(BICOS_MX_DIAG) && BICOS_MX_DIAG == 3  // timing only: expand the first chunk only
         const bool expand = k == 0;
 #else
         constexpr bool expand = true;
 #endif
-        if (k && expand) __syncthreads();
-        // expand the chunk's right descriptors: one col1 per thread, all its words
-        for (int c = threadIdx.x; expand && c < chunk; c += blockDim.x) {
-            const int c1 = base + c;
-#pragma unroll
-            for (int w = 0; w < WL; ++w) {
-                uint32_t x = 0;
-                if (c1 < cols && w < WORDS) x = row1[(size_t)c1 * WORDS + w];
-                if (WORDS == 8 && KS == 4 && w == 7) x &= 0x7FFFFFFFu;
-                if (FK && w == WL - 1)  // (the descriptors leave this slot 0: host check)
-                    lds_mx[w * chunk + c] = fk_digits(c1 & 31);
-                else
-                    lds_mx[w * chunk + c] = expand_bits(x, LUT_A);
+        if constexpr (STREAM) {
+            if (k == 0) {
+                base = own_chunk * chunk;
+                ncols = min(chunk, cols - base);
+            } else {
+                const int sbase = stage_base(k - 1);
+                b0 = ((k - 1) & 1) ? half >> 5 : 0;
+                base = sbase - 32 * b0;
+                ncols = max(0, min(half, cols - sbase));
             }
+            if (expand) {
+                if (k == 1) __syncthreads();  // every wave is done with the own chunk
+                const int tid = thread_index();
+                if (k >= 1) put_col(32 * b0 + tid, raw);
+                if (k < nstages) raw = raw_col(stage_base(k) + tid);  // the next stage's
+                __syncthreads();
+            }
+        } else {
+            int ci = FREE ? cstart - k : k;
+            if (ci < 0) ci += nchunks;
+            base = ci * chunk;
+            ncols = min(chunk, cols - base);
+            if (k && expand) __syncthreads();
+            // expand the chunk's right descriptors: one col1 per thread, all its words
+            for (int c = threadIdx.x; expand && c < chunk; c += blockDim.x) {
+                const int c1 = base + c;
+#pragma unroll
+                for (int w = 0; w < WL; ++w) {
+                    uint32_t x = 0;
+                    if (c1 < cols && w < WORDS) x = row1[(size_t)c1 * WORDS + w];
+                    if (WORDS == 8 && KS == 4 && w == 7) x &= 0x7FFFFFFFu;
+                    if (FK && w == WL - 1)  // (the descriptors leave this slot 0: host check)
+                        lds_mx[w * chunk + c] = fk_digits(c1 & 31);
+                    else
+                        lds_mx[w * chunk + c] = expand_bits(x, LUT_A);
+                }
+            }
+            if (expand) __syncthreads();
         }
-        if (expand) __syncthreads();
         if (idle) continue;
 
         const int nfull = ncols / 32;
@@ -735,6 +817,28 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
         // the block reaching past the image (last chunk): A = 0 there, so D1 = KEY_PAD,
         // D2 = 0 never win. Ascending orders take it last, FREE first.
         auto partial_block = [&](const v16f& cb) {
+            if constexpr (STREAM && PAIRS) {
+                // (no second C matrix, whose 16 registers would spill beside `raw`: the rows
+                // past the image are set to KEY_PAD after the products -- the same D)
+                const int b = b0 + nfull, B = base + 32 * b;
+                v4i af[KS];
+#pragma unroll
+                for (int s = 0; s < KS; ++s) af[s] = lds_mx[(2 * s + h) * chunk + 32 * b + j];
+#pragma unroll
+                for (int p = 0; p < T / 2; ++p) {
+                    products(0, af, af, cb, cb, 2 * p);
+                    products(1, af, af, cb, cb, 2 * p + 1);
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const bool in = 32 * nfull + rrow(r) < ncols;
+                        d[0][r] = in ? d[0][r] : KEY_PAD;
+                        d[1][r] = in ? d[1][r] : KEY_PAD;
+                    }
+                    pair_reduce(p, B, d[0], d[1]);
+                }
+                bprev = B;
+                return;
+            }
             v16f c1, c2;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -742,12 +846,13 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
                 c1[r] = in ? cb[r] : KEY_PAD;
                 c2[r] = in ? cb[r] : 0.f;
             }
-            block(nfull, c1, c2);
+            block(b0 + nfull, c1, c2);
         };
         if constexpr (FREE) {
             if (partial) partial_block(cc);
             // full blocks downwards from the one holding the wave's highest col0 (clamped)
-            const int sb = max(0, min(nfull - 1, (start_col(c0_wave + 32 * T, REV_AHEAD) - base) / 32));
+            // (block indices below are relative to the step's first LDS block b0)
+            const int sb = max(0, min(nfull - 1, (start_col(c0_wave + 32 * T, REV_AHEAD) - base - 32 * b0) / 32));
 #if !defined(BICOS_MX_DIAG) || BICOS_MX_DIAG >= 3
             if constexpr (PIPE) {
                 // software pipeline over the blocks (one tile pair per wave): the products of
@@ -758,6 +863,7 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
                 auto issue = [&](int i, v16f* dd) {
                     int b = sb - i;
                     if (b < 0) b += nfull;
+                    b += b0;
                     v4i af[KS];
 #pragma unroll
                     for (int s = 0; s < KS; ++s) af[s] = lds_mx[(2 * s + h) * chunk + 32 * b + j];
@@ -787,7 +893,7 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
             } else if constexpr (PREFETCH) {
                 auto bidx = [&](int i) {
                     int b = sb - i;
-                    return b < 0 ? b + nfull : b;
+                    return b0 + (b < 0 ? b + nfull : b);
                 };
                 v4i af[KS];
                 if (nfull > 0) load_af(af, bidx(0));
@@ -797,7 +903,7 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
             for (int i = 0; i < nfull; ++i) {
                 int b = sb - i;
                 if (b < 0) b += nfull;
-                block(b, cc, cc);
+                block(b0 + b, cc, cc);
             }
         } else if constexpr ((XK || FK) && PREFETCH) {
             v4i af[KS];
@@ -1703,13 +1809,22 @@ hipError_t launch_pk_w(const SearchArgs& a, const MxGeometry& g, hipStream_t st)
     return hipErrorInvalidValue;
 }
 
-template <int WORDS, int KSU, bool NODUPES, int T, int KEYS, bool TAIL, bool LIST = false, bool AG = false>
+// Whether a main launch takes the streamed kernel (search_mx_kernel ST): asked for
+// (MxGeometry.stream), more than one chunk per row, and a stage of half a chunk = one col1
+// per thread (1024-column chunks under 8 waves: cfg2, cfg5, readme and their row bands)
+inline bool mx_streamable(const SearchArgs& a, int waves, bool stream) {
+    return stream && a.cols > a.chunk && a.chunk == 2 * 64 * waves;
+}
+
+template <int WORDS, int KSU, bool NODUPES, int T, int KEYS, bool TAIL, bool LIST = false, bool AG = false,
+          bool ST = false>
 hipError_t launch_mx_grid(const SearchArgs& a, int waves, int nwg, hipStream_t st,
                           const AgreeArgs* ag = nullptr) {
     constexpr int WL = 2 * KSU;
+    // (ST stages the raw descriptors in registers: the same LDS, 64 KiB for 1024-column chunks)
     size_t lds = (size_t)WL * a.chunk * 16;
     if (LIST) lds = list_ent_offset((int)lds) + (size_t)waves * T * 32 * 2;
-    const auto kern = search_mx_kernel<WORDS, KSU, NODUPES, T, KEYS, TAIL, LIST, AG>;
+    const auto kern = search_mx_kernel<WORDS, KSU, NODUPES, T, KEYS, TAIL, LIST, AG, ST>;
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute((const void*)kern,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1728,11 +1843,25 @@ hipError_t launch_mx_grid(const SearchArgs& a, int waves, int nwg, hipStream_t s
 // last round, but hosting both tile counts in one kernel made the main path spill.)
 // Compacted col0 (a.keep) split the same way in entry space (see launch_pk).
 template <int WORDS, int KSU, bool NODUPES, int T, int KEYS, int TT>
-hipError_t launch_mx_tt(const SearchArgs& a, int waves, hipStream_t st) {
+hipError_t launch_mx_tt(const SearchArgs& a, int waves, bool stream, hipStream_t st) {
     const bool list = a.keep != nullptr;
-    hipError_t e = list ? launch_mx_grid<WORDS, KSU, NODUPES, T, KEYS, false, true>(
-                              a, waves, list_grid(a.rows, a.tiles_per_row), st)
-                        : launch_mx_grid<WORDS, KSU, NODUPES, T, KEYS, false>(a, waves, a.rows * a.tiles_per_row, st);
+    hipError_t e;
+    if (list) {
+        e = launch_mx_grid<WORDS, KSU, NODUPES, T, KEYS, false, true>(
+            a, waves, list_grid(a.rows, a.tiles_per_row), st);
+    } else {
+        e = hipErrorInvalidValue;
+        bool done = false;
+        if constexpr (WORDS == 4 && KSU == 2 && KEYS == 2 && (T == 2 || T == 4)) {
+            if (mx_streamable(a, waves, stream)) {
+                e = launch_mx_grid<WORDS, KSU, NODUPES, T, KEYS, false, false, false, true>(
+                    a, waves, a.rows * a.tiles_per_row, st);
+                done = true;
+            }
+        }
+        if (!done)
+            e = launch_mx_grid<WORDS, KSU, NODUPES, T, KEYS, false>(a, waves, a.rows * a.tiles_per_row, st);
+    }
     if constexpr (TT == 0) {
         return e;
     } else {
@@ -1746,14 +1875,14 @@ hipError_t launch_mx_tt(const SearchArgs& a, int waves, hipStream_t st) {
 }
 
 template <int WORDS, int KSU, bool NODUPES, int T, int KEYS>
-hipError_t launch_mx(const SearchArgs& a, int waves, hipStream_t st) {
+hipError_t launch_mx(const SearchArgs& a, int waves, bool stream, hipStream_t st) {
     // (tail tiles: 1 or 2, and fewer than the main workgroups'; KEYS 2 only -- the any-order
     // NoDuplicates search, whose block order starts at each wave's own col0)
     if constexpr (KEYS == 2 && T >= 2) {
-        if (a.tail_T == 1 && a.tail_col0 < a.cols) return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 1>(a, waves, st);
+        if (a.tail_T == 1 && a.tail_col0 < a.cols) return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 1>(a, waves, stream, st);
     }
     if constexpr (KEYS == 2 && T >= 4) {
-        if (a.tail_T == 2 && a.tail_col0 < a.cols) return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 2>(a, waves, st);
+        if (a.tail_T == 2 && a.tail_col0 < a.cols) return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 2>(a, waves, stream, st);
     }
     // no tail workgroups for these keys / tile counts: the main workgroups cover every col0
     SearchArgs b = a;
@@ -1761,7 +1890,7 @@ hipError_t launch_mx(const SearchArgs& a, int waves, hipStream_t st) {
     b.tiles_per_row = (int)((a.cols + per_wg - 1) / per_wg);
     b.tail_T = 0;
     b.tail_col0 = a.cols;
-    return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 0>(b, waves, st);
+    return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 0>(b, waves, stream, st);
 }
 
 // Tile counts whose registers fit (checked with -Rpass-analysis=kernel-resource-usage): 8
@@ -1774,19 +1903,19 @@ template <int WORDS, int KSU, bool NODUPES, int KEYS>
 hipError_t launch_mx_k(const SearchArgs& a, const MxGeometry& g, hipStream_t st) {
     if (g.T == 8) {
         if constexpr (mx_tiles_fit(WORDS, NODUPES, KEYS, 8)) {
-            return launch_mx<WORDS, KSU, NODUPES, 8, KEYS>(a, g.waves, st);
+            return launch_mx<WORDS, KSU, NODUPES, 8, KEYS>(a, g.waves, g.stream != 0, st);
         } else {  // does not fit: 4 tiles per wave, twice the workgroups per row
             SearchArgs b = a;
             const long per_wg = 32L * g.waves * 4;
             b.tiles_per_row = (int)((a.cols + per_wg - 1) / per_wg);
             b.tail_T = 0;  // (the tail was sized for 8 tiles)
             b.tail_col0 = a.cols;
-            return launch_mx<WORDS, KSU, NODUPES, 4, KEYS>(b, g.waves, st);
+            return launch_mx<WORDS, KSU, NODUPES, 4, KEYS>(b, g.waves, g.stream != 0, st);
         }
     }
     switch (g.T) {
-        case 2: return launch_mx<WORDS, KSU, NODUPES, 2, KEYS>(a, g.waves, st);
-        case 4: return launch_mx<WORDS, KSU, NODUPES, 4, KEYS>(a, g.waves, st);
+        case 2: return launch_mx<WORDS, KSU, NODUPES, 2, KEYS>(a, g.waves, g.stream != 0, st);
+        case 4: return launch_mx<WORDS, KSU, NODUPES, 4, KEYS>(a, g.waves, g.stream != 0, st);
     }
     return hipErrorInvalidValue;
 }
@@ -1818,6 +1947,7 @@ hipError_t launch_mx_w(const SearchArgs& a, const MxGeometry& g, bool nodupes, h
 MxGeometry search_mx_geometry(int rows, int cols, int words, int lds_bytes, int T, int waves,
                               int cus, int keys, int bits) {
     MxGeometry g;
+    g.stream = 1;
     g.keys = keys == 2 ? 2 : 1;
     // 64-bit K-steps the products need: all of the descriptor unless the caller knows that
     // the bits past `bits` are zero (transform output); only 256-bit descriptors have a
@@ -1953,9 +2083,15 @@ hipError_t launch_search_mx_agree(SearchArgs a, const AgreeArgs& ag, const MxGeo
     a.tail_T = 0;
     a.tail_col0 = a.cols;
     // 2 tiles per wave: narrow row bands (N = 8 bands of cfg2, 192 rows)
+    const int nwg = a.rows * a.tiles_per_row;
+    if (mx_streamable(a, g.waves, g.stream != 0)) {
+        if (g.T == 2)
+            return launch_mx_grid<4, 2, true, 2, 2, false, false, true, true>(a, g.waves, nwg, st, &ag);
+        return launch_mx_grid<4, 2, true, 4, 2, false, false, true, true>(a, g.waves, nwg, st, &ag);
+    }
     if (g.T == 2)
-        return launch_mx_grid<4, 2, true, 2, 2, false, false, true>(a, g.waves, a.rows * a.tiles_per_row, st, &ag);
-    return launch_mx_grid<4, 2, true, 4, 2, false, false, true>(a, g.waves, a.rows * a.tiles_per_row, st, &ag);
+        return launch_mx_grid<4, 2, true, 2, 2, false, false, true>(a, g.waves, nwg, st, &ag);
+    return launch_mx_grid<4, 2, true, 4, 2, false, false, true>(a, g.waves, nwg, st, &ag);
 }
 
 // tiles per wave of the one-pass Consistency search (BICOS_LR_T=2: two, A/B)
