@@ -183,6 +183,12 @@ static bool stream_search() {
     static const bool on = env_on("BICOS_MX_STREAM");
     return on;
 }
+// The second K-step of the same search only for the blocks that can hold a minimum
+// (search_mx.hip search_mx_kernel PRUNE; BICOS_MX_PRUNE=0: every block in full; read once)
+static bool prune_search() {
+    static const bool on = env_on("BICOS_MX_PRUNE");
+    return on;
+}
 // Consistency's left-right check inside the agree launch (kernels.hip agree_lds_kernel CONS;
 // BICOS_FUSE_CONS=0: consistency_kernel + the agree; read once)
 static bool fuse_consistency() {
@@ -223,6 +229,7 @@ static bicos_hip::MxGeometry mx_geometry(const bicos_engine* e, int rows, int co
         rows, cols, words, lds, tuned ? e->tune_R : 0, tuned ? e->tune_waves : 0, e ? e->cus : 256,
         tuned ? e->tune_variant - 64 : 0, bits);
     g.stream = stream_search() ? 1 : 0;
+    g.prune = prune_search() ? 1 : 0;
     return g;
 }
 

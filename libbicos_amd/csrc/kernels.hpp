@@ -147,6 +147,11 @@ struct MxGeometry {
     // row's chunks after a workgroup's own through LDS in half-chunk stages where its shape
     // allows (search_mx.hip search_mx_kernel ST); 0: the chunk loop
     int stream;
+    // 1 (search_mx_geometry's default): the same search multiplies a block's second K-step
+    // only for the tile pairs whose first K-step leaves a col0 within reach of its running
+    // minimum, with a per-wave fallback (search_mx.hip search_mx_kernel PRUNE); 0: every block
+    // in full
+    int prune;
 };
 // bits: highest used descriptor bit + 1 when the bits above are known to be zero (0 =
 // all of them)

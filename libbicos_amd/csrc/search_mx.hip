@@ -419,12 +419,37 @@ __device__ __forceinline__ const SearchArgs& search_part(const SearchAgreeArgs& 
 // Without ST every chunk costs barrier -> loads -> expansion -> barrier with no wave of the
 // workgroup multiplying. The stages run downwards from the own chunk (wrapping), upper half
 // first; any order gives the same minima (KEYS 2).
+//
+// PRUNE (KEYS 2, 128-bit descriptors in 2 K-steps, tiles in pairs, main launches): the second
+// K-step only where it can matter. The key carries x = ham - |a| = x_lo + x_hi, the sums over
+// the two 64-bit K-steps, and x_hi = sum_k b_k (1 - 2 a_k) >= -|a_hi|, |a_hi| = the popcount
+// of the left descriptor's words 2 and 3. So x >= x_lo - |a_hi|: if, after the FIRST K-step of
+// a tile pair, every col0's block minimum of x_lo - |a_hi| lies strictly above that col0's
+// running minimum cost, the block holds neither a new first minimum nor a tie (the last
+// minimum), and its second K-step, its key reduction and its update of mp / m2 change
+// nothing: they are skipped (block_pr; one wave-uniform branch per pair, both tiles taken
+// when either reaches). The test is exact in the key's integer cost field (bits 14 and up
+// of D = 768 + x + col * 2^-14, i.e. x + 256): it runs as x_lo <= running x + |a_hi|, the
+// bits of D_lo against thr = (running minimum | column field) + (|a_hi| << 14). x_lo in
+// [-64, 64] keeps D_lo in [704, 832]; the running x in [-128, 128] and |a_hi| <= 64 (62 for
+// transform output) keep thr's cost field in [128, 448]: positive, and D stays in the binade
+// [512, 1024), where adding to the bits IS the float addition. The comparison is "<=": a tie
+// is never pruned (NoDuplicates needs it). A pruned pair skips its update, so mp[p] keeps
+// its own previous base bpp[p], as m2[t] has b2[t].
+// Fallback: where true matches are poor (costs above ~10 of 126 bits) or absent, every
+// block reaches and the test is pure overhead. A wave counts its reaching pair-blocks (SALU,
+// from the ballots the branch takes anyway) over windows of PRUNE_WINDOW visited blocks, all
+// through the scan; a window in which >= 7/8 of them reached sends the wave to the unpruned
+// loop for the rest of the row.
+constexpr int PRUNE_WINDOW = 8;
 template <int WORDS, int KSU, bool NODUPES, int T, int KEYS, bool TAIL, bool LIST, bool AG = false,
-          bool ST = false>
+          bool ST = false, bool PRUNE = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(KSU >= 4 ? 3 : 4)))
 void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
     const SearchArgs& a = search_part(ka);
     constexpr bool STREAM = ST;
+    static_assert(!PRUNE || (KEYS == 2 && T % 2 == 0 && WORDS == 4 && KSU == 2 && !TAIL && !LIST),
+                  "PRUNE: the 128-bit any-order NoDuplicates search's main launches");
     static_assert(!ST || (KEYS == 2 && T % 2 == 0 && WORDS == 4 && KSU == 2 && !TAIL && !LIST),
                   "ST: the 128-bit any-order NoDuplicates search over every col0");
     constexpr bool FK = KEYS == 3;
@@ -544,6 +569,7 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
 #endif
     // one pair per wave: the block loop is software-pipelined (see the FREE chunk loop)
     constexpr bool PIPE = PAIRS && T == 2 && KS <= 3;
+    constexpr bool PR = PRUNE && PAIRS;
     // XK full blocks: the next block's A fragments are read while this one is reduced.
     // Only where the registers allow (paired NoDuplicates tiles, <= 2 K-steps): cfg2 -1.5 %,
     // cfg5 -1 %; with 3 K-steps the extra live fragments spill inside the loop (cfg4 2.3x
@@ -560,6 +586,29 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
     }
 #pragma unroll
     for (int p = 0; p < (T / 2 > 0 ? T / 2 : 1); ++p) mp[p] = XK_INF;
+    // PRUNE: |a_hi| of the col0 whose running minimum this lane homes (tile 2p in lanes 0-31,
+    // tile 2p+1 in lanes 32-63), in the key's cost field; the base mp[p] is relative to; the
+    // fallback's state (wave-uniform)
+    uint32_t ah[T / 2 > 0 ? T / 2 : 1];
+    // ... and the test's threshold: the running minimum's cost raised by |a_hi|, its column
+    // field all ones (the same in every block's frame), renewed where mp[p] changes
+    uint32_t thr[T / 2 > 0 ? T / 2 : 1];
+    int bpp[T / 2 > 0 ? T / 2 : 1];
+    bool prune_on = PR;
+    int wblocks = 0, wreach = 0;
+#pragma unroll
+    for (int p = 0; p < (T / 2 > 0 ? T / 2 : 1); ++p) {
+        ah[p] = 0u;
+        bpp[p] = 0;
+        if constexpr (PR) {
+            const int c0 = c0_wave + 32 * (2 * p + h) + j;
+            if (c0 < lcols) {
+                const uint32_t* q = row0 + (size_t)lcol(c0) * WORDS;
+                ah[p] = (uint32_t)(__popc(q[2]) + __popc(q[3])) << 14;
+            }
+        }
+        thr[p] = (XK_INF | XK_COL) + ah[p];
+    }
 
     // row offset of accumulator register r in this lane half
     auto rrow = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
@@ -638,7 +687,8 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
         const uint32_t y = min16(dy, KEY_NONE, 0u);
         const auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);
         const uint32_t comb = min((uint32_t)sw[0], (uint32_t)sw[1]);
-        const uint32_t ms = mp[p] - (uint32_t)(B - bprev);
+        const uint32_t ms = mp[p] - (uint32_t)(B - (PR ? bpp[p] : bprev));
+        if constexpr (PR) bpp[p] = B;
 #if defined(BICOS_MX_DIAG) && BICOS_MX_DIAG == 4  // timing only: the last-minimum path never runs
         const bool reach = comb <= (ms | XK_COL) && comb == 0u;
 #else
@@ -814,12 +864,44 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
             }
             bprev = B;
         };
+        // PRUNE: a full block with the second K-step only for the pairs that can reach (see
+        // the kernel's header). af0 holds the block's K-step 0 fragment on entry and the
+        // next block's (nb, if >= 0) on return, read once the last K-step 0 products are
+        // issued; the K-step 1 fragment is read here, ahead of the first test. Counts the
+        // reaching pairs into wreach.
+        auto block_pr = [&](int b, v4i& af0, int nb) {
+            const int B = base + 32 * b;
+            if constexpr (PR) {
+                const v4i af1 = lds_mx[(2 + h) * chunk + 32 * b + j];
+#pragma unroll
+                for (int p = 0; p < T / 2; ++p) {
+                    d[0] = mfma_fp4(af0, bf[2 * p][0], cc);
+                    d[1] = mfma_fp4(af0, bf[2 * p + 1][0], cc);
+                    if (p + 1 == T / 2 && nb >= 0) af0 = lds_mx[h * chunk + 32 * nb + j];
+                    // the first half of pair_reduce on the partial keys
+                    const uint32_t x = min16(d[0], KEY_NONE, 0u);
+                    const uint32_t y = min16(d[1], KEY_NONE, 0u);
+                    const auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);
+                    // x_lo - |a_hi| <= running x as x_lo <= thr; "<=": a tie reaches
+                    const uint32_t lb = min((uint32_t)sw[0], (uint32_t)sw[1]);
+                    if (__builtin_amdgcn_ballot_w64(lb <= thr[p])) {
+                        d[0] = mfma_fp4(af1, bf[2 * p][1], d[0]);
+                        d[1] = mfma_fp4(af1, bf[2 * p + 1][1], d[1]);
+                        pair_reduce(p, B, d[0], d[1]);
+                        thr[p] = (mp[p] | XK_COL) + ah[p];
+                        ++wreach;
+                    }
+                }
+            }
+            bprev = B;
+        };
         // the block reaching past the image (last chunk): A = 0 there, so D1 = KEY_PAD,
         // D2 = 0 never win. Ascending orders take it last, FREE first.
         auto partial_block = [&](const v16f& cb) {
-            if constexpr (STREAM && PAIRS) {
-                // (no second C matrix, whose 16 registers would spill beside `raw`: the rows
-                // past the image are set to KEY_PAD after the products -- the same D)
+            if constexpr ((STREAM || PR) && PAIRS) {
+                // (no second C matrix, whose 16 registers would spill beside `raw` or the
+                // pruned loop's state: the rows past the image are set to KEY_PAD after the
+                // products -- the same D)
                 const int b = b0 + nfull, B = base + 32 * b;
                 v4i af[KS];
 #pragma unroll
@@ -835,6 +917,7 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
                         d[1][r] = in ? d[1][r] : KEY_PAD;
                     }
                     pair_reduce(p, B, d[0], d[1]);
+                    if constexpr (PR) thr[p] = (mp[p] | XK_COL) + ah[p];
                 }
                 bprev = B;
                 return;
@@ -853,6 +936,31 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
             // full blocks downwards from the one holding the wave's highest col0 (clamped)
             // (block indices below are relative to the step's first LDS block b0)
             const int sb = max(0, min(nfull - 1, (start_col(c0_wave + 32 * T, REV_AHEAD) - base - 32 * b0) / 32));
+            // PRUNE: the pruned loop over the first i0 blocks of the visiting order -- all of
+            // them unless a window of PRUNE_WINDOW blocks had >= 7/8 of its pair-blocks reach,
+            // which sends the wave to the loops below for the rest of the row
+            int i0 = 0;
+            if constexpr (PR) {
+                if (prune_on && nfull > 0) {
+                    auto bidx = [&](int i) {
+                        int b = sb - i;
+                        return b0 + (b < 0 ? b + nfull : b);
+                    };
+                    v4i af0 = lds_mx[h * chunk + 32 * bidx(0) + j];
+                    while (i0 < nfull) {
+                        block_pr(bidx(i0), af0, i0 + 1 < nfull ? bidx(i0 + 1) : -1);
+                        ++i0;
+                        if (++wblocks == PRUNE_WINDOW) {
+                            const bool fall = 8 * wreach >= 7 * PRUNE_WINDOW * (T / 2);
+                            wblocks = wreach = 0;
+                            if (fall) {
+                                prune_on = false;
+                                break;
+                            }
+                        }
+                    }
+                }
+            }
 #if !defined(BICOS_MX_DIAG) || BICOS_MX_DIAG >= 3
             if constexpr (PIPE) {
                 // software pipeline over the blocks (one tile pair per wave): the products of
@@ -879,9 +987,9 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
                     pair_reduce(0, B, dd[0], dd[1]);
                     bprev = B;
                 };
-                if (nfull > 0) {
-                    BA = issue(0, dA);
-                    for (int i = 0;;) {
+                if (i0 < nfull) {
+                    BA = issue(i0, dA);
+                    for (int i = i0;;) {
                         if (i + 1 < nfull) BB = issue(i + 1, dB);
                         finish(BA, dA);
                         if (++i >= nfull) break;
@@ -896,8 +1004,8 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
                     return b0 + (b < 0 ? b + nfull : b);
                 };
                 v4i af[KS];
-                if (nfull > 0) load_af(af, bidx(0));
-                for (int i = 0; i < nfull; ++i) block_pf(bidx(i), af, i + 1 < nfull ? bidx(i + 1) : -1);
+                if (i0 < nfull) load_af(af, bidx(i0));
+                for (int i = i0; i < nfull; ++i) block_pf(bidx(i), af, i + 1 < nfull ? bidx(i + 1) : -1);
             } else
 #endif
             for (int i = 0; i < nfull; ++i) {
@@ -939,6 +1047,10 @@ void search_mx_kernel(typename SearchKArgs<AG>::type ka) {
     if constexpr (AG) __syncthreads();
 
     // the two lane halves hold the even / odd 4-row groups of every block
+    if constexpr (PR) {
+#pragma unroll
+        for (int p = 0; p < T / 2; ++p) mp[p] -= (uint32_t)(bprev - bpp[p]);  // as m2 below
+    }
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         if constexpr (FREE) m2[t] += (uint32_t)(bprev - b2[t]);  // into the last block's frame
@@ -1817,14 +1929,14 @@ inline bool mx_streamable(const SearchArgs& a, int waves, bool stream) {
 }
 
 template <int WORDS, int KSU, bool NODUPES, int T, int KEYS, bool TAIL, bool LIST = false, bool AG = false,
-          bool ST = false>
+          bool ST = false, bool PRUNE = false>
 hipError_t launch_mx_grid(const SearchArgs& a, int waves, int nwg, hipStream_t st,
                           const AgreeArgs* ag = nullptr) {
     constexpr int WL = 2 * KSU;
     // (ST stages the raw descriptors in registers: the same LDS, 64 KiB for 1024-column chunks)
     size_t lds = (size_t)WL * a.chunk * 16;
     if (LIST) lds = list_ent_offset((int)lds) + (size_t)waves * T * 32 * 2;
-    const auto kern = search_mx_kernel<WORDS, KSU, NODUPES, T, KEYS, TAIL, LIST, AG, ST>;
+    const auto kern = search_mx_kernel<WORDS, KSU, NODUPES, T, KEYS, TAIL, LIST, AG, ST, PRUNE>;
     if (lds > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute((const void*)kern,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1843,7 +1955,7 @@ hipError_t launch_mx_grid(const SearchArgs& a, int waves, int nwg, hipStream_t s
 // last round, but hosting both tile counts in one kernel made the main path spill.)
 // Compacted col0 (a.keep) split the same way in entry space (see launch_pk).
 template <int WORDS, int KSU, bool NODUPES, int T, int KEYS, int TT>
-hipError_t launch_mx_tt(const SearchArgs& a, int waves, bool stream, hipStream_t st) {
+hipError_t launch_mx_tt(const SearchArgs& a, int waves, bool stream, bool prune, hipStream_t st) {
     const bool list = a.keep != nullptr;
     hipError_t e;
     if (list) {
@@ -1852,10 +1964,15 @@ hipError_t launch_mx_tt(const SearchArgs& a, int waves, bool stream, hipStream_t
     } else {
         e = hipErrorInvalidValue;
         bool done = false;
+        // (the 128-bit any-order NoDuplicates search: streamed and / or pruned, see the kernel)
         if constexpr (WORDS == 4 && KSU == 2 && KEYS == 2 && (T == 2 || T == 4)) {
+            const int nwg = a.rows * a.tiles_per_row;
             if (mx_streamable(a, waves, stream)) {
-                e = launch_mx_grid<WORDS, KSU, NODUPES, T, KEYS, false, false, false, true>(
-                    a, waves, a.rows * a.tiles_per_row, st);
+                e = prune ? launch_mx_grid<WORDS, KSU, NODUPES, T, KEYS, false, false, false, true, true>(a, waves, nwg, st)
+                          : launch_mx_grid<WORDS, KSU, NODUPES, T, KEYS, false, false, false, true>(a, waves, nwg, st);
+                done = true;
+            } else if (prune) {
+                e = launch_mx_grid<WORDS, KSU, NODUPES, T, KEYS, false, false, false, false, true>(a, waves, nwg, st);
                 done = true;
             }
         }
@@ -1875,14 +1992,14 @@ hipError_t launch_mx_tt(const SearchArgs& a, int waves, bool stream, hipStream_t
 }
 
 template <int WORDS, int KSU, bool NODUPES, int T, int KEYS>
-hipError_t launch_mx(const SearchArgs& a, int waves, bool stream, hipStream_t st) {
+hipError_t launch_mx(const SearchArgs& a, int waves, bool stream, bool prune, hipStream_t st) {
     // (tail tiles: 1 or 2, and fewer than the main workgroups'; KEYS 2 only -- the any-order
     // NoDuplicates search, whose block order starts at each wave's own col0)
     if constexpr (KEYS == 2 && T >= 2) {
-        if (a.tail_T == 1 && a.tail_col0 < a.cols) return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 1>(a, waves, stream, st);
+        if (a.tail_T == 1 && a.tail_col0 < a.cols) return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 1>(a, waves, stream, prune, st);
     }
     if constexpr (KEYS == 2 && T >= 4) {
-        if (a.tail_T == 2 && a.tail_col0 < a.cols) return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 2>(a, waves, stream, st);
+        if (a.tail_T == 2 && a.tail_col0 < a.cols) return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 2>(a, waves, stream, prune, st);
     }
     // no tail workgroups for these keys / tile counts: the main workgroups cover every col0
     SearchArgs b = a;
@@ -1890,7 +2007,7 @@ hipError_t launch_mx(const SearchArgs& a, int waves, bool stream, hipStream_t st
     b.tiles_per_row = (int)((a.cols + per_wg - 1) / per_wg);
     b.tail_T = 0;
     b.tail_col0 = a.cols;
-    return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 0>(b, waves, stream, st);
+    return launch_mx_tt<WORDS, KSU, NODUPES, T, KEYS, 0>(b, waves, stream, prune, st);
 }
 
 // Tile counts whose registers fit (checked with -Rpass-analysis=kernel-resource-usage): 8
@@ -1903,19 +2020,19 @@ template <int WORDS, int KSU, bool NODUPES, int KEYS>
 hipError_t launch_mx_k(const SearchArgs& a, const MxGeometry& g, hipStream_t st) {
     if (g.T == 8) {
         if constexpr (mx_tiles_fit(WORDS, NODUPES, KEYS, 8)) {
-            return launch_mx<WORDS, KSU, NODUPES, 8, KEYS>(a, g.waves, g.stream != 0, st);
+            return launch_mx<WORDS, KSU, NODUPES, 8, KEYS>(a, g.waves, g.stream != 0, g.prune != 0, st);
         } else {  // does not fit: 4 tiles per wave, twice the workgroups per row
             SearchArgs b = a;
             const long per_wg = 32L * g.waves * 4;
             b.tiles_per_row = (int)((a.cols + per_wg - 1) / per_wg);
             b.tail_T = 0;  // (the tail was sized for 8 tiles)
             b.tail_col0 = a.cols;
-            return launch_mx<WORDS, KSU, NODUPES, 4, KEYS>(b, g.waves, g.stream != 0, st);
+            return launch_mx<WORDS, KSU, NODUPES, 4, KEYS>(b, g.waves, g.stream != 0, g.prune != 0, st);
         }
     }
     switch (g.T) {
-        case 2: return launch_mx<WORDS, KSU, NODUPES, 2, KEYS>(a, g.waves, g.stream != 0, st);
-        case 4: return launch_mx<WORDS, KSU, NODUPES, 4, KEYS>(a, g.waves, g.stream != 0, st);
+        case 2: return launch_mx<WORDS, KSU, NODUPES, 2, KEYS>(a, g.waves, g.stream != 0, g.prune != 0, st);
+        case 4: return launch_mx<WORDS, KSU, NODUPES, 4, KEYS>(a, g.waves, g.stream != 0, g.prune != 0, st);
     }
     return hipErrorInvalidValue;
 }
@@ -1948,6 +2065,7 @@ MxGeometry search_mx_geometry(int rows, int cols, int words, int lds_bytes, int 
                               int cus, int keys, int bits) {
     MxGeometry g;
     g.stream = 1;
+    g.prune = 1;
     g.keys = keys == 2 ? 2 : 1;
     // 64-bit K-steps the products need: all of the descriptor unless the caller knows that
     // the bits past `bits` are zero (transform output); only 256-bit descriptors have a
@@ -2084,6 +2202,16 @@ hipError_t launch_search_mx_agree(SearchArgs a, const AgreeArgs& ag, const MxGeo
     a.tail_col0 = a.cols;
     // 2 tiles per wave: narrow row bands (N = 8 bands of cfg2, 192 rows)
     const int nwg = a.rows * a.tiles_per_row;
+    if (g.prune) {
+        if (mx_streamable(a, g.waves, g.stream != 0)) {
+            if (g.T == 2)
+                return launch_mx_grid<4, 2, true, 2, 2, false, false, true, true, true>(a, g.waves, nwg, st, &ag);
+            return launch_mx_grid<4, 2, true, 4, 2, false, false, true, true, true>(a, g.waves, nwg, st, &ag);
+        }
+        if (g.T == 2)
+            return launch_mx_grid<4, 2, true, 2, 2, false, false, true, false, true>(a, g.waves, nwg, st, &ag);
+        return launch_mx_grid<4, 2, true, 4, 2, false, false, true, false, true>(a, g.waves, nwg, st, &ag);
+    }
     if (mx_streamable(a, g.waves, g.stream != 0)) {
         if (g.T == 2)
             return launch_mx_grid<4, 2, true, 2, 2, false, false, true, true>(a, g.waves, nwg, st, &ag);

@@ -1,0 +1,126 @@
+"""How often the pruned 128-bit NoDuplicates search (search_mx.hip search_mx_kernel PRUNE)
+needs a block's second K-step -- a CPU simulation in reach_sim's visiting order, on the
+synthetic stereo frame, on the same frame with a share of the right descriptor bits flipped,
+or on random descriptors.
+
+The kernel's test x_lo - |a_hi| <= running x is, in Hamming terms, ham_lo <= running ham
+(ham = x + |a|, |a| = |a_lo| + |a_hi|): a unit "reaches" when some col0 of it has its block
+minimum over the FIRST 64 descriptor bits <= its running minimum cost over all bits. Units
+are 32-col0 tiles or the kernel's tile pairs (64 col0, one branch). A unit that does not reach
+skips the block; the simulation checks that the minima and the last minima then still equal
+the full scan's. With --fallback the wave's window rule is simulated too (PRUNE_WINDOW blocks,
+>= 7/8 of the pair-blocks reaching sends the wave to the unpruned loop for the rest of the row).
+
+  python tools/prune_sim.py [--rows 0 500 767 1535] [--W 2048] [--flip 0 0.02 0.05 0.1]
+                            [--random] [--lo-bits 0] [--fallback]
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from reach_sim import costs, limited_bits, order_current, pack  # noqa: E402
+from libbicos_amd.synthetic import random_stack, stereo_stack  # noqa: E402
+
+PRUNE_WINDOW = 8  # search_mx.hip
+
+
+def simulate(C, Clo, cols, unit_tiles, fallback, waves=8, T=4, chunk=1024):
+    """-> (units, partial reaches, units whose second K-step runs, waves, waves fallen back)"""
+    units = reach = second = nwaves = fell = 0
+    per_wg = waves * T * 32
+    full_min = C.min(axis=1)
+    for wg in range((cols + per_wg - 1) // per_wg):
+        for w in range(waves):
+            c0_wave = wg * per_wg + w * T * 32
+            if c0_wave >= cols:
+                continue
+            nwaves += 1
+            blocks = order_current(c0_wave, (wg + 1) * per_wg - 1, cols, chunk)
+            spans = []
+            for t in range(0, T, unit_tiles):
+                lo, hi = c0_wave + 32 * t, min(cols, c0_wave + 32 * (t + unit_tiles))
+                if lo < cols:
+                    spans.append((lo, hi))
+            run = {s: np.full(s[1] - s[0], 1 << 30) for s in spans}
+            last = {s: np.full(s[1] - s[0], -1) for s in spans}
+            pruning, wb, wr = True, 0, 0
+            for B in blocks:
+                e = min(cols, B + 32)
+                full = e - B == 32  # the partial last block never prunes
+                for s in spans:
+                    units += 1
+                    c = C[s[0]:s[1], B:e]
+                    bm = c.min(axis=1)
+                    r = bool((Clo[s[0]:s[1], B:e].min(axis=1) <= run[s]).any())
+                    if full and pruning:
+                        reach += r
+                        wr += r
+                    if r or not (full and pruning):
+                        second += 1
+                        # the last column at the running minimum cost, any visiting order
+                        arg = B + c.shape[1] - 1 - np.argmin(c[:, ::-1], axis=1)
+                        take = (bm < run[s]) | ((bm == run[s]) & (arg > last[s]))
+                        last[s] = np.where(take, arg, last[s])
+                        run[s] = np.minimum(run[s], bm)
+                if full and pruning and fallback:
+                    wb += 1
+                    if wb == PRUNE_WINDOW:
+                        if 8 * wr >= 7 * PRUNE_WINDOW * len(spans):
+                            pruning = False
+                            fell += 1
+                        wb = wr = 0
+            for s in spans:  # pruning changed nothing
+                assert (run[s] == full_min[s[0]:s[1]]).all()
+                c = C[s[0]:s[1]]
+                want = cols - 1 - np.argmin(c[:, ::-1], axis=1)
+                assert (last[s] == want).all()
+    return units, reach, second, nwaves, fell
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, nargs="+", default=[0, 500, 767, 1535])
+    ap.add_argument("--W", type=int, default=2048)
+    ap.add_argument("--n", type=int, default=33)
+    ap.add_argument("--flip", type=float, nargs="+", default=[0.0, 0.02, 0.05, 0.10])
+    ap.add_argument("--random", action="store_true")
+    ap.add_argument("--lo-bits", type=int, default=0, help="first bit of the 64-bit partial subset")
+    ap.add_argument("--fallback", action="store_true")
+    args = ap.parse_args()
+    H = 1536
+    for flip in ([0.0] if args.random else args.flip):
+        tot = {1: np.zeros(5, np.int64), 2: np.zeros(5, np.int64)}
+        med = []
+        for r in args.rows:
+            if args.random:
+                L = random_stack(args.n, 1, args.W, seed=int(r) + 1)
+                R = random_stack(args.n, 1, args.W, seed=int(r) + 7)
+            else:
+                L, R = stereo_stack(args.n, H, args.W, row_begin=int(r), row_end=int(r) + 1)
+            b0, b1 = limited_bits(L)[0], limited_bits(R)[0]
+            if flip:
+                b1 = b1 ^ (np.random.default_rng(int(r)).random(b1.shape) < flip)
+            nb = b0.shape[-1]
+            sel = (np.arange(64) + args.lo_bits) % nb
+            C = costs(pack(b0), pack(b1))
+            Clo = costs(pack(b0[:, sel]), pack(b1[:, sel]))
+            med.append(float(np.median(C.min(axis=1))))
+            for ut in (1, 2):
+                tot[ut] += np.array(simulate(C, Clo, args.W, ut, args.fallback))
+        name = "random" if args.random else "flip %.2f" % flip
+        for ut, label in ((1, "tile"), (2, "pair")):
+            u, rch, sec, nw, fell = tot[ut]
+            # (partial reach counts the blocks tested while pruning: after a wave falls back its
+            # blocks are not tested any more and all run their second K-step)
+            print("%-10s median match cost %4.1f  per %s: partial reach %.3f, second K-step %.3f of "
+                  "unit-blocks, %d of %d waves fell back" % (name, np.median(med), label,
+                                                             rch / max(1, u), sec / u, fell, nw))
+
+
+if __name__ == "__main__":
+    main()
