@@ -258,7 +258,7 @@ static int required_bits(int n, int mode) { return mode ? n * n - 2 * n + 3 : 4 
 // Consistency's reverse search (reference bicos.hpp:94-106, bicos.cuh:110-135): rev[col1] is
 // read only for the col1 a valid forward match chose, so the matrix-core search runs only
 // over those -- per row the distinct valid fwd[col0] in ascending order, which each
-// workgroup of the compacted search finds itself (search_mx.hip list_prologue); rev
+// workgroup of the compacted search finds itself (search_dev.hpp list_prologue); rev
 // elsewhere is left unwritten and never read. Periodic inputs whose forward search keeps
 // nothing skip the reverse pass almost entirely. BICOS_REV_FULL=1 (A/B) and the VALU search
 // run the full reverse pass (run_search: keep = nullptr).
@@ -270,14 +270,14 @@ static bool reverse_compacted(bool mx) {
     return mx && !full;
 }
 
-// Consistency's dense-row fast path (SearchArgs.row_valid, search_mx.hip dense_row): the
+// Consistency's dense-row fast path (SearchArgs.row_valid, search_dev.hpp dense_row): the
 // forward search counts its valid col0 per 32-column tile and the compacted reverse search
 // skips its entry prologue on rows that kept >= 7/8 of them. BICOS_DENSE_ROWS=0: off (A/B).
 static bool dense_rows() {
     static const bool on = env_on("BICOS_DENSE_ROWS");
     return on;
 }
-// Consistency without NoDuplicates in one launch where the descriptors allow it (search_mx.hip
+// Consistency without NoDuplicates in one launch where the descriptors allow it (search_lr.hip
 // search_lr_kernel: the forward and reverse searches share their matrix products, the check
 // runs in the same workgroup). BICOS_LR_ONE_PASS=0: the two searches + the check (A/B; read
 // per call, so one process can compare the two forms).
@@ -385,10 +385,10 @@ int run_search(const bicos_engine* e, const SearchPlan& p, const SearchBuffers& 
                                      (size_t)cols, out_mode, 0, 0, 0};
     };
     // the headline shape runs the agree inside the search's workgroups (one launch,
-    // search_mx.hip fused_agree; BICOS_FUSE_AGREE=0 keeps the two launches)
+    // search_dev.hpp fused_agree; BICOS_FUSE_AGREE=0 keeps the two launches)
     if (fused_agree)
         return check_hip(bicos_hip::launch_search_mx_agree(args(j.d0, j.d1, out, 0), *fused_agree,
-                                                           p.mx, st),
+                                                           p.mx, words, st),
                          "search + agree launch");
     if (p.bits & BICOS_PLAN_CONSISTENCY_ONE_PASS)
         return check_hip(bicos_hip::launch_search_lr(args(j.d0, j.d1, out, 0), words,

@@ -118,7 +118,8 @@ hipError_t launch_search(SearchArgs a, const SearchGeometry& g, int words, bool 
                          hipStream_t st);
 hipError_t launch_consistency(const ConsistencyArgs& a, hipStream_t st);
 
-// Matrix-core search (search_mx.hip): FP4 MFMA Hamming products, argmin keys in the
+// Matrix-core search (search_mx.hip, search_pk.hip, search_lr.hip; geometry and launch plan:
+// search_plan.cpp): FP4 MFMA Hamming products, argmin keys in the
 // accumulator. Same outputs as launch_search (a.out, a.out_mode).
 struct MxGeometry {
     int chunk;              // col1 per LDS fill (multiple of 32)
@@ -131,7 +132,7 @@ struct MxGeometry {
     int fk;                 // 1: float keys with the column in the free upper half of the
                             // last K-step allowed (<= 64 ksteps - 32 used bits, cols <= 2048;
                             // search_mx.hip KEYS 3, first-minimum searches only)
-    // packed Hamming keys (search_mx.hip search_pk_kernel: NoDuplicates, <= 127 used bits,
+    // packed Hamming keys (search_pk.hip search_pk_kernel: NoDuplicates, <= 127 used bits,
     // 32/64/128-bit words): used instead of the fields above when pk != 0 and the search
     // is NoDuplicates
     // the row's last workgroup, when it would hold only a few col0: one tail workgroup per
@@ -167,9 +168,11 @@ hipError_t launch_search_mx(SearchArgs a, const MxGeometry& g, int words, bool n
 // of n = 8; float, no subpixel step. search_mx_agree_fusable says whether g / the match are one.
 bool search_mx_agree_fusable(const MxGeometry& g, int words, bool nodupes, int cols, int n,
                              int depth, bool dbl);
-hipError_t launch_search_mx_agree(SearchArgs a, const AgreeArgs& ag, const MxGeometry& g,
+// words: the descriptor width, as launch_search_mx's; a (words, ag.n) pair that is no fused
+// shape is hipErrorInvalidValue.
+hipError_t launch_search_mx_agree(SearchArgs a, const AgreeArgs& ag, const MxGeometry& g, int words,
                                   hipStream_t st);
-// Consistency in one pass (search_mx.hip search_lr_kernel): the forward and the reverse
+// Consistency in one pass (search_lr.hip search_lr_kernel): the forward and the reverse
 // search from the same matrix products and the left-right check (reference bicos.hpp:78-113,
 // no NoDuplicates), one workgroup per row; a.out gets consistency_kernel's disparity map
 // (out_mode 0). Only 256-bit descriptors with 129..154 used bits (`bits`: their count; the

@@ -75,6 +75,52 @@ __device__ __forceinline__ v16f mfma_fp4(v4i a, v4i b, v16f c) {
     return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, 0, 0, 0);
 }
 
+constexpr uint32_t XK_INF = 0x7F000000u;  // "no key yet"; stays huge under the shifts
+// KEYS 3 (float keys, no C matrix): where the descriptors leave the upper lane half of the
+// last 64-bit K-step free (e.g. 256-bit words with <= 160 transform bits, cfg4's 154), that
+// half carries the column: the right operand holds the binary digits of col1 % 32 there
+// (FP4 1, 2, 4, 4+4, 4+4+4+4 in nine elements), the left operand is +1.0 (its descriptor bits
+// are 0), and the MFMA scales that half of the right operand by 2^-12. So D = x + (col1 %
+// 32) * 2^-12 with C = 0 (an inline constant): 16 VGPRs freer than the XK keys. The running
+// minimum is kept relative to the current block base B, D = x + (col1 - B) * 2^-12, moved by
+// -32 * 2^-12 per (ascending) block with one float subtract; |col1 - B| < 2048 keeps the
+// column term inside (-0.5, 0.5), so floats order by x first and then by col1 (the first
+// minimum, v_min3_f32), rint(D) = x, and (D - x) * 4096 = col1 - B exactly (|D| < 256 ->
+// ulp 2^-16). NoDuplicates keeps the XK keys (the last minimum needs the bit trick).
+constexpr float FK_EPS = 1.f / 4096.f;
+constexpr int FK_SCALE_E8M0 = 127 - 12;  // 2^-12
+
+// FK column digits of r = col1 % 32 as one lane's 32 FP4 elements (element k = nibble k):
+// 1.0 * bit0, 2.0 * bit1, 4.0 * bit2, 4.0 * bit3 (twice), 4.0 * bit4 (four times)
+__device__ __forceinline__ v4i fk_digits(int r) {
+    uint32_t w0 = 0, w1 = 0;
+    w0 |= (r & 1) ? 0x2u : 0u;
+    w0 |= (r & 2) ? 0x40u : 0u;
+    w0 |= (r & 4) ? 0x600u : 0u;
+    w0 |= (r & 8) ? 0x66000u : 0u;
+    w0 |= (r & 16) ? 0x66600000u : 0u;
+    w1 |= (r & 16) ? 0x6u : 0u;
+    return v4i{(int)w0, (int)w1, 0, 0};
+}
+
+__device__ __forceinline__ float fmin3(float a, float b, float c) {
+    return __builtin_fminf(__builtin_fminf(a, b), c);
+}
+// min over the 16 float keys of a D tile and m (v_min3_f32 tree)
+__device__ __forceinline__ float fmin16(const v16f& d, float m) {
+    const float a0 = fmin3(d[0], d[1], d[2]), a1 = fmin3(d[3], d[4], d[5]);
+    const float a2 = fmin3(d[6], d[7], d[8]), a3 = fmin3(d[9], d[10], d[11]);
+    const float a4 = fmin3(d[12], d[13], d[14]);
+    return fmin3(m, fmin3(a0, a1, a2), fmin3(a3, a4, d[15]));
+}
+
+// the same with E8M0 scales: sa for this lane's block of the right operand (A), 2^0 for B
+__device__ __forceinline__ v16f mfma_fp4_sa(v4i a, v4i b, v16f c, int sa) {
+    const v8i a8 = {a[0], a[1], a[2], a[3], 0, 0, 0, 0};
+    const v8i b8 = {b[0], b[1], b[2], b[3], 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, sa, 0, 127);
+}
+
 // col1 encoded in a key (D1 or D2 bits): key - 256 = +-x + col1 * 2^-15, x integer
 __device__ __forceinline__ int key_col(uint32_t key) {
     const float v = bitsf(key) - KEY_BIAS;  // exact

@@ -1,0 +1,432 @@
+// search_pk.hip -- the bicos Hamming search (reference include/impl/cpu/bicos.hpp:50-113) on the
+// gfx950 matrix cores with packed keys: NoDuplicates, descriptors with <= 127 used bits in
+// 32/64/128-bit words. Same FP4 products, workgroup layout and LDS staging as search_mx_kernel
+// (search_mx.hip, whose header comment derives the scheme); what differs is the key.
+//
+// The one-product search spends most of its VALU issue on the first-minimum trees: one v_min3_u32
+// per two keys, one key per accumulator register. Here every accumulator register carries
+// TWO Hamming distances, and the tree runs on gfx950's v_pk_minimum3_f16 (half rate, four
+// keys per instruction; profiles/valu_rates_r03.jsonl), so the reduction per pair halves.
+//
+// Operands: right A = 1 - 2b in {+1, -1}, left B = -(1 - 2a) / 2 in {-0.5, +0.5} (both exact
+// FP4 e2m1), so one K position contributes -(1 - 2a)(1 - 2b) / 2 and K positions sum to
+// ham - K / 2 (K = 32 WORDS, the zero bits past the used ones included: they add the same
+// -1/2 to every pair). One MFMA multiplies ONE descriptor word: the B lanes of K-half 0 hold
+// word w of col0 P, those of K-half 1 word w of col0 Q = P + 32, and the E8M0 scale of the
+// K-half-0 lanes is 2^16. With C = 2^23 + 2^16 (K/2) + 0x4B00 + K/2 every D is an integer in
+// [2^23, 2^24) (ulp 1), so
+//     bits(D) = 0x4B000000 + 2^16 ham(P, col1) + 0x4B00 + ham(Q, col1)
+// exactly: the high half is 0x4B00 + ham_P, the low half 0x4B00 + ham_Q, both positive normal
+// f16 values whose order is the order of the distances (ham <= 127 keeps each in 7 bits; the
+// partial sums of the first words stay inside [0, 127] too). WORDS MFMAs cover 32 col1 x 64
+// col0 pairs: the same matrix-core work per pair as the one-product keys.
+//
+// The keys carry no column. Per wide tile (64 col0) and block (32 col1) the tree gives the
+// block's minimum distance per col0 (both lane halves combined by one v_permlane32_swap per
+// two tiles, as in pair_reduce); against the running minimum R (packed, per col0):
+//   block > R: nothing;  block == R: a second column at the running minimum -> duplicate
+//   (tracked as M = min over blocks of (block - R), packed; 0 = tie); block < R: a new
+//   minimum: the rare branch finds its first column in the block and whether the block holds
+//   it twice ((distance, row) keys through v_perm + v_pk_min_u16, first and reversed rows),
+//   and resets M. Any block order gives the same result (a tie with a later-improved minimum
+//   is forgotten on the improvement, exactly as the reference's strict '<' scan would).
+// Columns beyond the image in the partial block are set to 0x7BFF (the largest finite f16)
+// before the tree.
+#include "search_dev.hpp"
+
+#include <type_traits>
+
+namespace bicos_hip {
+
+namespace {
+
+constexpr uint32_t LUT_PA = 0xAAA22A22u;  // right: bit 0 -> +1.0 (0x2), 1 -> -1.0 (0xA)
+constexpr uint32_t LUT_PB = 0x11199199u;  // left: bit 0 -> -0.5 (0x9), 1 -> +0.5 (0x1)
+constexpr int PK_SCALE_HI = 127 + 16;     // E8M0 2^16 for the K-half-0 (col0 P) lanes
+constexpr uint32_t PK_PAD = 0x7BFF7BFFu;
+// Lazy drops (round 6). A strict drop of the running minimum used to branch into (distance,
+// row) key trees that found its first row and whether the block holds it twice -- one
+// wave-uniform branch whenever any of the wave's 128 col0 dropped, ~150 VALU; on random
+// descriptors most blocks of a scan take it. Now a drop only records the block base (C) and
+// clears the tie marker, and each col0 rescans its final block once after the scan, from the
+// right row's raw words staged in LDS: 32 popcounts of WORDS words, the first col1 at the
+// minimum and whether it occurs twice (rescan). The plan chooses per shape (PK_LAZY_MIN_COLS,
+// search_plan.hpp); BICOS_PK_LAZY=0 builds the branch only (A/B).
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+typedef short i16x2 __attribute__((ext_vector_type(2)));
+
+// v_pk_minimum3_f16 on two packed positive f16 keys per register
+__device__ __forceinline__ uint32_t pkmin3(uint32_t a, uint32_t b, uint32_t c) {
+    const h2 x = __builtin_bit_cast(h2, a), y = __builtin_bit_cast(h2, b), z = __builtin_bit_cast(h2, c);
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_minimum(__builtin_elementwise_minimum(x, y), z));
+}
+__device__ __forceinline__ uint32_t pkminu(uint32_t a, uint32_t b) {  // v_pk_min_u16
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a),
+                                                                  __builtin_bit_cast(u16x2, b)));
+}
+__device__ __forceinline__ uint32_t pksub(uint32_t a, uint32_t b) {  // v_pk_sub_u16 (wraps)
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b));
+}
+__device__ __forceinline__ uint32_t pksign(uint32_t a) {  // 0xFFFF per field with its top bit set
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(i16x2, a) >> (short)15);
+}
+__device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) {
+    return (a & mask) | (b & ~mask);
+}
+
+// minimum over the 16 packed keys of a D tile (v_pk_minimum3_f16 tree, 8 instructions)
+__device__ __forceinline__ uint32_t pk_tree(const v16f& d) {
+    auto k = [&](int r) { return fbits(d[r]); };
+    const uint32_t a0 = pkmin3(k(0), k(1), k(2)), a1 = pkmin3(k(3), k(4), k(5));
+    const uint32_t a2 = pkmin3(k(6), k(7), k(8)), a3 = pkmin3(k(9), k(10), k(11));
+    const uint32_t a4 = pkmin3(k(12), k(13), k(14));
+    return pkminu(pkmin3(a0, a1, a2), pkmin3(a3, a4, k(15)));
+}
+// (distance, row) keys of ONE distance field of a D tile, minimum over this lane half's
+// rows: low half distance * 256 + row, high half distance * 256 + (31 - row), row = (r & 3)
+// + 8 (r >> 2) (the lane half's 4h is added by the caller) -- the first and the LAST row
+// at the minimum distance in one v_pk_min_u16 tree. SEL picks the distance byte of D
+// (byte 2: ham_P, byte 0: ham_Q).
+template <uint32_t SEL>
+__device__ __forceinline__ uint32_t pk_row_keys(const v16f& d) {
+    uint32_t k[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const uint32_t row = (uint32_t)((r & 3) + 8 * (r >> 2));
+        // bytes: [row, ham, 31 - row, ham]
+        k[r] = __builtin_amdgcn_perm(fbits(d[r]), row | ((31u - row) << 8), SEL);
+    }
+#pragma unroll
+    for (int s = 1; s < 16; s *= 2)
+#pragma unroll
+        for (int r = 0; r < 16; r += 2 * s) k[r] = pkminu(k[r], k[r + s]);
+    return k[0];
+}
+constexpr uint32_t PK_SEL_P = 0x06010600u;
+constexpr uint32_t PK_SEL_Q = 0x04010400u;
+
+__device__ __forceinline__ v16f mfma_pk(v4i a, v4i b, v16f c, int sb) {
+    const v8i a8 = {a[0], a[1], a[2], a[3], 0, 0, 0, 0};
+    const v8i b8 = {b[0], b[1], b[2], b[3], 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, 127, 0, sb);
+}
+
+// T wide tiles (64 col0 each) per wave; T = 1 or an even count (tiles reduced in pairs);
+// TAIL: the col0 range starts at a.tail_col0 (the tail launch, as search_mx_kernel's);
+// LIST: compacted col0 entries (as search_mx_kernel's)
+template <int WORDS, int T, bool TAIL, bool LIST, bool AG = false, bool LAZY = PK_LAZY>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
+void search_pk_kernel(typename SearchKArgs<AG>::type ka) {
+    const SearchArgs& a = search_part(ka);
+    static_assert(T == 1 || T % 2 == 0, "wide tiles: 1 or pairs");
+    static_assert(!AG || (!TAIL && !LIST), "the fused agree: main launch, every col0");
+    static_assert(!AG || WORDS == 1 || WORDS == 4, "the fused agree: cfg1's and cfg2's widths");
+    constexpr int NP = T == 1 ? 1 : T / 2;
+    extern __shared__ __attribute__((aligned(16))) v4i lds_mx[];  // [WORDS][chunk]
+
+    int row, tile;
+    if constexpr (LIST) {
+        list_row_tile(a.tiles_per_row, a.rows, row, tile);
+        if (row >= a.rows) return;
+    } else {
+        xcd_row_tile(a.tiles_per_row, row, tile);
+    }
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int h = lane >> 5;
+    const int j = lane & 31;
+    const int cols = a.cols;
+    const int chunk = a.chunk;
+    const int waves = blockDim.x >> 6;
+    const int c0_base = TAIL ? a.tail_col0 : 0;
+    const int c0_wave = c0_base + (tile * waves + wave) * (T * 64);
+    int lcols = cols;
+    const int e0 = c0_base + tile * waves * T * 64;
+    int16_t* ent = nullptr;
+    bool dense = false;  // (as search_mx_kernel's)
+    if constexpr (LIST) {
+        ent = (int16_t*)((char*)lds_mx + list_ent_offset(WORDS * chunk * 16));
+        dense = a.row_valid != nullptr && dense_row(a, row);
+        if (!dense)
+            lcols = list_prologue(a.keep + (size_t)row * a.keep_pitch, cols, (uint32_t*)lds_mx, ent,
+                                  e0, waves * T * 64);
+        if (!TAIL) lcols = min(lcols, a.tail_col0);  // the tail launch takes the entries past it
+        if (e0 >= lcols) return;  // the whole workgroup, past the prologue's barriers
+    }
+    auto lcol = [&](int i) { return LIST && !dense ? (int)ent[i - e0] : i; };
+    auto start_col = [&](int e, int ahead) {
+        return LIST ? min(cols - 1, lcol(min(e, lcols) - 1) + ahead) : min(cols - 1, e - 1);
+    };
+
+    const uint32_t* __restrict__ row0 = a.desc0 + (size_t)row * a.desc_pitch;
+    const uint32_t* __restrict__ row1 = a.desc1 + (size_t)row * a.desc_pitch;
+
+    // B fragments: wide tile t, word w; this lane's col0 is c0_wave + 64 t + lane (K-half h:
+    // P = lanes 0-31, Q = lanes 32-63)
+    v4i bf[T][WORDS];
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const int c0 = c0_wave + 64 * t + lane;
+        const int cl = c0 < lcols ? lcol(c0) : 0;
+#pragma unroll
+        for (int w = 0; w < WORDS; ++w) {
+            const uint32_t x = c0 < lcols ? row0[(size_t)cl * WORDS + w] : 0u;
+            bf[t][w] = expand_bits(x, LUT_PB);
+        }
+    }
+    const int sb = h ? 127 : PK_SCALE_HI;
+    constexpr float CBIAS = 8388608.f + 65536.f * (16 * WORDS) + (float)(0x4B00 + 16 * WORDS);
+    v16f cb;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) cb[r] = CBIAS;
+
+    // per pair p (lanes 0-31: tile 2p, lanes 32-63: tile 2p+1; T = 1: all lanes tile 0):
+    // running minimum, tie marker, first column of the minimum
+    uint32_t R[NP], M[NP], C[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        R[p] = PK_PAD;
+        M[p] = 0xFFFFFFFFu;
+        C[p] = 0u;
+    }
+    auto rrow = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
+
+    // one pair's block minima x (tile 2p) / y (tile 2p+1) at block base B
+    auto pair_step = [&](int p, int B, const v16f& dx, const v16f& dy) {
+        const uint32_t x = pk_tree(dx);
+        const uint32_t y = T == 1 ? x : pk_tree(dy);
+        const auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);
+        const uint32_t comb = pkminu(sw[0], sw[1]);
+        const uint32_t diff = pksub(comb, R[p]);
+        if constexpr (LAZY) {
+            // a strict drop only records the block (branch-free); its first row and whether
+            // it holds the minimum twice are found once, after the scan (pk_rescan)
+            const uint32_t mi = pksign(diff);
+            M[p] = pkminu(M[p], diff) | mi;  // a drop: no tie seen since
+            R[p] = bfi(mi, comb, R[p]);
+            // (one v_bfi_b32 with the block base as an SGPR operand: left alone, the compiler
+            // rebuilt the per-field select from two compares, two cndmasks and a v_perm)
+            uint32_t c = C[p];
+            asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(c) : "v"(mi), "s"((uint32_t)B * 0x10001u));
+            C[p] = c;
+            return;
+        }
+        M[p] = pkminu(M[p], diff);
+        const bool imp = (diff & 0x80008000u) != 0u;
+        if (__builtin_amdgcn_ballot_w64(imp)) {
+            // a new running minimum somewhere in the pair: per (tile, distance field) that
+            // holds one, the first row at it and whether the block holds it twice
+            const uint32_t mi = pksign(diff);
+            const uint32_t hoff = h ? 0xFFFC0004u : 0u;  // rows + 4h (low), 31 - rows - 4h (high)
+            auto field = [&](auto sel_tag, uint32_t top, int sh) {
+                constexpr uint32_t SEL = decltype(sel_tag)::value;
+                const uint64_t bal = __builtin_amdgcn_ballot_w64((diff & top) != 0u);
+                uint32_t lo = (uint32_t)bal, hi = (uint32_t)(bal >> 32);
+                asm volatile("" : "+s"(lo), "+s"(hi));
+                if (T == 1) hi = 0;  // (one tile: both halves hold it)
+                if (!(lo | hi)) return;
+                uint32_t kx = 0, ky = 0;
+                if (lo) kx = pk_row_keys<SEL>(dx) + hoff;
+                if constexpr (T != 1) {
+                    if (hi) ky = pk_row_keys<SEL>(dy) + hoff;
+                }
+                if (!lo) kx = ky;
+                if (!hi) ky = kx;
+                const auto sk = __builtin_amdgcn_permlane32_swap(kx, ky, false, false);
+                const uint32_t res = pkminu(sk[0], sk[1]);
+                const uint32_t first = res & 0x1Fu;
+                const uint32_t uniq = first + ((res >> 16) & 0x1Fu) == 31u ? 0xFFFFu : 0u;
+                const uint32_t fm = mi & (0xFFFFu << sh);
+                R[p] = bfi(fm, comb, R[p]);
+                C[p] = bfi(fm, ((uint32_t)B + first) << sh, C[p]);
+                M[p] = bfi(fm, uniq << sh, M[p]);
+            };
+            field(std::integral_constant<uint32_t, PK_SEL_P>{}, 0x80000000u, 16);
+            field(std::integral_constant<uint32_t, PK_SEL_Q>{}, 0x00008000u, 0);
+        }
+    };
+
+    const bool idle = c0_wave >= lcols;  // wave-uniform; still joins the barriers
+    const int nchunks = (cols + chunk - 1) / chunk;
+    // chunks downwards from the one holding the workgroup's highest col0, blocks downwards
+    // from the wave's highest col0 (stereo matches lie at col1 <= col0 within a few blocks,
+    // so the running minimum is found early and later blocks rarely take the branch)
+    const int cstart = start_col(c0_base + (tile + 1) * waves * T * 64, 0) / chunk;
+    for (int k = 0; k < nchunks; ++k) {
+        int ci = cstart - k;
+        if (ci < 0) ci += nchunks;
+        const int base = ci * chunk;
+        const int ncols = min(chunk, cols - base);
+        if (k) __syncthreads();
+        for (int c = threadIdx.x; c < chunk; c += blockDim.x) {
+            const int c1 = base + c;
+#pragma unroll
+            for (int w = 0; w < WORDS; ++w) {
+                const uint32_t x = c1 < cols ? row1[(size_t)c1 * WORDS + w] : 0u;
+                lds_mx[w * chunk + c] = expand_bits(x, LUT_PA);
+            }
+        }
+        __syncthreads();
+        if (idle) continue;
+
+        const int nfull = ncols / 32;
+        auto block = [&](int b, bool pad) {
+            const int B = base + 32 * b;
+            // (C kept in VGPRs: left alone the compiler re-copies it from SGPRs every block)
+            asm volatile("" : "+v"(cb));
+            v4i af[WORDS];
+#pragma unroll
+            for (int w = 0; w < WORDS; ++w) af[w] = lds_mx[w * chunk + 32 * b + j];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                const int tx = T == 1 ? 0 : 2 * p, ty = T == 1 ? 0 : 2 * p + 1;
+                v16f dx = mfma_pk(af[0], bf[tx][0], cb, sb);
+                v16f dy = dx;
+                if constexpr (T != 1) dy = mfma_pk(af[0], bf[ty][0], cb, sb);
+#pragma unroll
+                for (int w = 1; w < WORDS; ++w) {
+                    dx = mfma_pk(af[w], bf[tx][w], dx, sb);
+                    if constexpr (T != 1) dy = mfma_pk(af[w], bf[ty][w], dy, sb);
+                }
+                if (pad) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const bool in = 32 * b + rrow(r) < ncols;
+                        dx[r] = in ? dx[r] : bitsf(PK_PAD);
+                        dy[r] = in ? dy[r] : bitsf(PK_PAD);
+                    }
+                }
+                pair_step(p, B, dx, dy);
+            }
+        };
+        if ((ncols & 31) != 0) block(nfull, true);
+        const int sb0 = max(0, min(nfull - 1, (start_col(c0_wave + 64 * T, REV_AHEAD) - base) / 32));
+        for (int i = 0; i < nfull; ++i) {
+            int b = sb0 - i;
+            if (b < 0) b += nfull;
+            block(b, false);
+        }
+    }
+    // AG: the workgroup's integer results go through LDS to the fused agree (as in
+    // search_mx_kernel); the chunk region is reused once every wave is done with its blocks.
+    // PK_LAZY: the right row's raw words are staged past those results when they fit (one
+    // coalesced copy per workgroup, L2-resident), for the rescans below; else read from HBM.
+    int16_t* raw_lds = reinterpret_cast<int16_t*>(lds_mx);
+    const int wg_c0 = c0_base + tile * waves * T * 64;
+    const int row_off = (waves * T * 64 * 2 + 15) & ~15;  // bytes: past raw_lds
+    const bool staged = LAZY && (size_t)WORDS * chunk * 16 >= (size_t)row_off + (size_t)cols * WORDS * 4;
+    if (!AG && !staged && idle) return;
+    if (AG || staged) __syncthreads();
+    uint32_t* row_lds = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds_mx) + row_off);
+    if (staged) {
+        const int nw = cols * WORDS;
+        if ((reinterpret_cast<uintptr_t>(row1) & 15u) == 0) {
+            for (int i = threadIdx.x; i < nw / 4; i += blockDim.x)
+                reinterpret_cast<v4i*>(row_lds)[i] = reinterpret_cast<const v4i*>(row1)[i];
+            for (int i = nw / 4 * 4 + threadIdx.x; i < nw; i += blockDim.x) row_lds[i] = row1[i];
+        } else {
+            for (int i = threadIdx.x; i < nw; i += blockDim.x) row_lds[i] = row1[i];
+        }
+        __syncthreads();
+        if (!AG && idle) return;
+    }
+    // PK_LAZY: col0 c's final block (base Bb, minimum distance hm) rescanned by popcounts --
+    // the first col1 at hm, and whether it occurs twice there; src = the right row's words
+    auto rescan = [&](const uint32_t* src, int c, int Bb, uint32_t hm, int& best, bool& uniq) {
+        uint32_t aw[WORDS];
+#pragma unroll
+        for (int w = 0; w < WORDS; ++w) aw[w] = row0[(size_t)c * WORDS + w];
+        uint32_t eq = 0;
+#pragma unroll 4
+        for (int r = 0; r < 32; ++r) {
+            const int c1 = Bb + r;
+            const int cc = min(c1, cols - 1);  // (past the row: never counted, read in bounds)
+            uint32_t hsum = 0;
+#pragma unroll
+            for (int w = 0; w < WORDS; ++w) hsum = __popc(aw[w] ^ src[(size_t)cc * WORDS + w]) + hsum;
+            eq |= (c1 < cols && hsum == hm) ? (1u << r) : 0u;
+        }
+        best = Bb + (int)__builtin_ctz(eq | 0x80000000u);
+        uniq = __popc(eq) == 1;
+    };
+
+    int16_t* out = a.out + (size_t)row * a.out_pitch;
+    int jo = j;
+    asm volatile("" : "+v"(jo));
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        if (T == 1 && h) continue;  // one tile: lanes 0-31 hold it
+        const int t = T == 1 ? 0 : 2 * p + h;
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {  // f = 0: high field (col0 P), 1: low field (Q = P + 32)
+            const int c0i = c0_wave + 64 * t + 32 * f + jo;
+            const int sh = f ? 0 : 16;
+            const bool live = !idle && c0i < lcols;
+            int best = (int)((C[p] >> sh) & 0xFFFFu);
+            bool ok = ((M[p] >> sh) & 0xFFFFu) != 0u;
+            if constexpr (LAZY) {
+                // no tie in another block since the drop: count the final block's minima
+                if (live && ok) {
+                    const uint32_t hm = ((R[p] >> sh) & 0xFFFFu) - 0x4B00u;
+                    if (staged)
+                        rescan(row_lds, lcol(c0i), best, hm, best, ok);
+                    else
+                        rescan(row1, lcol(c0i), best, hm, best, ok);
+                }
+            }
+            if constexpr (!LIST && !AG) {  // dense-row fast path: this tile's valid count
+                if (a.row_valid)
+                    tile_valid_store(a, row, c0_wave + 64 * t + 32 * f, live && ok, best, jo == 0);
+            }
+            if (!live) continue;
+            const int c0 = lcol(c0i);
+            int16_t v;
+            if (a.out_mode == 0)
+                v = ok ? (int16_t)(c0 - best) : INVALID_I16;
+            else
+                v = ok ? (int16_t)best : (int16_t)-1;
+            if constexpr (AG)
+                raw_lds[c0 - wg_c0] = v;
+            else
+                out[c0] = v;
+        }
+    }
+    if constexpr (AG) {
+        __syncthreads();
+        // (n = 8 with 32-bit descriptors, cfg1; n = 33 with 128-bit, cfg2 / cfg5)
+        fused_agree<WORDS == 1 ? FUSED_AGREE_N_PK : FUSED_AGREE_N>(
+            ka.ag, row, wg_c0, min(waves * T * 64, cols - wg_c0), raw_lds);
+    }
+}
+
+}  // namespace
+
+// The instantiations that are built: 1, 2 or (32/64-bit descriptors) 4 wide tiles per wave, whole
+// rows or compacted, the drop branch or lazy drops; tails of one wide tile; the fused agree
+// for cfg1's and cfg2's widths with 1 or (128-bit) 2 wide tiles.
+hipError_t launch_pk_variant(const SearchLaunch& l, const SearchArgs& a, const AgreeArgs* ag,
+                             hipStream_t st) {
+    const SearchVariant& v = l.v;
+    if (!PK_LAZY && v.lazy) return hipErrorInvalidValue;
+    // clang-format off
+    return pick<int, 1, 2, 4>(v.words, [&](auto words) {
+    return pick<int, 1, 2, 4>(v.T, [&](auto T) {
+    return pick<bool, false, true>(v.tail, [&](auto tail) {
+    return pick<bool, false, true>(v.list, [&](auto list) {
+    return pick<bool, false, true>(v.agree, [&](auto agree) {
+    return pick<bool, false, PK_LAZY>(v.lazy, [&](auto lazy) {
+        constexpr int W = words.value, TW = T.value;
+        constexpr bool built = agree.value ? !tail.value && !list.value && (W == 1 ? TW == 1 : W == 4 && TW <= 2)
+                               : tail.value ? TW == 1 : TW <= 2 || W <= 2;
+        if constexpr (built)
+            return launch_planned<agree.value>(
+                search_pk_kernel<W, TW, tail.value, list.value, agree.value, lazy.value>, l, a, ag, st);
+        else
+            return hipErrorInvalidValue;
+    }); }); }); }); }); });
+    // clang-format on
+}
+
+}  // namespace bicos_hip

@@ -23,8 +23,7 @@
 //    on the block order and hold for every cols <= 32767.
 //  * No candidate. A pixel whose window holds no column leaves its running minimum at its
 //    initial value (or at KEY_PAD, from masked pairs): tested before the key is decoded.
-#include "kernels.hpp"
-#include "search_mx_common.hpp"
+#include "search_dev.hpp"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -55,14 +54,8 @@ __global__ __launch_bounds__(512) void search_range_kernel(SearchRangeArgs ka) {
     constexpr int WL = 2 * KS;  // LDS word slots per col1 (W=1: 1 pad)
     extern __shared__ __attribute__((aligned(16))) v4i lds_rg[];  // [WL][chunk]
 
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x;
-    // XCD-aware order: the tiles of one row on one XCD (shared right row in its L2)
-    const int per_xcd = (nwg + 7) / 8;
-    int logical = (bid % 8) * per_xcd + bid / 8;
-    if (nwg % 8 != 0) logical = bid;
-    const int row = logical / a.tiles_per_row;
-    const int tile = logical % a.tiles_per_row;
+    int row, tile;
+    xcd_row_tile(a.tiles_per_row, row, tile);
 
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -88,13 +81,7 @@ __global__ __launch_bounds__(512) void search_range_kernel(SearchRangeArgs ka) {
         const int c0 = c0_wave + 32 * t + j;
         dlo_lane[t] = max(dmin, c0 - (cols - 1));
 #pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            const int w = 2 * s + h;
-            uint32_t x = 0;
-            if (c0 < cols && w < WORDS) x = row0[(size_t)c0 * WORDS + w];
-            if (WORDS == 8 && KS == 4 && w == 7) x &= 0x7FFFFFFFu;  // bit 255 masked
-            bf[t][s] = expand_bits(x, LUT_B);
-        }
+        for (int s = 0; s < KS; ++s) bf[t][s] = expand_bits(desc_word<WORDS, KS>(row0, c0, 2 * s + h, c0 < cols), LUT_B);
     }
 
     uint32_t m1[T];
@@ -134,10 +121,7 @@ __global__ __launch_bounds__(512) void search_range_kernel(SearchRangeArgs ka) {
             const int c1 = base + c;
 #pragma unroll
             for (int w = 0; w < WL; ++w) {
-                uint32_t x = 0;
-                if (c1 < cols && w < WORDS) x = row1[(size_t)c1 * WORDS + w];
-                if (WORDS == 8 && KS == 4 && w == 7) x &= 0x7FFFFFFFu;
-                lds_rg[w * chunk + c] = expand_bits(x, LUT_A);
+                lds_rg[w * chunk + c] = expand_bits(desc_word<WORDS, KS>(row1, c1, w, c1 < cols), LUT_A);
             }
         }
         __syncthreads();

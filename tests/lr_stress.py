@@ -1,4 +1,4 @@
-"""Randomised parity stress of the one-launch Consistency search (search_mx.hip
+"""Randomised parity stress of the one-launch Consistency search (search_lr.hip
 search_lr_kernel) against the oracle at the descriptor level: random widths (1..2048), used
 bits (129..154), max_lr_diff (0..6), row counts and descriptor families (random, shifted
 copies with bit flips, low-entropy with heavy ties both ways, few distinct popcounts). Test

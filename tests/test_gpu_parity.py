@@ -847,7 +847,7 @@ def test_mx_search_edges(gpu, oracle, words, W):
         gpu.tune(0, 0, 0, 0)
 
 
-# Tail workgroups (search_mx.hip launch_mx_tt / launch_pk, round 4): a row remainder of at most
+# Tail workgroups (search_plan.cpp tail_launch, round 4): a row remainder of at most
 # half a workgroup and 8 waves x 2 tiles goes to one extra workgroup per row with 1 or 2 tiles
 # per wave. Widths on either side of every selection boundary for 4-tile (per workgroup 1024
 # col0) and 8-tile (2048) main workgroups -- remainder 1, 255/256 (1 tile), 257, 512 (2 tiles),
@@ -880,7 +880,7 @@ def test_search_tail_workgroups(gpu, oracle, words, W):
         gpu.tune(0, 0, 0, 0)
 
 
-# Packed Hamming keys (search_mx.hip search_pk_kernel, the default NoDuplicates search when
+# Packed Hamming keys (search_pk.hip search_pk_kernel, the default NoDuplicates search when
 # the used-bits hint is <= 127): two distances per accumulator register, no column in the
 # key, first column and in-block duplicates resolved where the running minimum drops.
 # Extreme distances (0 and `bits`), rows where every col1 ties, tie-heavy sparse rows,
@@ -1242,7 +1242,7 @@ def test_int16_disparity_rejects_subpixel(gpu):
                   out=torch.empty((16, 64), dtype=torch.int16, device="cuda"))
 
 
-# ------------------- agree fused into the search launch (search_mx.hip fused_agree, round 5)
+# ------------------- agree fused into the search launch (search_dev.hpp fused_agree, round 5)
 # The headline shape (128-bit NoDuplicates search with 4 tiles per wave and no tail launch,
 # u8 stacks of n = 33, float, no subpixel) runs the agree inside the search's workgroups.
 # Frames tall enough for that geometry (300 rows x 1800 / 2048 columns: >= 2 workgroups per
@@ -1398,7 +1398,7 @@ def test_consistency_in_agree(gpu, oracle, monkeypatch, n, H, W, dt, kw):
     assert not gpu.plan(s0, s1, sub) & _lib.PLAN_CONSISTENCY_IN_AGREE
 
 
-# ------------------------ Consistency's dense-row fast path (search_mx.hip dense_row)
+# ------------------------ Consistency's dense-row fast path (search_dev.hpp dense_row)
 # Rows whose forward search kept >= 7/8 of their col0 run the reverse search over every col0
 # instead of the compacted entries; sparse rows keep the prologue. A frame mixing both (planted
 # stereo rows, rows with an unrelated right image, rows between) against the oracle, every
@@ -1430,7 +1430,7 @@ def test_consistency_dense_rows(gpu, oracle, monkeypatch, n, W, kw, nxc):
         same(host(c), rc)
 
 
-# ------------------------------- Consistency in one pass (search_mx.hip search_lr_kernel)
+# ------------------------------- Consistency in one pass (search_lr.hip search_lr_kernel)
 # First-minimum Consistency over 256-bit descriptors with 129..154 used bits and <= 2048
 # columns: both searches from one set of matrix products and the left-right check in the same
 # workgroup. Descriptor level (bicos_search_device with the used-bits hint) on random,

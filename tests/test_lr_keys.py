@@ -1,4 +1,4 @@
-"""Host-side checks of the one-launch Consistency search's key arithmetic (search_mx.hip
+"""Host-side checks of the one-launch Consistency search's key arithmetic (search_lr.hip
 search_lr_kernel): the FP4 digit encoding of |a| (lr_abs_digits, restated
 here as the kernel computes it), and the float32 exactness of the keys the products form,
 
@@ -18,7 +18,7 @@ def lr_code(u):
 
 
 def lr_abs_digits(n):
-    """Mirror of search_mx.hip lr_abs_digits: the left FP4 codes of the six |a| elements."""
+    """Mirror of search_lr.hip lr_abs_digits: the left FP4 codes of the six |a| elements."""
     if n < 0:
         return [7] * 6
     v0, q = n % 3, n // 3

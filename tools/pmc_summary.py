@@ -57,6 +57,8 @@ def main():
                 name = r["Kernel_Name"]
                 if "bicos_hip" not in name:
                     continue
+                # (template arguments may name types of the anonymous namespace too)
+                name = name.replace("(anonymous namespace)::", "")
                 km = re.search(r"::(\w+)<([^()]*)>\(", name) or re.search(r"::(\w+)\(", name)
                 short = ("%s<%s>" % (km.group(1), km.group(2)) if km and km.lastindex == 2
                          else (km.group(1) if km else name))

@@ -2,6 +2,7 @@
 logs (VGPRs, AGPRs, SGPRs, scratch, occupancy), e.g. before / after a source change:
 
     hipcc ... -c search_mx.hip -Rpass-analysis=kernel-resource-usage 2> new.txt
+    (likewise search_pk.hip, search_lr.hip, search_range.hip; concatenate the logs)
     python tools/resource_diff.py old.txt new.txt [--drop-last-bool]
 
 --drop-last-bool maps a new kernel whose template list gained a trailing bool parameter
