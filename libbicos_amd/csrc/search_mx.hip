@@ -547,8 +547,8 @@ void search_mx_kernel(typename SearchKArgs<V::AG>::type ka) {
             bprev = B;
         };
         // PRUNE: a full block with the second K-step only for the pairs that can reach (see
-        // the kernel's header). af0 holds the block's K-step 0 fragment on entry and the
-        // next block's (nb, if >= 0) on return, read once the last K-step 0 products are
+        // the kernel's header). af0 holds the block's K-step 0 fragment on entry and block
+        // nb's (the next one) on return, read once the last K-step 0 products are
         // issued; the K-step 1 fragment is read here, ahead of the first test. Counts the
         // reaching pairs into wreach.
         auto block_pr = [&](int b, v4i& af0, int nb) {
@@ -559,7 +559,10 @@ void search_mx_kernel(typename SearchKArgs<V::AG>::type ka) {
                 for (int p = 0; p < T / 2; ++p) {
                     d[0] = mfma_fp4(af0, bf[2 * p][0], cc);
                     d[1] = mfma_fp4(af0, bf[2 * p + 1][0], cc);
-                    if (p + 1 == T / 2 && nb >= 0) af0 = lds_mx[h * chunk + 32 * nb + j];
+                    // (both products go out before the first key is read: left alone the
+                    // scheduler may put tile 2p's whole tree ahead of tile 2p+1's product)
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (p + 1 == T / 2) af0 = lds_mx[h * chunk + 32 * nb + j];
                     // the first half of pair_reduce on the partial keys
                     const uint32_t x = min16(d[0], KEY_NONE, 0u);
                     const uint32_t y = min16(d[1], KEY_NONE, 0u);
@@ -569,6 +572,7 @@ void search_mx_kernel(typename SearchKArgs<V::AG>::type ka) {
                     if (__builtin_amdgcn_ballot_w64(lb <= thr[p])) {
                         d[0] = mfma_fp4(af1, bf[2 * p][1], d[0]);
                         d[1] = mfma_fp4(af1, bf[2 * p + 1][1], d[1]);
+                        __builtin_amdgcn_sched_barrier(0);
                         pair_reduce(p, B, d[0], d[1]);
                         thr[p] = (mp[p] | XK_COL) + ah[p];
                         ++wreach;
@@ -624,15 +628,25 @@ void search_mx_kernel(typename SearchKArgs<V::AG>::type ka) {
             int i0 = 0;
             if constexpr (PR) {
                 if (prune_on && nfull > 0) {
-                    auto bidx = [&](int i) {
-                        int b = sb - i;
-                        return b0 + (b < 0 ? b + nfull : b);
-                    };
-                    v4i af0 = lds_mx[h * chunk + 32 * bidx(0) + j];
+                    // The scalar unit's instructions take issue slots of the wave like the
+                    // VALU's, so the loop carries little of them: the blocks
+                    // up to the end of the fallback's window run in an inner loop that only
+                    // steps the block index (wrapping) and counts down -- the window is looked
+                    // at between two such runs -- and the next block's fragment is read
+                    // unconditionally (behind the row's last block: the wrapped index, a block
+                    // of this step that nobody uses).
+                    int b = sb;
+                    v4i af0 = lds_mx[h * chunk + 32 * (b0 + b) + j];
                     while (i0 < nfull) {
-                        block_pr(bidx(i0), af0, i0 + 1 < nfull ? bidx(i0 + 1) : -1);
-                        ++i0;
-                        if (++wblocks == PRUNE_WINDOW) {
+                        int n = min(nfull - i0, PRUNE_WINDOW - wblocks);
+                        i0 += n;
+                        wblocks += n;
+                        for (; n > 0; --n) {
+                            const int nb = b > 0 ? b - 1 : nfull - 1;
+                            block_pr(b0 + b, af0, b0 + nb);
+                            b = nb;
+                        }
+                        if (wblocks == PRUNE_WINDOW) {
                             const bool fall = 8 * wreach >= 7 * PRUNE_WINDOW * (T / 2);
                             wblocks = wreach = 0;
                             if (fall) {
