@@ -294,6 +294,13 @@ int bicos_agree_stage_device(const int16_t* raw, const void* stack0, const void*
 int bicos_match_plan(bicos_engine* e, const void* stack0, const void* stack1, int n, int rows,
                      int cols, size_t row_pitch, size_t plane_pitch, int depth,
                      const BicosConfig* cfg, int has_nxcorr);
+/* Whether the NoDuplicates search of rows x cols descriptors of `words` 32-bit words, `bits`
+ * of them used (0: unknown, as bicos_search_device's flags), runs its main launch as the
+ * pruned packed-key kernel (search_pkp_kernel) instead of the one-product one: 1 or 0.
+ * fused != 0: the search inside the fused search + agree launch of stacks of n u8 images
+ * (0 where that launch is not planned); else n is ignored. For tests; no HIP call, e may be
+ * NULL. */
+int bicos_search_packed(bicos_engine* e, int rows, int cols, int words, int bits, int n, int fused);
 
 /* bicos_match_device from its search on: desc0 / desc1 are the two stacks' descriptors as
  * bicos_transform_device writes them (rows x bicos_desc_pitch(cols, words) uint32, words =

@@ -59,7 +59,7 @@ EXPORTS = (
     "bicos_match_device", "bicos_match_device_i16", "bicos_match_host", "bicos_match_host_multi", "bicos_match_bands_device",
     "bicos_desc_pitch", "bicos_transform_device", "bicos_search_device",
     "bicos_agree_device", "bicos_subpixel_device", "bicos_agree_stage_device", "bicos_build_info",
-    "bicos_match_plan", "bicos_search_agree_device",
+    "bicos_match_plan", "bicos_search_agree_device", "bicos_search_packed",
     "bicos_match_device_range", "bicos_match_host_range", "bicos_search_device_range",
 )
 
@@ -156,6 +156,8 @@ def lib() -> ctypes.CDLL:
     L.bicos_agree_stage_device.restype = I
     L.bicos_match_plan.argtypes = [P, P, P, I, I, I, Z, Z, I, ctypes.POINTER(BicosConfig), I]
     L.bicos_match_plan.restype = I
+    L.bicos_search_packed.argtypes = [P, I, I, I, I, I, I]
+    L.bicos_search_packed.restype = I
     L.bicos_search_agree_device.argtypes = [P, P, P, P, P, I, I, I, Z, Z, I,
                                             ctypes.POINTER(BicosConfig), I, P, P, P]
     L.bicos_search_agree_device.restype = I

@@ -189,6 +189,13 @@ static bool prune_search() {
     static const bool on = env_on("BICOS_MX_PRUNE");
     return on;
 }
+// That search's pruned main launch of 4 tiles per wave on packed keys where the descriptors'
+// used bits allow (search_pk.hip search_pkp_kernel; BICOS_MX_PACKED=0: the one-product kernel;
+// read once)
+static bool packed_search() {
+    static const bool on = env_on("BICOS_MX_PACKED");
+    return on;
+}
 // Consistency's left-right check inside the agree launch (kernels.hip agree_lds_kernel CONS;
 // BICOS_FUSE_CONS=0: consistency_kernel + the agree; read once)
 static bool fuse_consistency() {
@@ -230,7 +237,19 @@ static bicos_hip::MxGeometry mx_geometry(const bicos_engine* e, int rows, int co
         tuned ? e->tune_variant - 64 : 0, bits);
     g.stream = stream_search() ? 1 : 0;
     g.prune = prune_search() ? 1 : 0;
+    if (!packed_search()) g.packed = 0;
     return g;
+}
+
+// Whether the NoDuplicates search of rows x cols descriptors of `words` words with `bits` used
+// bits (0: unknown) -- fused: inside the fused search + agree launch of a stack of n images --
+// runs its main launch on packed keys (bicos_search_packed, bicos_c.h)
+bool search_runs_packed(const bicos_engine* e, int rows, int cols, int words, int bits, int n,
+                        bool fused) {
+    if (rows <= 0 || cols <= 0 || !use_mx(e)) return false;
+    const bicos_hip::MxGeometry g = mx_geometry(e, rows, cols, words, bits);
+    if (fused && !fuse_agree()) return false;
+    return bicos_hip::search_mx_packed(g, rows, cols, words, fused ? n : 0);
 }
 
 // Number of x the reference's subpixel loop visits: for (float x = -1.f; x <= 1.f; x += step)

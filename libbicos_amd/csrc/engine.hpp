@@ -249,6 +249,11 @@ MatchPlan match_plan(const bicos_engine* e, int n, int rows, int cols, size_t ro
                      size_t plane_pitch, int depth, const BicosConfig& cfg, bool has_nxcorr,
                      const void* s0, const void* s1, bool ranged = false);
 
+// bicos_search_packed (bicos_c.h): whether this NoDuplicates search's main launch runs on packed
+// keys (search_pk.hip search_pkp_kernel)
+bool search_runs_packed(const bicos_engine* e, int rows, int cols, int words, int bits, int n,
+                        bool fused);
+
 // Host buffers in and out (the reference's cv::Mat path, src/impl/cpu.cpp:100-159): the
 // stacks are uploaded in row bands through pinned slots on a copy stream while earlier
 // bands match on the compute stream; the maps are downloaded into `disp` / `corr` (dense

@@ -244,6 +244,10 @@ int bicos_match_plan(bicos_engine* e, const void* stack0, const void* stack1, in
                       stack0, stack1).bits();
 }
 
+int bicos_search_packed(bicos_engine* e, int rows, int cols, int words, int bits, int n, int fused) {
+    return search_runs_packed(e, rows, cols, words, bits, n, fused != 0) ? 1 : 0;
+}
+
 int bicos_search_agree_device(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1,
                               const void* stack0, const void* stack1, int n, int rows, int cols,
                               size_t row_pitch, size_t plane_pitch, int depth,

@@ -153,6 +153,11 @@ struct MxGeometry {
     // minimum, with a per-wave fallback (search_mx.hip search_mx_kernel PRUNE); 0: every block
     // in full
     int prune;
+    // 1 (search_mx_geometry's default where the caller states <= PK_MAX_BITS used bits of a
+    // 128-bit descriptor): the pruned main launch of 4 tiles per wave runs on packed keys
+    // (search_pk.hip search_pkp_kernel) where the raw right row fits the LDS stage
+    // (search_plan.cpp packed_search); 0: the one-product kernel
+    int packed;
 };
 // bits: highest used descriptor bit + 1 when the bits above are known to be zero (0 =
 // all of them)
@@ -172,6 +177,10 @@ bool search_mx_agree_fusable(const MxGeometry& g, int words, bool nodupes, int c
 // shape is hipErrorInvalidValue.
 hipError_t launch_search_mx_agree(SearchArgs a, const AgreeArgs& ag, const MxGeometry& g, int words,
                                   hipStream_t st);
+// Whether launch_search_mx's (n == 0) or launch_search_mx_agree's (n: the stack depth; false
+// where the shape is not fusable) NoDuplicates main launch over every col0 runs on packed keys
+// (search_pk.hip search_pkp_kernel, MxGeometry.packed). No HIP call.
+bool search_mx_packed(const MxGeometry& g, int rows, int cols, int words, int n);
 // Consistency in one pass (search_lr.hip search_lr_kernel): the forward and the reverse
 // search from the same matrix products and the left-right check (reference bicos.hpp:78-113,
 // no NoDuplicates), one workgroup per row; a.out gets consistency_kernel's disparity map

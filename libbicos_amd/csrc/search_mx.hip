@@ -117,8 +117,8 @@ constexpr int XKF_K0 = 8160;
 // block reaches and the test is pure overhead. A wave counts its reaching pair-blocks (SALU,
 // from the ballots the branch takes anyway) over windows of PRUNE_WINDOW visited blocks, all
 // through the scan; a window in which >= 7/8 of them reached sends the wave to the unpruned
-// loop for the rest of the row.
-constexpr int PRUNE_WINDOW = 8;
+// loop for the rest of the row (PRUNE_WINDOW: search_plan.hpp, shared with
+// search_pk.hip's pruned kernel).
 
 // Diagnostic builds (tools/build_diag.sh, -DBICOS_MX_DIAG=1..5; results are WRONG, timing only):
 // 1 = MFMA skeleton, one key per tile; 2 = + the first-minimum tree only; 3 = the real kernel
@@ -830,6 +830,15 @@ constexpr bool mx_built(const SearchVariant& v) {
 hipError_t launch_mx_variant(const SearchLaunch& l, const SearchArgs& a, const AgreeArgs* ag,
                              hipStream_t st) {
     const SearchVariant& v = l.v;
+    if (v.packed) {
+        // the same geometry on packed keys (search_pk.hip search_pkp_kernel): two 32-col0 tiles are one
+        // wide tile, the drops lazy
+        SearchLaunch pl = l;
+        pl.v.family = SearchFamily::pk;
+        pl.v.T = v.T / 2;
+        pl.v.lazy = true;
+        return launch_pk_variant(pl, a, ag, st);
+    }
     // clang-format off
     return pick<int, 1, 2, 4, 8>(v.words, [&](auto words) {
     return pick<int, 1, 2, 3, 4>(v.ksteps, [&](auto ksteps) {

@@ -32,6 +32,33 @@
 //   is forgotten on the improvement, exactly as the reference's strict '<' scan would).
 // Columns beyond the image in the partial block are set to 0x7BFF (the largest finite f16)
 // before the tree.
+//
+// search_pkp_kernel (128-bit descriptors, two wide tiles per wave, lazy drops, main launches
+// over every col0; a kernel of its own, so that search_pk_kernel's instantiations stay as they
+// are): words 2 and 3 only where they can matter. After the MFMAs of words 0 and 1 both fields
+// of every accumulator hold 0x4B00 + 32 + ham_lo (C carries + 64, each word adds ham_w - 16),
+// and the final field is 0x4B00 + ham with ham >= ham_lo. The packed tree of these partial keys,
+// combined over the lane halves as in pair_step, is tested per field against thr = R +
+// 0x00200020 as UNSIGNED 16-BIT INTEGERS (not f16: PK_PAD + 0x20 is a NaN pattern): reach is
+// ham_lo <= running minimum, "<=" because a tie must never be pruned (NoDuplicates needs
+// it). The decision is per wide tile (the ballot's halves): a tile none of whose 64 col0
+// reaches skips its MFMAs of words 2 and 3 and its tree; it enters the pair step, if the
+// other tile takes one, with its partial keys. That is safe under lazy drops: a pruned
+// tile-block has block minimum > R for every col0, and R only falls, so the block is neither
+// a drop nor a tie now or later; its partial keys lie above R too, so all they can give M is
+// a positive value, which never decides anything -- `ok` tests M == 0 only, and a later drop
+// resets M. thr is renewed only where R may have changed. The partial last block never
+// prunes. Fallback as search_mx_kernel's: over windows of PRUNE_WINDOW visited blocks a wave
+// counts its reaching wide-tile-blocks from the branch's own ballots; >= 7/8 of them (14 of
+// 16) send it to the unpruned loop for the rest of the row. (Lazy drops stay under pruning:
+// with the drop branch in the reaching blocks instead of the rescans the fused cfg2 launch
+// took 313.8 instead of 276.2 us.)
+//
+// ST (search_pkp_kernel only; the plan guarantees chunk = 2 * blockDim.x and cols > chunk): the
+// right row streamed exactly as search_mx_kernel ST does -- the workgroup's own chunk
+// expanded whole, the rest of the row in stages of half a chunk alternating between the two
+// halves of the chunk region, the next stage's raw descriptor held in four VGPRs across the
+// block loop, one barrier per stage. Same LDS layout; only the expansion table differs.
 #include "search_dev.hpp"
 
 #include <type_traits>
@@ -401,15 +428,334 @@ void search_pk_kernel(typename SearchKArgs<AG>::type ka) {
     }
 }
 
+// The pruned 128-bit search (see the header): WORDS = 4, one pair of wide tiles per wave, lazy
+// drops, every col0 of the row (no tail, no list); ST: the right row streamed. Prologue, pair
+// step, rescans and epilogue are search_pk_kernel<4, 2, false, false, AG, true>'s.
+template <bool AG, bool ST>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
+void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
+    const SearchArgs& a = search_part(ka);
+    constexpr int WORDS = 4, T = 2;
+    extern __shared__ __attribute__((aligned(16))) v4i lds_mx[];  // [WORDS][chunk]
+
+    int row, tile;
+    xcd_row_tile(a.tiles_per_row, row, tile);
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int h = lane >> 5;
+    const int j = lane & 31;
+    const int cols = a.cols;
+    const int chunk = a.chunk;
+    const int waves = blockDim.x >> 6;
+    const int c0_wave = (tile * waves + wave) * (T * 64);
+
+    const uint32_t* __restrict__ row0 = a.desc0 + (size_t)row * a.desc_pitch;
+    const uint32_t* __restrict__ row1 = a.desc1 + (size_t)row * a.desc_pitch;
+
+    // ST: the raw right descriptor of col1 (zero past the image), and the own chunk's two
+    // columns of this thread, requested ahead of the B-fragment loads below
+    auto raw_col = [&](int c1) {
+        v4i x = {0, 0, 0, 0};
+        if (c1 < cols) {
+#pragma unroll
+            for (int w = 0; w < WORDS; ++w) x[w] = (int)row1[(size_t)c1 * WORDS + w];
+        }
+        return x;
+    };
+    auto put_col = [&](int c, const v4i& x) {  // LDS column c of the chunk region
+#pragma unroll
+        for (int w = 0; w < WORDS; ++w) lds_mx[w * chunk + c] = expand_bits((uint32_t)x[w], LUT_PA);
+    };
+    const int half = chunk >> 1;
+    const int nchunks = (cols + chunk - 1) / chunk;
+    // chunks downwards from the one holding the workgroup's highest col0 (as search_pk_kernel)
+    const int cstart = min(cols - 1, (tile + 1) * waves * T * 64 - 1) / chunk;
+    v4i raw = {0, 0, 0, 0}, raw_hi = {0, 0, 0, 0};
+    if constexpr (ST) {
+        raw = raw_col(cstart * chunk + (int)threadIdx.x);
+        raw_hi = raw_col(cstart * chunk + half + (int)threadIdx.x);
+    }
+
+    // B fragments: wide tile t, word w; this lane's col0 is c0_wave + 64 t + lane
+    v4i bf[T][WORDS];
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const int c0 = c0_wave + 64 * t + lane;
+#pragma unroll
+        for (int w = 0; w < WORDS; ++w) {
+            const uint32_t x = c0 < cols ? row0[(size_t)c0 * WORDS + w] : 0u;
+            bf[t][w] = expand_bits(x, LUT_PB);
+        }
+    }
+    const int sb = h ? 127 : PK_SCALE_HI;
+    constexpr float CBIAS = 8388608.f + 65536.f * (16 * WORDS) + (float)(0x4B00 + 16 * WORDS);
+    v16f cb;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) cb[r] = CBIAS;
+
+    // lanes 0-31: tile 0, lanes 32-63: tile 1 -- running minimum, tie marker, block base of
+    // the last drop; the reach test's threshold R + 32 per field; the fallback's state
+    // (wave-uniform)
+    uint32_t R = PK_PAD, M = 0xFFFFFFFFu, C = 0u;
+    uint32_t thr = PK_PAD + 0x00200020u;
+    bool prune_on = true;
+    int wblocks = 0, wreach = 0;
+    auto rrow = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
+
+    // the lazy pair step from the two trees' results x (tile 0) / y (tile 1) in this lane half
+    // at block base B (a pruned tile passes its partial one); renews thr
+    auto pair_update = [&](int B, uint32_t x, uint32_t y) {
+        const auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);
+        const uint32_t comb = pkminu(sw[0], sw[1]);
+        const uint32_t diff = pksub(comb, R);
+        const uint32_t mi = pksign(diff);
+        M = pkminu(M, diff) | mi;  // a drop: no tie seen since
+        R = bfi(mi, comb, R);
+        asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(C) : "v"(mi), "s"((uint32_t)B * 0x10001u));
+        thr = R + 0x00200020u;
+    };
+
+    const bool idle = c0_wave >= cols;  // wave-uniform; still joins the barriers
+    // ST: streamed stage s (after the own chunk) starts at col1 stage_base(s) and lives in
+    // half s & 1 of the chunk region; 2 (nchunks - 1) of them, the last chunk's possibly
+    // short or empty (they still take their barrier: workgroup-uniform)
+    auto stage_base = [&](int s) {
+        int ci = cstart - 1 - (s >> 1);
+        if (ci < 0) ci += nchunks;
+        return ci * chunk + ((s & 1) ? 0 : half);
+    };
+    const int nstages = ST ? 2 * (nchunks - 1) : 0;
+    const int nsteps = ST ? 1 + nstages : nchunks;
+    if constexpr (ST) {
+        put_col((int)threadIdx.x, raw);
+        put_col(half + (int)threadIdx.x, raw_hi);
+    }
+    for (int k = 0; k < nsteps; ++k) {
+        // this step's columns: col1 base + c for LDS column c, from LDS block b0, ncols of them
+        int base, ncols, b0 = 0;
+        if constexpr (ST) {
+            if (k == 0) {
+                base = cstart * chunk;
+                ncols = min(chunk, cols - base);
+            } else {
+                const int sbase = stage_base(k - 1);
+                b0 = ((k - 1) & 1) ? half >> 5 : 0;
+                base = sbase - 32 * b0;
+                ncols = max(0, min(half, cols - sbase));
+            }
+            if (k == 1) __syncthreads();  // every wave is done with the own chunk
+            if (k >= 1) put_col(32 * b0 + (int)threadIdx.x, raw);
+            if (k < nstages) raw = raw_col(stage_base(k) + (int)threadIdx.x);  // the next stage's
+            __syncthreads();
+        } else {
+            int ci = cstart - k;
+            if (ci < 0) ci += nchunks;
+            base = ci * chunk;
+            ncols = min(chunk, cols - base);
+            if (k) __syncthreads();
+            for (int c = threadIdx.x; c < chunk; c += blockDim.x) put_col(c, raw_col(base + c));
+            __syncthreads();
+        }
+        if (idle) continue;
+
+        const int nfull = ncols / 32;
+        // (block indices: LDS blocks of the chunk region, the step's first one b0)
+        // a block in full: the partial last block (pad) and the fallback's loop
+        auto block = [&](int b, bool pad) {
+            const int B = base + 32 * b;
+            // (C kept in VGPRs: left alone the compiler re-copies it from SGPRs every block)
+            asm volatile("" : "+v"(cb));
+            v4i af[WORDS];
+#pragma unroll
+            for (int w = 0; w < WORDS; ++w) af[w] = lds_mx[w * chunk + 32 * b + j];
+            v16f dx = mfma_pk(af[0], bf[0][0], cb, sb);
+            v16f dy = mfma_pk(af[0], bf[1][0], cb, sb);
+#pragma unroll
+            for (int w = 1; w < WORDS; ++w) {
+                dx = mfma_pk(af[w], bf[0][w], dx, sb);
+                dy = mfma_pk(af[w], bf[1][w], dy, sb);
+            }
+            if (pad) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const bool in = 32 * (b - b0) + rrow(r) < ncols;
+                    dx[r] = in ? dx[r] : bitsf(PK_PAD);
+                    dy[r] = in ? dy[r] : bitsf(PK_PAD);
+                }
+            }
+            pair_update(B, pk_tree(dx), pk_tree(dy));
+        };
+        // a full block with words 2 and 3 only for the wide tiles that can reach (see the
+        // header). af0 holds the block's word-0 fragment on entry and block nb's (the next
+        // one) on return, read once the probe products are issued; the other words' fragments
+        // are read here, at the top of the block. Counts the reaching wide tiles into wreach.
+        auto block_pr = [&](int b, v4i& af0, int nb) {
+            const int B = base + 32 * b;
+            asm volatile("" : "+v"(cb));
+            const v4i af1 = lds_mx[chunk + 32 * b + j];
+            // (words 2 and 3 read here too: read only in the blocks that reach, the fused
+            // cfg2 launch took 275.9 instead of 273.5 us)
+            const v4i af2 = lds_mx[2 * chunk + 32 * b + j];
+            const v4i af3 = lds_mx[3 * chunk + 32 * b + j];
+            v16f dx = mfma_pk(af0, bf[0][0], cb, sb);
+            v16f dy = mfma_pk(af0, bf[1][0], cb, sb);
+            dx = mfma_pk(af1, bf[0][1], dx, sb);
+            dy = mfma_pk(af1, bf[1][1], dy, sb);
+            // (both tiles' probe products go out before the first key is read)
+            __builtin_amdgcn_sched_barrier(0);
+            af0 = lds_mx[32 * nb + j];
+            uint32_t x = pk_tree(dx), y = pk_tree(dy);
+            const auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);
+            // ham_lo <= running minimum in either field, as u16: thr - lb does not wrap
+            // below zero ("<=": a tie reaches)
+            const uint32_t under = pksub(thr, pkminu(sw[0], sw[1])) & 0x80008000u;
+            const uint64_t bal = __builtin_amdgcn_ballot_w64(under != 0x80008000u);
+            if (bal) {
+                uint32_t lo = (uint32_t)bal, hi = (uint32_t)(bal >> 32);
+                asm volatile("" : "+s"(lo), "+s"(hi));
+                if (lo) {
+                    dx = mfma_pk(af2, bf[0][2], dx, sb);
+                    dx = mfma_pk(af3, bf[0][3], dx, sb);
+                    x = pk_tree(dx);
+                    ++wreach;
+                }
+                if (hi) {
+                    dy = mfma_pk(af2, bf[1][2], dy, sb);
+                    dy = mfma_pk(af3, bf[1][3], dy, sb);
+                    y = pk_tree(dy);
+                    ++wreach;
+                }
+                pair_update(B, x, y);
+            }
+        };
+        if ((ncols & 31) != 0) block(b0 + nfull, true);
+        // full blocks downwards from the one holding the wave's highest col0 (clamped)
+        const int sb0 = max(0, min(nfull - 1, (min(cols - 1, c0_wave + 64 * T - 1) - base - 32 * b0) / 32));
+        // The pruned loop over the first i0 blocks of the visiting order -- all of them unless
+        // a window sends the wave to the unpruned loop below for the rest of the row. Shaped
+        // as search_mx_kernel's: an inner run of blocks up to the window's end that only steps
+        // the (wrapping) block index, the next block's word-0 fragment read unconditionally
+        // (behind the last block: the wrapped index, a block nobody uses)
+        int i0 = 0;
+        if (prune_on && nfull > 0) {
+            int b = sb0;
+            v4i af0 = lds_mx[32 * (b0 + b) + j];
+            while (i0 < nfull) {
+                int n = min(nfull - i0, PRUNE_WINDOW - wblocks);
+                i0 += n;
+                wblocks += n;
+                for (; n > 0; --n) {
+                    const int nb = b > 0 ? b - 1 : nfull - 1;
+                    block_pr(b0 + b, af0, b0 + nb);
+                    b = nb;
+                }
+                if (wblocks == PRUNE_WINDOW) {
+                    const bool fall = 8 * wreach >= 7 * PRUNE_WINDOW * T;
+                    wblocks = wreach = 0;
+                    if (fall) {
+                        prune_on = false;
+                        break;
+                    }
+                }
+            }
+        }
+        for (int i = i0; i < nfull; ++i) {
+            int b = sb0 - i;
+            if (b < 0) b += nfull;
+            block(b0 + b, false);
+        }
+    }
+    // The workgroup's integer results (AG) and the right row's raw words for the rescans go
+    // into the chunk region once every wave is done with its blocks (the plan guarantees that
+    // the row fits: packed_search, search_plan.cpp)
+    int16_t* raw_lds = reinterpret_cast<int16_t*>(lds_mx);
+    const int wg_c0 = tile * waves * T * 64;
+    const int row_off = (waves * T * 64 * 2 + 15) & ~15;  // bytes: past raw_lds
+    uint32_t* row_lds = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds_mx) + row_off);
+    __syncthreads();
+    {
+        const int nw = cols * WORDS;
+        if ((reinterpret_cast<uintptr_t>(row1) & 15u) == 0) {
+            for (int i = threadIdx.x; i < nw / 4; i += blockDim.x)
+                reinterpret_cast<v4i*>(row_lds)[i] = reinterpret_cast<const v4i*>(row1)[i];
+        } else {
+            for (int i = threadIdx.x; i < nw; i += blockDim.x) row_lds[i] = row1[i];
+        }
+        __syncthreads();
+        if (!AG && idle) return;
+    }
+    // col0 c's final block (base Bb, minimum distance hm) rescanned by popcounts: the first
+    // col1 at hm, and whether it occurs twice there (as search_pk_kernel's rescan)
+    auto rescan = [&](int c, int Bb, uint32_t hm, int& best, bool& uniq) {
+        uint32_t aw[WORDS];
+#pragma unroll
+        for (int w = 0; w < WORDS; ++w) aw[w] = row0[(size_t)c * WORDS + w];
+        uint32_t eq = 0;
+#pragma unroll 4
+        for (int r = 0; r < 32; ++r) {
+            const int c1 = Bb + r;
+            const int cc = min(c1, cols - 1);  // (past the row: never counted, read in bounds)
+            uint32_t hsum = 0;
+#pragma unroll
+            for (int w = 0; w < WORDS; ++w) hsum = __popc(aw[w] ^ row_lds[(size_t)cc * WORDS + w]) + hsum;
+            eq |= (c1 < cols && hsum == hm) ? (1u << r) : 0u;
+        }
+        best = Bb + (int)__builtin_ctz(eq | 0x80000000u);
+        uniq = __popc(eq) == 1;
+    };
+
+    int16_t* out = a.out + (size_t)row * a.out_pitch;
+    int jo = j;
+    asm volatile("" : "+v"(jo));
+#pragma unroll
+    for (int f = 0; f < 2; ++f) {  // f = 0: high field (col0 P), 1: low field (Q = P + 32)
+        const int c0 = c0_wave + 64 * h + 32 * f + jo;
+        const int sh = f ? 0 : 16;
+        const bool live = !idle && c0 < cols;
+        int best = (int)((C >> sh) & 0xFFFFu);
+        bool ok = ((M >> sh) & 0xFFFFu) != 0u;
+        // no tie in another block since the drop: count the final block's minima
+        if (live && ok) rescan(c0, best, ((R >> sh) & 0xFFFFu) - 0x4B00u, best, ok);
+        if constexpr (!AG) {  // dense-row fast path: this tile's valid count
+            if (a.row_valid) tile_valid_store(a, row, c0_wave + 64 * h + 32 * f, live && ok, best, jo == 0);
+        }
+        if (!live) continue;
+        int16_t v;
+        if (a.out_mode == 0)
+            v = ok ? (int16_t)(c0 - best) : INVALID_I16;
+        else
+            v = ok ? (int16_t)best : (int16_t)-1;
+        if constexpr (AG)
+            raw_lds[c0 - wg_c0] = v;
+        else
+            out[c0] = v;
+    }
+    if constexpr (AG) {
+        __syncthreads();
+        fused_agree<FUSED_AGREE_N>(ka.ag, row, wg_c0, min(waves * T * 64, cols - wg_c0), raw_lds);
+    }
+}
+
 }  // namespace
 
 // The instantiations that are built: 1, 2 or (32/64-bit descriptors) 4 wide tiles per wave, whole
 // rows or compacted, the drop branch or lazy drops; tails of one wide tile; the fused agree
-// for cfg1's and cfg2's widths with 1 or (128-bit) 2 wide tiles.
+// for cfg1's and cfg2's widths with 1 or (128-bit) 2 wide tiles. And search_pkp_kernel, with and
+// without the fused agree and the streamed row.
 hipError_t launch_pk_variant(const SearchLaunch& l, const SearchArgs& a, const AgreeArgs* ag,
                              hipStream_t st) {
     const SearchVariant& v = l.v;
     if (!PK_LAZY && v.lazy) return hipErrorInvalidValue;
+    if (v.prune || v.stream) {  // search_pkp_kernel: the pruned 128-bit lazy search, streamed or not
+        if (!v.prune || !v.lazy || v.words != 4 || v.T != 2 || v.tail || v.list) return hipErrorInvalidValue;
+        // clang-format off
+        return pick<bool, false, true>(v.agree, [&](auto agree) {
+        return pick<bool, false, true>(v.stream, [&](auto stream) {
+            return launch_planned<agree.value>(search_pkp_kernel<agree.value, stream.value>, l, a, ag, st);
+        }); });
+        // clang-format on
+    }
     // clang-format off
     return pick<int, 1, 2, 4>(v.words, [&](auto words) {
     return pick<int, 1, 2, 4>(v.T, [&](auto T) {

@@ -29,6 +29,17 @@ bool mx_streamable(int cols, int chunk, int waves, bool stream) {
     return stream && cols > chunk && chunk == 2 * 64 * waves;
 }
 
+// Whether a pruned main launch runs on packed keys (search_pk.hip search_pkp_kernel): asked
+// for (MxGeometry.packed: 128-bit descriptors whose used bits the caller states, <=
+// PK_MAX_BITS), 4 tiles = 2 wide tiles per wave, and the raw right row fits the LDS stage
+// behind the workgroup's results for the lazy rescans (8 waves: 3968 columns). The geometry
+// is the one-product kernel's: the same workgroups, threads, chunk and LDS bytes.
+bool packed_search(const MxGeometry& g, const SearchVariant& v, int cols) {
+    if (!PK_LAZY || !g.packed || !v.prune || v.T != 4 || v.words != 4 || v.keys != 2 || v.list) return false;
+    const long row_off = (64L * g.waves * v.T + 15) & ~15L;  // the results: int16 per col0
+    return (long)g.chunk * v.words * 16 >= row_off + (long)cols * v.words * 4;
+}
+
 int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 const FusedAgreeShape* fused_agree_shape(int words, int n, SearchFamily family, int tiles) {
@@ -75,7 +86,7 @@ SearchLaunch tail_launch(const SearchLaunch& main, int rows, int cols, int tail_
     SearchVariant v = main.v;
     v.T = tail_tiles;
     v.tail = true;
-    v.agree = v.stream = v.prune = false;
+    v.agree = v.stream = v.prune = v.packed = false;
     int waves = main.block / 64, chunk = main.chunk;
     if (BICOS_TAIL_CHUNK > 0) {
         const int per_wave = col_tile * tail_tiles, rem = cols - main.tail_col0;
@@ -145,6 +156,7 @@ SearchLaunchPlan plan_mx(const SearchArgs& a, const MxGeometry& g, int words, bo
     if (!v.list && words == 4 && v.ksteps == 2 && v.keys == 2 && (v.T == 2 || v.T == 4)) {
         v.stream = mx_streamable(a.cols, g.chunk, g.waves, g.stream != 0);
         v.prune = g.prune != 0;
+        v.packed = packed_search(g, v, a.cols);
     }
     SearchLaunchPlan p;
     p.launch[p.n++] = make_launch(v, a.rows, g.waves, 32, 2 * v.ksteps, g.chunk, tiles_per_row, tail_col0, tail_T);
@@ -165,6 +177,7 @@ MxGeometry search_mx_geometry(int rows, int cols, int words, int lds_bytes, int 
     MxGeometry g;
     g.stream = 1;
     g.prune = 1;
+    g.packed = words == 4 && bits > 0 && bits <= PK_MAX_BITS;
     g.keys = keys == 2 ? 2 : 1;
     // 64-bit K-steps the products need: all of the descriptor unless the caller knows that
     // the bits past `bits` are zero (transform output); only 256-bit descriptors have a
@@ -280,6 +293,17 @@ SearchLaunchPlan plan_search_mx(const SearchArgs& a, const MxGeometry& g, int wo
     if (g.chunk < 32 || (g.chunk & 31)) return invalid();
     if (!ag && g.pk && nodupes) return plan_pk(a, g, words, false);
     return plan_mx(a, g, words, ag ? true : nodupes, ag != nullptr);
+}
+
+bool search_mx_packed(const MxGeometry& g, int rows, int cols, int words, int n) {
+    SearchArgs a{};
+    a.rows = rows;
+    a.cols = cols;
+    AgreeArgs ag{};
+    ag.n = n;
+    if (n && !search_mx_agree_fusable(g, words, true, cols, n, 1, false)) return false;
+    const SearchLaunchPlan p = plan_search_mx(a, g, words, true, n ? &ag : nullptr);
+    return p.ok && p.n > 0 && p.launch[0].v.packed;
 }
 
 bool search_lr_eligible(int words, int bits, int cols) {

@@ -19,6 +19,9 @@ constexpr int PK_MAX_COLS = 32767;
 constexpr int LR_MAX_COLS = FK_MAX_COLS;  // search_lr.hip
 constexpr int LR_FREE_BITS = 38;     // 32 upper-half + 6 lower-half K elements
 constexpr int LR_KSTEPS = 3;
+// The pruned 128-bit searches' fallback (search_mx.hip PRUNE, search_pk.hip search_pkp_kernel): visited
+// blocks per window
+constexpr int PRUNE_WINDOW = 8;
 
 // Lazy drops of the packed-key search (search_pk.hip; BICOS_PK_LAZY=0 builds the branch
 // only, A/B). They pay a fixed rescan per col0 (~32 popcounts of WORDS words); the drop
@@ -76,6 +79,9 @@ struct SearchVariant {
     bool stream = false;   // mx: the right row streamed in half-chunk stages (ST)
     bool prune = false;    // mx: the second K-step only where it can matter (PRUNE)
     bool lazy = false;     // pk: lazy drops
+    // mx, pruned main launches of 4 tiles per wave: run by search_pkp_kernel on packed
+    // keys in the same geometry (launch_mx_variant forwards it); the plan's packed_search
+    bool packed = false;
 };
 
 struct SearchLaunch {

@@ -192,6 +192,12 @@ class Engine:
             _lib.check(rc, "bicos_match_plan")
         return rc
 
+    def search_packed(self, rows: int, cols: int, words: int = 4, bits: int = 0, n: int = 0,
+                      fused: bool = False) -> bool:
+        """bicos_search_packed: whether the NoDuplicates search of this shape (fused: inside the
+        fused search + agree launch of n-image stacks) runs the pruned packed-key kernel."""
+        return bool(self._L.bicos_search_packed(self._h, rows, cols, words, bits, n, int(fused)))
+
     def search_agree(self, desc0: torch.Tensor, desc1: torch.Tensor, stack0: torch.Tensor,
                      stack1: torch.Tensor, cfg: Optional[MatchConfig] = None,
                      out: Optional[torch.Tensor] = None, corrmap: Optional[torch.Tensor] = None,
