@@ -54,6 +54,31 @@
 // with the drop branch in the reaching blocks instead of the rescans the fused cfg2 launch
 // took 313.8 instead of 276.2 us.)
 //
+// EOR (search_pkp_kernel only; BICOS_PKP_EOR=0 launches the instantiations without it): a
+// shorter end of row. A lazy drop also records WHICH LANE HALF of the block holds the new
+// minimum. In pair_update sw[0] / sw[1] are the block minima of the lane's tile over the rows
+// of lane half 0 / 1 (rrow(r) = (r & 3) + 8 (r >> 2) + 4 h: half 0 owns rows 0-3, 8-11, 16-19,
+// 24-27 of the block, half 1 the others). On a strict drop of a field:
+//   sw[0] != sw[1]: every column of the block at the new minimum lies in the half with the
+//     smaller value; bit 15 of the field of C (block bases stay below 2^15) takes the sign of
+//     sw[1] - sw[0], and M takes sw[0] ^ sw[1], some value != 0: "no tie seen since".
+//   sw[0] == sw[1]: the block holds the new minimum in two rows of different halves, that is
+//     in two different columns -- exactly what a tie in a later block would have meant. M
+//     takes sw[0] ^ sw[1] = 0, the tie marker, and no rescan is needed for this col0.
+// Why that is exact: R ends as the row's minimum distance hm, and reaches it by a strict drop
+// in the first visited block whose minimum is hm; C holds that block and half. If M ends 0,
+// either a later block had minimum hm too (as before) or both halves of C's block did: a
+// second column at hm either way, invalid. A later strict drop overwrites M and C as a whole,
+// so a duplicate of a minimum that was improved on is forgotten, as before. If M ends != 0,
+// every column at hm lies in the recorded half of C's block, and the rescan of its 16 rows
+// counts them and finds the first: the same answer as the rescan of all 32. The rescan runs
+// in two levels: ham_lo (words 0 and 1) of the 16 rows against hm, then the full distance of
+// the candidates only (ham >= ham_lo, so a column at hm is always a candidate), one per lane
+// and trip of a loop that runs the wave's largest candidate count. A pruned tile's partial
+// keys lie above R in every field, so they never take the drop's side of any of this.
+// EOR also requests the raw right row and the lane's two left descriptors before the barrier
+// that waits for the workgroup's slowest wave, and writes the row to LDS behind it.
+//
 // ST (search_pkp_kernel only; the plan guarantees chunk = 2 * blockDim.x and cols > chunk): the
 // right row streamed exactly as search_mx_kernel ST does -- the workgroup's own chunk
 // expanded whole, the rest of the row in stages of half a chunk alternating between the two
@@ -61,6 +86,8 @@
 // block loop, one barrier per stage. Same LDS layout; only the expansion table differs.
 #include "search_dev.hpp"
 
+#include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 namespace bicos_hip {
@@ -71,6 +98,12 @@ constexpr uint32_t LUT_PA = 0xAAA22A22u;  // right: bit 0 -> +1.0 (0x2), 1 -> -1
 constexpr uint32_t LUT_PB = 0x11199199u;  // left: bit 0 -> -0.5 (0x9), 1 -> +0.5 (0x1)
 constexpr int PK_SCALE_HI = 127 + 16;     // E8M0 2^16 for the K-half-0 (col0 P) lanes
 constexpr uint32_t PK_PAD = 0x7BFF7BFFu;
+// search_pkp_kernel EOR: the end-of-row loads requested ahead of the barrier behind the scan
+// (BICOS_PKP_EARLY=0 builds them behind it: A/B of the two parts of EOR)
+#ifndef BICOS_PKP_EARLY
+#define BICOS_PKP_EARLY 1
+#endif
+constexpr bool PKP_EARLY = BICOS_PKP_EARLY != 0;
 // Lazy drops (round 6). A strict drop of the running minimum used to branch into (distance,
 // row) key trees that found its first row and whether the block holds it twice -- one
 // wave-uniform branch whenever any of the wave's 128 col0 dropped, ~150 VALU; on random
@@ -82,6 +115,7 @@ constexpr uint32_t PK_PAD = 0x7BFF7BFFu;
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t v2u __attribute__((ext_vector_type(2)));
 
 // v_pk_minimum3_f16 on two packed positive f16 keys per register
 __device__ __forceinline__ uint32_t pkmin3(uint32_t a, uint32_t b, uint32_t c) {
@@ -430,8 +464,9 @@ void search_pk_kernel(typename SearchKArgs<AG>::type ka) {
 
 // The pruned 128-bit search (see the header): WORDS = 4, one pair of wide tiles per wave, lazy
 // drops, every col0 of the row (no tail, no list); ST: the right row streamed. Prologue, pair
-// step, rescans and epilogue are search_pk_kernel<4, 2, false, false, AG, true>'s.
-template <bool AG, bool ST>
+// step, rescans and epilogue are search_pk_kernel<4, 2, false, false, AG, true>'s; EOR: the
+// drop's lane half recorded, 16-row two-level rescans, early end-of-row loads (see the header).
+template <bool AG, bool ST, bool EOR>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
 void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     const SearchArgs& a = search_part(ka);
@@ -510,9 +545,22 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         const uint32_t comb = pkminu(sw[0], sw[1]);
         const uint32_t diff = pksub(comb, R);
         const uint32_t mi = pksign(diff);
-        M = pkminu(M, diff) | mi;  // a drop: no tie seen since
-        R = bfi(mi, comb, R);
-        asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(C) : "v"(mi), "s"((uint32_t)B * 0x10001u));
+        if constexpr (EOR) {
+            // a drop: the tie marker restarts from the two halves' minima (0: the block holds
+            // the new minimum in both), and bit 15 of C's field says which half holds it
+            // (v_bfi_b32 by hand, as below: left alone the compiler selects per field)
+            uint32_t m = pkminu(M, diff);
+            asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(m) : "v"(mi), "v"(sw[0] ^ sw[1]));
+            M = m;
+            R = bfi(mi, comb, R);
+            uint32_t bh = pksub(sw[1], sw[0]);
+            asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(bh) : "v"(0x7FFF7FFFu), "s"((uint32_t)B * 0x10001u));
+            asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(C) : "v"(mi), "v"(bh));
+        } else {
+            M = pkminu(M, diff) | mi;  // a drop: no tie seen since
+            R = bfi(mi, comb, R);
+            asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(C) : "v"(mi), "s"((uint32_t)B * 0x10001u));
+        }
         thr = R + 0x00200020u;
     };
 
@@ -673,6 +721,130 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     const int wg_c0 = tile * waves * T * 64;
     const int row_off = (waves * T * 64 * 2 + 15) & ~15;  // bytes: past raw_lds
     uint32_t* row_lds = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds_mx) + row_off);
+    if constexpr (EOR) {
+        int16_t* out = a.out + (size_t)row * a.out_pitch;
+        // The raw row's first EARLY * blockDim columns (one dwordx4 each) and this lane's two
+        // left descriptors are requested here, behind the wave's own last block; they arrive
+        // while the barrier waits for the workgroup's slowest wave. (k * blockDim < cols is
+        // workgroup-uniform: a scalar branch around each load, none waits for another.)
+        constexpr int EARLY = 8;
+        const bool al16 = (reinterpret_cast<uintptr_t>(row1) & 15u) == 0;
+        const int bd = (int)blockDim.x;
+        v4i early[EARLY];
+        if constexpr (!PKP_EARLY) __syncthreads();
+        if (al16) {
+#pragma unroll
+            for (int k = 0; k < EARLY; ++k) {
+                early[k] = v4i{0, 0, 0, 0};
+                if (k * bd < cols)
+                    early[k] = reinterpret_cast<const v4i*>(row1)[min(k * bd + (int)threadIdx.x, cols - 1)];
+            }
+        }
+        v4i aw[2];
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            const int c = min(c0_wave + 64 * h + 32 * f + j, cols - 1);
+#pragma unroll
+            for (int w = 0; w < WORDS; ++w) aw[f][w] = (int)row0[(size_t)c * WORDS + w];
+        }
+        if constexpr (PKP_EARLY) __syncthreads();
+        if (al16) {
+#pragma unroll
+            for (int k = 0; k < EARLY; ++k) {
+                const int i = k * bd + (int)threadIdx.x;
+                if (i < cols) reinterpret_cast<v4i*>(row_lds)[i] = early[k];
+            }
+            for (int i = EARLY * bd + (int)threadIdx.x; i < cols; i += bd)
+                reinterpret_cast<v4i*>(row_lds)[i] = reinterpret_cast<const v4i*>(row1)[i];
+        } else {
+            for (int i = threadIdx.x; i < cols * WORDS; i += bd) row_lds[i] = row1[i];
+        }
+        __syncthreads();
+        if (!AG && idle) return;
+
+        // col0's final block rescanned in the recorded half only (16 rows from col1 B0 = block
+        // base + 4 half, at (k & 3) + 8 (k >> 2)), in two levels: ham_lo of the 16 rows, then
+        // the full distance of the rows with ham_lo <= hm. Masks are indexed by the row's
+        // offset from B0. CLAMP: the block may reach past the row (the partial last block) --
+        // those rows are read in bounds and never counted.
+        auto rescan = [&](auto clamp_tag, const v4i& x, int B0, uint32_t hm, int& best, bool& uniq) {
+            constexpr bool CLAMP = decltype(clamp_tag)::value;
+            uint32_t cand = 0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int r = (k & 3) + 8 * (k >> 2);
+                const int cc = CLAMP ? min(B0 + r, cols - 1) : B0 + r;
+                const v2u w = *reinterpret_cast<const v2u*>(row_lds + (size_t)cc * WORDS);
+                const uint32_t lo = __popc((uint32_t)x[0] ^ w[0]) + __popc((uint32_t)x[1] ^ w[1]);
+                cand |= lo <= hm ? (1u << r) : 0u;
+            }
+            if constexpr (CLAMP) {
+                const int n = cols - B0;  // (>= 1: the recorded half holds a column of the row)
+                cand &= n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u;
+            }
+            uint32_t eq = 0;
+            while (__builtin_amdgcn_ballot_w64(cand != 0u)) {
+                const bool act = cand != 0u;
+                const int r = act ? (int)__builtin_ctz(cand | 0x80000000u) : 0;
+                cand &= cand - 1u;
+                const v4i w = *reinterpret_cast<const v4i*>(row_lds + (size_t)(B0 + r) * WORDS);
+                uint32_t hsum = 0;
+#pragma unroll
+                for (int q = 0; q < WORDS; ++q) hsum = __popc((uint32_t)(x[q] ^ w[q])) + hsum;
+                eq |= (act && hsum == hm) ? (1u << r) : 0u;
+            }
+            best = B0 + (int)__builtin_ctz(eq | 0x80000000u);
+            uniq = __popc(eq) == 1;
+        };
+
+        int jo = j;
+        asm volatile("" : "+v"(jo));
+        // (wave-uniform: does any rescan of this wave touch the partial last block)
+        bool need[2];
+        bool part = false;
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {
+            const int sh = f ? 0 : 16;
+            need[f] = !idle && c0_wave + 64 * h + 32 * f + jo < cols && ((M >> sh) & 0xFFFFu) != 0u;
+            part = part || (need[f] && (int)((C >> sh) & 0x7FE0u) + 32 > cols);
+        }
+        const bool anypart = __builtin_amdgcn_ballot_w64(part) != 0;
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {  // f = 0: high field (col0 P), 1: low field (Q = P + 32)
+            const int c0 = c0_wave + 64 * h + 32 * f + jo;
+            const int sh = f ? 0 : 16;
+            const bool live = !idle && c0 < cols;
+            const uint32_t cf = (C >> sh) & 0xFFFFu;
+            int best = (int)(cf & 0x7FFFu);
+            bool ok = need[f];
+            if (ok) {
+                const int B0 = best + (int)((cf >> 15) << 2);
+                const uint32_t hm = ((R >> sh) & 0xFFFFu) - 0x4B00u;
+                if (anypart)
+                    rescan(std::true_type{}, aw[f], B0, hm, best, ok);
+                else
+                    rescan(std::false_type{}, aw[f], B0, hm, best, ok);
+            }
+            if constexpr (!AG) {  // dense-row fast path: this tile's valid count
+                if (a.row_valid) tile_valid_store(a, row, c0_wave + 64 * h + 32 * f, live && ok, best, jo == 0);
+            }
+            if (!live) continue;
+            int16_t v;
+            if (a.out_mode == 0)
+                v = ok ? (int16_t)(c0 - best) : INVALID_I16;
+            else
+                v = ok ? (int16_t)best : (int16_t)-1;
+            if constexpr (AG)
+                raw_lds[c0 - wg_c0] = v;
+            else
+                out[c0] = v;
+        }
+        if constexpr (AG) {
+            __syncthreads();
+            fused_agree<FUSED_AGREE_N>(ka.ag, row, wg_c0, min(waves * T * 64, cols - wg_c0), raw_lds);
+        }
+        return;
+    }
     __syncthreads();
     {
         const int nw = cols * WORDS;
@@ -737,12 +909,22 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     }
 }
 
+// search_pkp_kernel's shorter end of row (EOR; BICOS_PKP_EOR=0: the instantiations without it,
+// the rescans of all 32 rows and the row copy behind the barrier; read once)
+bool pkp_eor() {
+    static const bool on = [] {
+        const char* v = std::getenv("BICOS_PKP_EOR");
+        return !(v && !std::strcmp(v, "0"));
+    }();
+    return on;
+}
+
 }  // namespace
 
 // The instantiations that are built: 1, 2 or (32/64-bit descriptors) 4 wide tiles per wave, whole
 // rows or compacted, the drop branch or lazy drops; tails of one wide tile; the fused agree
 // for cfg1's and cfg2's widths with 1 or (128-bit) 2 wide tiles. And search_pkp_kernel, with and
-// without the fused agree and the streamed row.
+// without the fused agree, the streamed row and the shorter end of row.
 hipError_t launch_pk_variant(const SearchLaunch& l, const SearchArgs& a, const AgreeArgs* ag,
                              hipStream_t st) {
     const SearchVariant& v = l.v;
@@ -752,8 +934,9 @@ hipError_t launch_pk_variant(const SearchLaunch& l, const SearchArgs& a, const A
         // clang-format off
         return pick<bool, false, true>(v.agree, [&](auto agree) {
         return pick<bool, false, true>(v.stream, [&](auto stream) {
-            return launch_planned<agree.value>(search_pkp_kernel<agree.value, stream.value>, l, a, ag, st);
-        }); });
+        return pick<bool, false, true>(pkp_eor(), [&](auto eor) {
+            return launch_planned<agree.value>(search_pkp_kernel<agree.value, stream.value, eor.value>, l, a, ag, st);
+        }); }); });
         // clang-format on
     }
     // clang-format off
