@@ -313,6 +313,49 @@ int bicos_search_agree_device(bicos_engine* e, const uint32_t* desc0, const uint
                               const BicosConfig* cfg, int has_nxcorr, void* disparity,
                               void* corrmap, void* stream);
 
+/* ---------------------------------------------------------- reprojection */
+/* A dense rows x cols disparity map (BICOS_CV_16S or BICOS_CV_32F) through the rig's 4x4 matrix
+ * Q (16 doubles, row-major) to 3-D points: what the reference's command-line tool does with
+ * cv::reprojectImageTo3D and save_pointcloud (src/cli.cpp:238, include/fileutils.hpp:44-89).
+ * For pixel (x = col, y = row) with d = (double)disparity, in IEEE double without contraction:
+ *     o[i] = ((Q[4i]*x + Q[4i+1]*y) + Q[4i+2]*d) + Q[4i+3]      i = 0..3
+ *     iw   = 1.0 / o[3]
+ *     X, Y, Z = (float)(o[0]*iw), (float)(o[1]*iw), (float)(o[2]*iw)
+ * Every pixel falls into exactly one class, tested in this order:
+ *     invalid     int16 -32768; float NaN; with BICOS_REPROJECT_F32_SENTINEL also the float
+ *                 -32768.0f (what a match with the NXC stage and no subpixel step writes for
+ *                 a rejected pixel; without the flag it is reprojected like any number)
+ *     nonfinite   X, Y or Z is not finite
+ *     negative_z  Z < 0.0f, unless BICOS_REPROJECT_ALLOW_NEGATIVE_Z
+ *     kept
+ * Outputs, either alone or both:
+ *     xyz_map  float32 [rows][cols][3]: the point where the pixel is kept, three NaNs elsewhere
+ *     points   float32 [capacity][3]: the kept points in row-major pixel order (deterministic);
+ *              index, optional, int32 [capacity]: each point's pixel row*cols + col;
+ *              counts, uint32[4]: {kept, invalid, nonfinite, negative_z}, summing to rows*cols.
+ *              With kept > capacity the first `capacity` points are written and nothing past
+ *              them; counts[0] is still the full number. counts is written only with points.
+ * rows*cols must fit int32. rows == 0 or cols == 0 is legal (counts all zero). Argument errors
+ * (a type other than 16S / 32F, a negative size, too many pixels, no output, points without
+ * counts, index without points, unknown flag bits, a NULL map or Q) are BICOS_E_ARG before any
+ * HIP call. No reference counterpart in its library. */
+#define BICOS_REPROJECT_ALLOW_NEGATIVE_Z 1
+#define BICOS_REPROJECT_F32_SENTINEL 2
+/* device: asynchronous on `stream`; xyz_map and points may each be NULL (not both);
+ * index may be NULL; counts (device uint32[4]) is required with points. e is needed
+ * for points (workspace); the dense map alone works with e == NULL. */
+int bicos_reproject_device(bicos_engine* e, const void* disparity, int disp_type, int rows,
+                           int cols, const double Q[16], int flags, float* xyz_map,
+                           float* points, int32_t* index, size_t capacity, uint32_t* counts,
+                           void* stream);
+/* host buffers, synchronous, e NULL = default engine: uploads the map, runs the same
+ * launches, downloads counts and then only the first min(kept, capacity) points. */
+int bicos_reproject_host(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                         const double Q[16], int flags, float* xyz_map, float* points,
+                         int32_t* index, size_t capacity, uint32_t counts[4]);
+/* Pixels per segment of the point list's count / scan / write launches (tests). */
+int bicos_reproject_segment(void);
+
 /* Build identification (arch, flags) for reports. */
 const char* bicos_build_info(void);
 

@@ -61,6 +61,7 @@ EXPORTS = (
     "bicos_agree_device", "bicos_subpixel_device", "bicos_agree_stage_device", "bicos_build_info",
     "bicos_match_plan", "bicos_search_agree_device", "bicos_search_packed",
     "bicos_match_device_range", "bicos_match_host_range", "bicos_search_device_range",
+    "bicos_reproject_device", "bicos_reproject_host", "bicos_reproject_segment",
 )
 
 # bicos_match_plan bits (include/bicos_c.h)
@@ -71,6 +72,10 @@ PLAN_REVERSE_COMPACTED = 8
 PLAN_CONSISTENCY_IN_AGREE = 16
 PLAN_DENSE_ROWS = 32
 PLAN_CONSISTENCY_ONE_PASS = 64
+
+# bicos_reproject_* flags (include/bicos_c.h)
+REPROJECT_ALLOW_NEGATIVE_Z = 1
+REPROJECT_F32_SENTINEL = 2
 
 
 def build(verbose: bool = False, jobs: int = 4) -> str:
@@ -169,6 +174,13 @@ def lib() -> ctypes.CDLL:
     L.bicos_match_host_range.restype = I
     L.bicos_search_device_range.argtypes = [P, P, P, I, I, I, I, I, I, I, P, P]
     L.bicos_search_device_range.restype = I
+    PD = ctypes.POINTER(ctypes.c_double)
+    L.bicos_reproject_device.argtypes = [P, P, I, I, I, PD, I, P, P, P, Z, P, P]
+    L.bicos_reproject_device.restype = I
+    L.bicos_reproject_host.argtypes = [P, P, I, I, I, PD, I, P, P, P, Z, P]
+    L.bicos_reproject_host.restype = I
+    L.bicos_reproject_segment.argtypes = []
+    L.bicos_reproject_segment.restype = I
     L.bicos_build_info.restype = ctypes.c_char_p
     L.bicos_build_info.argtypes = []
     _lib = L
@@ -193,6 +205,21 @@ def check_disparity_range(rng):
     if not (-2 ** 31 <= lo and hi < 2 ** 31):
         raise ValueError("disparity_range bounds must fit a C int")
     return lo, hi
+
+
+def reproject_q(Q):
+    """The 16 doubles of a 4x4 matrix (anything numpy reads as one), row-major, as the
+    ctypes array the bicos_reproject_* entries take (ValueError otherwise)."""
+    import numpy as np
+    q = np.asarray(Q, dtype=np.float64)
+    if q.shape != (4, 4):
+        raise ValueError("Q must be a 4x4 matrix, got shape %s" % (q.shape,))
+    return (ctypes.c_double * 16)(*q.ravel().tolist())
+
+
+def reproject_flags(allow_negative_z: bool, sentinel: bool) -> int:
+    return (REPROJECT_ALLOW_NEGATIVE_Z if allow_negative_z else 0) | \
+        (REPROJECT_F32_SENTINEL if sentinel else 0)
 
 
 def check(rc: int, what: str = "bicos") -> None:

@@ -15,6 +15,7 @@
 // never takes effect; here it does.
 #include <bicos/common.hpp>
 #include <bicos/match.hpp>
+#include <bicos_c.h>
 
 #include <chrono>
 #include <cstdio>
@@ -205,10 +206,19 @@ int run(int argc, char** argv) {
         const auto Q = bicos_cli::read_filestorage_matrix(*q_store, "Q");
         fs::path xyz = outfile;
         xyz.replace_extension("xyz");
-        const auto st = bicos_cli::write_xyz(xyz.string(), disp, Q, args.has("allow-negative-z"));
+        // the points come from the GPU (bicos_reproject_host: bicos_cli::write_xyz's arithmetic
+        // bit for bit); only the text is made here
+        const size_t pixels = (size_t)disp.rows() * disp.cols();
+        std::vector<float> points(3 * pixels + 1);
+        uint32_t counts[4] = {0, 0, 0, 0};  // kept, invalid, nonfinite, negative_z
+        if (bicos_reproject_host(nullptr, disp.data(), disp.type(), disp.rows(), disp.cols(),
+                                 Q.data(), args.has("allow-negative-z") ? BICOS_REPROJECT_ALLOW_NEGATIVE_Z : 0,
+                                 nullptr, points.data(), nullptr, pixels, counts) != BICOS_OK)
+            throw std::runtime_error(std::string("reprojection failed: ") + bicos_last_error());
+        bicos_cli::write_xyz_points(xyz.string(), points.data(), counts[0]);
         std::cout << "Saved pointcloud in ascii-format to\t" << xyz << std::endl;
-        if (st.nonfinite) std::cerr << "Skipped " << st.nonfinite << " points with non-finite fp values" << std::endl;
-        if (st.negative_z) std::cerr << "Skipped " << st.negative_z << " points with negative Z values" << std::endl;
+        if (counts[2]) std::cerr << "Skipped " << counts[2] << " points with non-finite fp values" << std::endl;
+        if (counts[3]) std::cerr << "Skipped " << counts[3] << " points with negative Z values" << std::endl;
     }
     return 0;
 }

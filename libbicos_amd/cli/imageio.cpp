@@ -438,6 +438,13 @@ XyzStats write_xyz(const std::string& path, const BICOS::Image& disp,
     return st;
 }
 
+void write_xyz_points(const std::string& path, const float* points, size_t count) {
+    std::ofstream xyz(path);
+    if (!xyz) throw std::runtime_error("cannot write " + path);
+    for (const float* p = points; p != points + 3 * count; p += 3)
+        xyz << p[0] << ' ' << p[1] << ' ' << p[2] << '\n';
+}
+
 void read_stacks(const std::string& folder0, const std::optional<std::string>& folder1,
                  std::vector<Gray>& left, std::vector<Gray>& right) {
     namespace fs = std::filesystem;

@@ -2,8 +2,11 @@
 //
 //   BICOS::match   <- reference BICOS::match (src/lib.cpp:31-49) and the backend entry
 //                     impl::cpu::match (src/impl/cpu.cpp:100-159)
+//   BICOS::reproject  (bicos/reproject.hpp; no reference counterpart in its library)
 #include "engine.hpp"
 
+#include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <memory>
 #include <vector>
@@ -11,6 +14,7 @@
 #include "../../include/bicos/common.hpp"
 #include "../../include/bicos/match.hpp"
 #include "../../include/bicos/hip.hpp"
+#include "../../include/bicos/reproject.hpp"
 
 using bicos_impl::check_hip;
 
@@ -204,6 +208,95 @@ void impl::hip::match(const std::vector<Image>& stack0, const std::vector<Image>
                                       c, has_nxcorr, c.nxcorr_threshold, disparity.data(),
                                       want_corr ? corrmap->data() : nullptr, st, false, nullptr,
                                       nullptr, rg));
+}
+
+// ---------------------------------------------------------------- BICOS::reproject
+// over the C entries (entries.cpp), which validate, lock the engine and launch
+
+namespace {
+
+void check_map(const Image& disparity) {
+    if (disparity.type() != S16 && disparity.type() != F32)
+        throw Exception("reproject: the disparity map must be S16 or F32");
+    if (disparity.step() != (size_t)disparity.cols() * disparity.elemSize() && disparity.rows() > 1)
+        throw Exception("reproject: the disparity map must be dense");
+}
+
+bicos_engine* current_engine() {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    bicos_engine* e = bicos_impl::default_engine(dev);
+    if (!e) throw Exception(bicos_impl::last_error());
+    return e;
+}
+
+}  // namespace
+
+void reproject(const Image& disparity, const Matx44d& Q, Image& xyz, int flags,
+               hipStream_t stream) {
+    check_map(disparity);
+    const int rows = disparity.rows(), cols = disparity.cols();
+    if ((int64_t)cols * 3 > INT32_MAX) throw Exception("reproject: map too wide");
+    xyz.create(rows, 3 * cols, F32, disparity.memory());
+    if (disparity.memory() == Memory::Host)
+        throw_rc(bicos_reproject_host(nullptr, disparity.data(), disparity.type(), rows, cols,
+                                      Q.data(), flags, (float*)xyz.data(), nullptr, nullptr, 0,
+                                      nullptr));
+    else
+        throw_rc(bicos_reproject_device(nullptr, disparity.data(), disparity.type(), rows, cols,
+                                        Q.data(), flags, (float*)xyz.data(), nullptr, nullptr, 0,
+                                        nullptr, stream));
+}
+
+void reproject(const Image& disparity, const Matx44d& Q, float* points, int32_t* index,
+               size_t capacity, uint32_t* counts, int flags, hipStream_t stream) {
+    check_map(disparity);
+    if (disparity.memory() != Memory::Device)
+        throw Exception("reproject: device buffers need a device map");
+    if (!points) throw Exception("reproject: null points");
+    throw_rc(bicos_reproject_device(current_engine(), disparity.data(), disparity.type(),
+                                    disparity.rows(), disparity.cols(), Q.data(), flags, nullptr,
+                                    points, index, capacity, counts, stream));
+}
+
+ReprojectStats reproject(const Image& disparity, const Matx44d& Q, std::vector<float>& points,
+                         int flags, std::vector<int32_t>* index) {
+    check_map(disparity);
+    const int rows = disparity.rows(), cols = disparity.cols();
+    const size_t pixels = (size_t)(rows > 0 ? rows : 0) * (size_t)(cols > 0 ? cols : 0);
+    uint32_t counts[4] = {0, 0, 0, 0};
+    points.resize(3 * pixels + 1);  // (+1: never a null pointer)
+    if (index) index->resize(pixels + 1);
+    if (disparity.memory() == Memory::Host) {
+        throw_rc(bicos_reproject_host(nullptr, disparity.data(), disparity.type(), rows, cols,
+                                      Q.data(), flags, nullptr, points.data(),
+                                      index ? index->data() : nullptr, pixels, counts));
+    } else {
+        // device buffers for every pixel, then only the kept points come down
+        // counts | points | index in one allocation
+        const size_t words = 4 + 3 * pixels + (index ? pixels : 0);
+        void* raw = nullptr;
+        throw_rc(check_hip(hipMalloc(&raw, words * 4), "hipMalloc(points)"));
+        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
+        uint32_t* d_counts = (uint32_t*)raw;
+        float* d_points = (float*)raw + 4;
+        int32_t* d_index = index ? (int32_t*)raw + 4 + 3 * pixels : nullptr;
+        throw_rc(bicos_reproject_device(current_engine(), disparity.data(), disparity.type(), rows,
+                                        cols, Q.data(), flags, nullptr, d_points, d_index, pixels,
+                                        d_counts, nullptr));
+        throw_rc(check_hip(hipMemcpy(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost),
+                           "counts download"));
+        const size_t kept = counts[0];
+        if (kept)
+            throw_rc(check_hip(hipMemcpy(points.data(), d_points, kept * 3 * sizeof(float),
+                                         hipMemcpyDeviceToHost), "points download"));
+        if (kept && index)
+            throw_rc(check_hip(hipMemcpy(index->data(), d_index, kept * sizeof(int32_t),
+                                         hipMemcpyDeviceToHost), "index download"));
+    }
+    points.resize(3 * (size_t)counts[0]);
+    if (index) index->resize(counts[0]);
+    return ReprojectStats{counts[0], counts[1], counts[2], counts[3]};
 }
 
 }  // namespace BICOS

@@ -5,6 +5,7 @@
 // The host-buffer pipeline is host.cpp, the C-ABI entries entries.cpp / multi.cpp, the C++
 // API cxxapi.cpp (engine.hpp).
 #include "engine.hpp"
+#include "reproject.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -548,6 +549,59 @@ int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int row
     }
     if (has_step) return check_hip(bicos_hip::launch_subpixel(aa, depth, dbl, st), "subpixel launch");
     return check_hip(bicos_hip::launch_agree(aa, depth, dbl, st), "agree launch");
+}
+
+// -------------------------------------------------------------- reprojection
+
+int check_reproject(const ReprojectJob& j, const bicos_engine* e, bool needs_engine) {
+    if (j.disp_type != BICOS_CV_16S && j.disp_type != BICOS_CV_32F)
+        return fail(BICOS_E_ARG, "reproject: the disparity map must be CV_16S or CV_32F");
+    if (j.rows < 0 || j.cols < 0) return fail(BICOS_E_ARG, "reproject: negative image size");
+    if ((int64_t)j.rows * j.cols > INT32_MAX)
+        return fail(BICOS_E_ARG, "reproject: rows * cols exceeds int32");
+    if (j.flags & ~(BICOS_REPROJECT_ALLOW_NEGATIVE_Z | BICOS_REPROJECT_F32_SENTINEL))
+        return fail(BICOS_E_ARG, "reproject: unknown flag bits");
+    if (!j.xyz_map && !j.points)
+        return fail(BICOS_E_ARG, "reproject: no output (xyz_map and points both null)");
+    if (j.points && !j.counts) return fail(BICOS_E_ARG, "reproject: points need counts");
+    if (j.index && !j.points) return fail(BICOS_E_ARG, "reproject: index without points");
+    if (j.points && needs_engine && !e)
+        return fail(BICOS_E_ARG, "reproject: points need an engine workspace");
+    if (!j.Q) return fail(BICOS_E_ARG, "reproject: null Q");
+    if (j.rows > 0 && j.cols > 0 && !j.disp) return fail(BICOS_E_ARG, "reproject: null disparity map");
+    return BICOS_OK;
+}
+
+int reproject_device(bicos_engine* e, const ReprojectJob& j, hipStream_t st) {
+    const uint32_t pixels = (uint32_t)j.rows * (uint32_t)j.cols;
+    if (pixels == 0)  // nothing to launch: the counts are all zero
+        return j.points ? check_hip(hipMemsetAsync(j.counts, 0, 4 * sizeof(uint32_t), st),
+                                    "hipMemsetAsync(counts)")
+                        : (int)BICOS_OK;
+    bicos_hip::ReprojectArgs a{};
+    a.disp = j.disp;
+    a.cols = j.cols;
+    a.pixels = pixels;
+    a.flags = j.flags;
+    std::copy(j.Q, j.Q + 16, a.Q.q);
+    a.xyz_map = j.xyz_map;
+    a.points = j.points;
+    a.index = j.index;
+    a.capacity = (uint32_t)std::min<size_t>(j.capacity, pixels);
+    a.counts = j.counts;
+    const bool f32 = j.disp_type == BICOS_CV_32F;
+    if (!j.points)
+        return check_hip(bicos_hip::launch_reproject_map(a, f32, st), "reproject launch");
+    const uint32_t segments = bicos_hip::reproject_segments(pixels);
+    Lease ws(e, e->ws, e->ws_bytes, st);
+    auto carve = [&] {
+        a.seg_counts = ws.take<uint32_t>((size_t)segments * 4);
+        a.seg_offsets = ws.take<uint32_t>(segments);
+    };
+    carve();
+    if (int rc = ws.acquire()) return rc;
+    carve();
+    return check_hip(bicos_hip::launch_reproject_points(a, f32, st), "reproject launches");
 }
 
 // ------------------------------------------------------- process-wide engines

@@ -5,11 +5,11 @@
 // optional agree / subpixel. All launches are asynchronous on one HIP stream.
 //
 //   engine.cpp  errors, the workspace lease, engine resources, the plans, the search driver
-//               and match_device
-//   host.cpp    the banded host-buffer pipeline (HostPool, match_host)
+//               and match_device; reproject_device (disparity map -> 3-D points)
+//   host.cpp    the banded host-buffer pipeline (HostPool, match_host); reproject_host
 //   entries.cpp the bicos_* extern "C" entries (bicos_c.h) but the multi-GPU ones
 //   multi.cpp   bicos_match_host_multi, bicos_match_bands_device
-//   cxxapi.cpp  namespace BICOS (HipImage, match)
+//   cxxapi.cpp  namespace BICOS (HipImage, match, reproject)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -266,6 +266,29 @@ int match_host(bicos_engine* e, const void* const* p0, const size_t* steps0,
 
 // BICOS_E_ARG (with a message) for a window whose min exceeds its max; no HIP call
 int check_range(int min_disparity, int max_disparity);
+
+// One reprojection (bicos_c.h "reprojection"): the arguments of bicos_reproject_device /
+// bicos_reproject_host, the pointers all in device or all in host memory.
+struct ReprojectJob {
+    const void* disp;
+    int disp_type, rows, cols;
+    const double* Q;
+    int flags;
+    float* xyz_map;
+    float* points;
+    int32_t* index;
+    size_t capacity;
+    uint32_t* counts;
+};
+// BICOS_E_ARG (with a message) for what the entries refuse; no HIP call. needs_engine: points
+// without an engine are an error (the device entry; the host entry has a default engine).
+int check_reproject(const ReprojectJob& j, const bicos_engine* e, bool needs_engine);
+// The launches on `st` (validated arguments): the dense map alone, or count / scan / write
+// with the segment counts in the engine's workspace.
+int reproject_device(bicos_engine* e, const ReprojectJob& j, hipStream_t st);
+// Host buffers: the map uploaded into the engine's staging, the same launches on the engine's
+// own stream, the counts and then min(kept, capacity) points downloaded. Synchronous.
+int reproject_host(bicos_engine* e, const ReprojectJob& j);
 
 // Process-wide engine for `device` (created on first use).
 bicos_engine* default_engine(int device);

@@ -1,6 +1,7 @@
 // entries.cpp -- the bicos_* extern "C" entries of include/bicos_c.h over bicos_impl
 // (engine.hpp); the multi-GPU entries are multi.cpp, the reference's ctypes ABI capi.cpp.
 #include "engine.hpp"
+#include "reproject.hpp"
 
 #include <cmath>
 #include <vector>
@@ -331,6 +332,41 @@ int bicos_subpixel_device(const int16_t* raw, const void* stack0, const void* st
     return agree_common(true, raw, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth,
                         threshold, step, has_minvar, minvar_scaled, out, corrmap, stream);
 }
+
+int bicos_reproject_device(bicos_engine* e, const void* disparity, int disp_type, int rows,
+                           int cols, const double Q[16], int flags, float* xyz_map,
+                           float* points, int32_t* index, size_t capacity, uint32_t* counts,
+                           void* stream) {
+    const ReprojectJob job{disparity, disp_type, rows, cols, Q, flags, xyz_map, points, index,
+                           capacity, counts};
+    if (int rc0 = check_reproject(job, e, true)) return rc0;
+    return guarded([&]() -> int {
+        if (!points) return reproject_device(e, job, (hipStream_t)stream);  // no workspace
+        std::lock_guard<std::mutex> g(e->lock);
+        return reproject_device(e, job, (hipStream_t)stream);
+    });
+}
+
+int bicos_reproject_host(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                         const double Q[16], int flags, float* xyz_map, float* points,
+                         int32_t* index, size_t capacity, uint32_t counts[4]) {
+    const ReprojectJob job{disparity, disp_type, rows, cols, Q, flags, xyz_map, points, index,
+                           capacity, counts};
+    if (int rc0 = check_reproject(job, e, false)) return rc0;
+    return guarded([&]() -> int {
+        if (!e) {
+            int dev = 0;
+            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
+            if (rc) return rc;
+            e = default_engine(dev);
+            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        }
+        std::lock_guard<std::mutex> g(e->lock);
+        return reproject_host(e, job);
+    });
+}
+
+int bicos_reproject_segment(void) { return bicos_hip::REPROJECT_SEGMENT; }
 
 const char* bicos_build_info(void) {
     return "libbicos_amd: gfx950 HIP kernels (transform, mx search: FP4 MFMA Hamming products "

@@ -362,4 +362,51 @@ int match_host(bicos_engine* e, const void* const* p0, const size_t* steps0,
     return m.drain(rc);
 }
 
+int reproject_host(bicos_engine* e, const ReprojectJob& j) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    if (int rc0 = check_reproject(j, e, false)) return rc0;
+    const size_t pixels = (size_t)j.rows * j.cols;
+    if (pixels == 0) {
+        if (j.counts) std::fill(j.counts, j.counts + 4, 0u);
+        return BICOS_OK;
+    }
+    hipStream_t st = e->own_stream;
+    const size_t esz = j.disp_type == BICOS_CV_32F ? 4 : 2;
+    const size_t cap = std::min(j.capacity, pixels);
+    ReprojectJob d = j;  // the same job on staged device buffers
+    Lease stage(e, e->stage, e->stage_bytes, st);
+    auto carve = [&] {
+        d.disp = stage.take(pixels * esz);
+        d.xyz_map = j.xyz_map ? stage.take<float>(3 * pixels) : nullptr;
+        d.points = j.points ? stage.take<float>(3 * cap + 1) : nullptr;  // (non-null at cap 0)
+        d.index = j.index ? stage.take<int32_t>(cap + 1) : nullptr;
+        d.counts = j.points ? stage.take<uint32_t>(4) : nullptr;
+    };
+    carve();
+    int rc = stage.acquire();
+    if (rc) return rc;
+    carve();
+    d.capacity = cap;
+    rc = check_hip(hipMemcpyAsync((void*)d.disp, j.disp, pixels * esz, hipMemcpyHostToDevice, st),
+                   "disparity upload");
+    if (!rc) rc = reproject_device(e, d, st);
+    if (!rc && j.points) {
+        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 4 * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, st), "counts download");
+        if (!rc) rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+        const size_t got = rc ? 0 : std::min<size_t>(j.counts[0], cap);
+        if (!rc && got)
+            rc = check_hip(hipMemcpyAsync(j.points, d.points, got * 3 * sizeof(float),
+                                          hipMemcpyDeviceToHost, st), "points download");
+        if (!rc && got && j.index)
+            rc = check_hip(hipMemcpyAsync(j.index, d.index, got * sizeof(int32_t),
+                                          hipMemcpyDeviceToHost, st), "index download");
+    }
+    if (!rc && j.xyz_map)
+        rc = check_hip(hipMemcpyAsync(j.xyz_map, d.xyz_map, pixels * 3 * sizeof(float),
+                                      hipMemcpyDeviceToHost, st), "xyz map download");
+    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    return rc ? rc : rc2;
+}
+
 }  // namespace bicos_impl

@@ -237,6 +237,88 @@ class Engine:
         _lib.check(rc, "bicos_search_agree_device")
         return out, corrmap
 
+    # ------------------------------------------------------------ reprojection
+    def _reproject_args(self, disp: torch.Tensor, Q):
+        if not disp.is_cuda:
+            raise ValueError("device API needs CUDA/HIP tensors")
+        if disp.dim() != 2:
+            raise ValueError("disparity map must be [rows, cols]")
+        if disp.dtype not in (torch.int16, torch.float32):
+            raise ValueError("disparity map must be int16 or float32, got %s" % disp.dtype)
+        if not disp.is_contiguous():
+            raise ValueError("disparity map must be contiguous (dense rows)")
+        rows, cols = disp.shape
+        if rows * cols >= 2 ** 31:
+            raise ValueError("disparity map has more than 2^31 - 1 pixels")
+        typ = _lib.CV_32F if disp.dtype == torch.float32 else _lib.CV_16S
+        return rows, cols, typ, _lib.reproject_q(Q)
+
+    def reproject_map(self, disp: torch.Tensor, Q, *, allow_negative_z: bool = False,
+                      sentinel: bool = True, out: Optional[torch.Tensor] = None,
+                      stream=None) -> torch.Tensor:
+        """bicos_reproject_device, the dense map: an int16 or float32 disparity map [rows, cols]
+        through the 4x4 matrix Q to a float32 [rows, cols, 3] tensor -- the pixel's point
+        (X, Y, Z) where it is kept, three NaNs where it is invalid, not finite or (unless
+        allow_negative_z) behind the camera. sentinel: a float -32768.0 is invalid too, as
+        match() writes it for rejected pixels without a subpixel step. Asynchronous on `stream`
+        (default: torch's current stream)."""
+        rows, cols, typ, q = self._reproject_args(disp, Q)
+        if out is None:
+            out = torch.empty((rows, cols, 3), dtype=torch.float32, device=disp.device)
+        _check_out(out, "out", (rows, cols, 3), (torch.float32,), disp.device)
+        if rows * cols == 0:  # (an empty tensor has no pointer to hand over)
+            return out
+        rc = self._L.bicos_reproject_device(
+            self._h, disp.data_ptr(), typ, rows, cols, q,
+            _lib.reproject_flags(allow_negative_z, sentinel), out.data_ptr(), None, None, 0, None,
+            _stream(disp.device, stream))
+        _lib.check(rc, "bicos_reproject_device")
+        return out
+
+    def reproject_points(self, disp: torch.Tensor, Q, *, allow_negative_z: bool = False,
+                         sentinel: bool = True, with_index: bool = False,
+                         out: Optional[torch.Tensor] = None, stream=None):
+        """bicos_reproject_device, the point list: returns (points[:kept], index[:kept] or None,
+        stats) -- the kept points as float32 [kept, 3] in row-major pixel order, with
+        with_index each point's pixel row * cols + col (int32), and stats = dict(kept, invalid,
+        nonfinite, negative_z), which sum to rows * cols. The flags are reproject_map's.
+
+        `out`, a float32 [capacity, 3] tensor, receives the points; without it rows * cols
+        points are allocated. The launches are asynchronous on `stream`, but the call then
+        synchronises that stream ONCE to read the counts (the size of what it returns). A
+        RuntimeError says so if `out` was too small for the kept points (its first `capacity`
+        rows are then valid)."""
+        rows, cols, typ, q = self._reproject_args(disp, Q)
+        dev = disp.device
+        if out is None:
+            out = torch.empty((rows * cols, 3), dtype=torch.float32, device=dev)
+        if out.dim() != 2:
+            raise ValueError("out must be [capacity, 3]")
+        capacity = out.shape[0]
+        _check_out(out, "out", (capacity, 3), (torch.float32,), dev)
+        index = torch.empty((capacity,), dtype=torch.int32, device=dev) if with_index else None
+        if rows * cols == 0:  # (an empty tensor has no pointer to hand over)
+            return out[:0], (index[:0] if with_index else None), \
+                dict(kept=0, invalid=0, nonfinite=0, negative_z=0)
+        if capacity == 0:
+            raise ValueError("out must hold at least one point")
+        counts = torch.empty((4,), dtype=torch.int32, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        rc = self._L.bicos_reproject_device(
+            self._h, disp.data_ptr(), typ, rows, cols, q,
+            _lib.reproject_flags(allow_negative_z, sentinel), None, out.data_ptr(),
+            index.data_ptr() if index is not None else None, capacity, counts.data_ptr(),
+            s.cuda_stream)
+        _lib.check(rc, "bicos_reproject_device")
+        with torch.cuda.stream(s):
+            host = counts.cpu()  # the one synchronisation
+        kept, invalid, nonfinite, negative_z = (int(v) & 0xFFFFFFFF for v in host.tolist())
+        stats = dict(kept=kept, invalid=invalid, nonfinite=nonfinite, negative_z=negative_z)
+        if kept > capacity:
+            raise RuntimeError("reproject_points: out holds %d points, %d were kept"
+                               % (capacity, kept))
+        return out[:kept], (index[:kept] if index is not None else None), stats
+
     # ----------------------------------------------------------------- stages
     def transform(self, stack: torch.Tensor, mode: int = 0, words: Optional[int] = None,
                   out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:

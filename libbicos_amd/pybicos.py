@@ -236,6 +236,33 @@ def match(stack0, stack1, cfg=None, devices=None):
     return disparity, corrmap
 
 
+def reproject(disparity, Q, allow_negative_z=False, sentinel=True):
+    """An extension (the reference reprojects in its command-line tool only, src/cli.cpp:238):
+    a disparity map from match() -- int16 or float32, [rows, cols] -- through the rig's 4x4
+    matrix Q to the kept 3-D points, a float32 [kept, 3] array in row-major pixel order
+    (bicos_reproject_host, include/bicos_c.h "reprojection": on the GPU, bit for bit the
+    double-precision formula). Invalid pixels (int16 -32768, NaN, and with `sentinel` the
+    float -32768.0 of a match without subpixel step), points that are not finite and, unless
+    allow_negative_z, points with Z < 0 are left out."""
+    d = np.ascontiguousarray(disparity)
+    if d.ndim != 2:
+        raise ValueError("disparity map must be 2-D")
+    if d.dtype != np.int16 and d.dtype != np.float32:
+        raise ValueError(f"Unsupported disparity dtype: {d.dtype}")
+    rows, cols = d.shape
+    q = _lib.reproject_q(Q)
+    points = np.empty((max(rows * cols, 1), 3), np.float32)
+    counts = (ctypes.c_uint32 * 4)()
+    L = _lib.lib()
+    rc = L.bicos_reproject_host(None, d.ctypes.data, _get_cv_type(d.dtype), rows, cols, q,
+                                _lib.reproject_flags(allow_negative_z, sentinel), None,
+                                points.ctypes.data, None, rows * cols, counts)
+    if rc != 0:
+        raise RuntimeError("BICOS reprojection failed: " +
+                           L.bicos_last_error().decode(errors="replace"))
+    return points[:counts[0]].copy()
+
+
 def invalid_disparity(dtype):
     """reference pybicos/__init__.py:246-252."""
     L = _lib.lib()
