@@ -414,12 +414,166 @@ void bicos_oracle_agree_subpixel(const int16_t* disp, const void* stack0, const 
     parallel_rows(rows, nthreads, subpixel_rows, &c);
 }
 
+/* ------------------------------------------------ Precision::DOUBLE (agree) */
+
+/* include/impl/cuda/agree.cuh:35-65 (nxcorrd). The reference's DOUBLE exists only in its
+ * CUDA build; this is its operation order in IEEE double: sums by __dadd_rn (integers below
+ * 2^53: exact), __ddiv_rn by n, diffs, three __fma_rn chains in t order, the min-variance
+ * test on the double variances, covar / sqrt(var0 * var1). */
+static double nxcorr_vals_f64(const unsigned* pix0, const unsigned* pix1, int n, int has_minvar,
+                              double minvar) {
+    double mean0 = 0.0, mean1 = 0.0;
+    for (int i = 0; i < n; ++i) {
+        mean0 += (double)pix0[i]; /* agree.cuh:44 */
+        mean1 += (double)pix1[i]; /* agree.cuh:45 */
+    }
+    mean0 /= (double)n; /* agree.cuh:48 */
+    mean1 /= (double)n; /* agree.cuh:49 */
+
+    double covar = 0.0, var0 = 0.0, var1 = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const double diff0 = (double)pix0[i] - mean0, diff1 = (double)pix1[i] - mean1;
+        covar = fma(diff0, diff1, covar); /* agree.cuh:55 */
+        var0 = fma(diff0, diff0, var0);   /* agree.cuh:56 */
+        var1 = fma(diff1, diff1, var1);   /* agree.cuh:57 */
+    }
+    if (has_minvar && (var0 < minvar || var1 < minvar)) return -1.0; /* agree.cuh:60-62 */
+    return covar / sqrt(var0 * var1);                                /* agree.cuh:64 */
+}
+
+/* minvar_scaled is the float the match computes (cpu.cpp:127); the kernels take it as a
+ * double argument (agree.cuh:104), so it is widened, never recomputed in double. */
+double bicos_oracle_nxcorr_f64(const void* pix0, const void* pix1, int n, int depth,
+                               int has_minvar, float minvar_scaled) {
+    unsigned a[MAX_N], b[MAX_N];
+    for (int i = 0; i < n; ++i) {
+        a[i] = pix_at(pix0, depth, i);
+        b[i] = pix_at(pix1, depth, i);
+    }
+    return nxcorr_vals_f64(a, b, n, has_minvar, (double)minvar_scaled);
+}
+
+typedef struct {
+    int16_t* disp_rw;
+    const int16_t* disp_ro;
+    const void *s0, *s1;
+    int n, rows, cols, depth;
+    double thr;
+    float step;
+    int has_minvar;
+    double minvar;
+    float* out;
+    double* corrmap;
+} agree_ctx_f64;
+
+/* include/impl/cuda/agree.cuh:110-159 (agree_kernel, TPrecision = double), in the shape of
+ * include/impl/cpu/agree.hpp:53-93: int16 disparities invalidated in place, the corrmap
+ * written for every in-range valid pixel, 'nxc < (double)min_nxc' (agree.cuh:157: a NaN
+ * passes). */
+static void agree_rows_f64(void* p, int r0, int r1) {
+    agree_ctx_f64* c = (agree_ctx_f64*)p;
+    const size_t plane = (size_t)c->rows * c->cols;
+    unsigned a[MAX_N], b[MAX_N];
+    for (int r = r0; r < r1; ++r)
+        for (int col = 0; col < c->cols; ++col) {
+            int16_t* d = &c->disp_rw[(size_t)r * c->cols + col];
+            if (*d == INVALID_I16) continue; /* agree.cuh:129 */
+            const int idx1 = col - *d;
+            if (idx1 < 0 || c->cols <= idx1) { /* agree.cuh:134-137 */
+                *d = INVALID_I16;
+                continue;
+            }
+            load_px(c->s0, c->depth, plane, (size_t)r * c->cols + col, c->n, a);
+            load_px(c->s1, c->depth, plane, (size_t)r * c->cols + idx1, c->n, b);
+            const double nxc = nxcorr_vals_f64(a, b, c->n, c->has_minvar, c->minvar);
+            if (c->corrmap) c->corrmap[(size_t)r * c->cols + col] = nxc;
+            if (nxc < c->thr) *d = INVALID_I16;
+        }
+}
+
+void bicos_oracle_agree_f64(int16_t* disp, const void* stack0, const void* stack1, int n, int rows,
+                            int cols, int depth, float threshold, int has_minvar,
+                            float minvar_scaled, double* corrmap, int nthreads) {
+    agree_ctx_f64 c = {disp, NULL, stack0, stack1, n, rows, cols, depth, (double)threshold, 0.f,
+                       has_minvar, (double)minvar_scaled, NULL, corrmap};
+    parallel_rows(rows, nthreads, agree_rows_f64, &c);
+}
+
+/* include/impl/cuda/agree.cuh:161-259 (agree_subpixel_kernel, TPrecision = double), in the
+ * shape of include/impl/cpu/agree.hpp:95-191: the float quadratic, 'x += step', the
+ * round-to-even narrowing and the output typing are the CPU path's, exactly as in
+ * subpixel_rows above; the correlation, best_nxc and the first-strict-maximum test
+ * (agree.cuh:242) are double, best_x stays float (agree.cuh:230). */
+static void subpixel_rows_f64(void* p, int r0, int r1) {
+    agree_ctx_f64* c = (agree_ctx_f64*)p;
+    const size_t plane = (size_t)c->rows * c->cols;
+    const int n = c->n;
+    unsigned left[MAX_N], y0[MAX_N], y1[MAX_N], y2[MAX_N], interp[MAX_N];
+    float A[MAX_N], B[MAX_N], C[MAX_N];
+    for (int r = r0; r < r1; ++r)
+        for (int col = 0; col < c->cols; ++col) {
+            const size_t o = (size_t)r * c->cols + col;
+            c->out[o] = NAN;
+            const int16_t d = c->disp_ro[o];
+            if (d == INVALID_I16) continue; /* agree.cuh:182 */
+            const int col1 = col - d;
+            if (col1 < 0 || c->cols <= col1) continue; /* agree.cuh:187 */
+
+            load_px(c->s0, c->depth, plane, o, n, left);
+            if (col1 == 0 || col1 == c->cols - 1) { /* agree.cuh:201-213 */
+                load_px(c->s1, c->depth, plane, (size_t)r * c->cols + col1, n, y1);
+                const double nxc = nxcorr_vals_f64(left, y1, n, c->has_minvar, c->minvar);
+                if (c->corrmap) c->corrmap[o] = nxc;
+                if (nxc < c->thr) continue;
+                c->out[o] = (float)d;
+                continue;
+            }
+            load_px(c->s1, c->depth, plane, (size_t)r * c->cols + col1 - 1, n, y0);
+            load_px(c->s1, c->depth, plane, (size_t)r * c->cols + col1, n, y1);
+            load_px(c->s1, c->depth, plane, (size_t)r * c->cols + col1 + 1, n, y2);
+            for (int t = 0; t < n; ++t) { /* agree.cuh:220-228 as agree.hpp:159-161 */
+                A[t] = 0.5f * (((float)y0[t] - 2.0f * (float)y1[t]) + (float)y2[t]);
+                B[t] = 0.5f * (float)(-(int)y0[t] + (int)y2[t]);
+                C[t] = (float)y1[t];
+            }
+            float best_x = 0.f;
+            double best_nxc = -1.0; /* agree.cuh:231 */
+            for (float x = -1.f; x <= 1.f; x += c->step) {
+                for (int t = 0; t < n; ++t) {
+                    const float ax = A[t] * x;
+                    const float axx = ax * x;
+                    const float bx = B[t] * x;
+                    interp[t] = narrow_input((axx + bx) + C[t], c->depth);
+                }
+                const double nxc = nxcorr_vals_f64(left, interp, n, c->has_minvar, c->minvar);
+                if (best_nxc < nxc) { /* agree.cuh:242 */
+                    best_x = x;
+                    best_nxc = nxc;
+                }
+            }
+            if (c->corrmap) c->corrmap[o] = best_nxc;
+            if (best_nxc < c->thr) continue; /* agree.cuh:251 */
+            c->out[o] = (float)d - best_x;   /* agree.cuh:255 */
+        }
+}
+
+void bicos_oracle_agree_subpixel_f64(const int16_t* disp, const void* stack0, const void* stack1,
+                                     int n, int rows, int cols, int depth, float threshold,
+                                     float step, int has_minvar, float minvar_scaled, float* out,
+                                     double* corrmap, int nthreads) {
+    agree_ctx_f64 c = {NULL, disp, stack0, stack1, n, rows, cols, depth, (double)threshold, step,
+                       has_minvar, (double)minvar_scaled, out, corrmap};
+    parallel_rows(rows, nthreads, subpixel_rows_f64, &c);
+}
+
 /* ---------------------------------------------------------------- match */
 
 /* src/impl/cpu.cpp:100-159 (match) + :35-98 (match_impl) */
-int bicos_oracle_match(const void* stack0, const void* stack1, int n, int rows, int cols,
-                       int depth, const bicos_oracle_config* cfg, void* disp_out, float* corrmap,
-                       int nthreads) {
+static int match_impl(const void* stack0, const void* stack1, int n, int rows, int cols,
+                      int depth, const bicos_oracle_config* cfg, void* disp_out, void* corrmap_v,
+                      int nthreads, int dbl) {
+    float* corrmap = dbl ? NULL : (float*)corrmap_v;
+    double* corrmap64 = dbl ? (double*)corrmap_v : NULL;
     if (n < 2) return BICOS_ORACLE_ERR_N;
     if (depth != 1 && depth != 2) return BICOS_ORACLE_ERR_DEPTH;
     if (n > MAX_N) return BICOS_ORACLE_ERR_BITS;
@@ -453,7 +607,20 @@ int bicos_oracle_match(const void* stack0, const void* stack1, int n, int rows, 
         const float mv = cfg->has_minvar ? cfg->min_variance * (float)n : 0.f;
         if (corrmap)
             for (size_t i = 0; i < px; ++i) corrmap[i] = NAN; /* cpu.cpp:78-81 */
-        if (cfg->has_step) {
+        if (corrmap64)
+            for (size_t i = 0; i < px; ++i) corrmap64[i] = NAN;
+        if (dbl && cfg->has_step) {
+            bicos_oracle_agree_subpixel_f64(raw, stack0, stack1, n, rows, cols, depth,
+                                            cfg->nxcorr_threshold, cfg->subpixel_step,
+                                            cfg->has_minvar, mv, (float*)disp_out, corrmap64,
+                                            nthreads);
+        } else if (dbl) {
+            bicos_oracle_agree_f64(raw, stack0, stack1, n, rows, cols, depth,
+                                   cfg->nxcorr_threshold, cfg->has_minvar, mv, corrmap64,
+                                   nthreads);
+            float* f = (float*)disp_out;
+            for (size_t i = 0; i < px; ++i) f[i] = (float)raw[i];
+        } else if (cfg->has_step) {
             bicos_oracle_agree_subpixel(raw, stack0, stack1, n, rows, cols, depth,
                                         cfg->nxcorr_threshold, cfg->subpixel_step,
                                         cfg->has_minvar, mv, (float*)disp_out, corrmap, nthreads);
@@ -467,4 +634,19 @@ int bicos_oracle_match(const void* stack0, const void* stack1, int n, int rows, 
     }
     free(raw);
     return kind;
+}
+
+int bicos_oracle_match(const void* stack0, const void* stack1, int n, int rows, int cols,
+                       int depth, const bicos_oracle_config* cfg, void* disp_out, float* corrmap,
+                       int nthreads) {
+    return match_impl(stack0, stack1, n, rows, cols, depth, cfg, disp_out, corrmap, nthreads, 0);
+}
+
+/* The same match with Precision::DOUBLE (src/impl/cuda.cu's dispatch on cfg.precision): the
+ * transform and the search are untouched, the agree stage is the _f64 one, the corrmap is
+ * double. */
+int bicos_oracle_match_f64(const void* stack0, const void* stack1, int n, int rows, int cols,
+                           int depth, const bicos_oracle_config* cfg, void* disp_out,
+                           double* corrmap, int nthreads) {
+    return match_impl(stack0, stack1, n, rows, cols, depth, cfg, disp_out, corrmap, nthreads, 1);
 }

@@ -14,8 +14,10 @@
  * committed, and tests/test_reference_parity.py demands byte-identical results
  * from every function below and the reference's: whole matches, each stage, the
  * error kinds, and every committed fixture. Not covered, for want of a reference
- * CPU counterpart: Precision::DOUBLE and the disparity range, which this file
- * does not restate either. The restatement is also cross-checked against an
+ * CPU counterpart: the disparity range, which this file does not restate, and
+ * Precision::DOUBLE, which it states from the CUDA build's agree.cuh (the _f64
+ * functions at the end; pinned to exact rational arithmetic instead of a
+ * reference binary). The restatement is also cross-checked against an
  * independent numpy restatement (oracle/ref_numpy.py), hand-derived known-answer
  * cases and the reference behaviours recorded in SURVEY.md Appendix A
  * (tests/test_oracle.py).
@@ -88,6 +90,32 @@ float bicos_oracle_nxcorr(const void* pix0, const void* pix1, int n, int depth, 
 int bicos_oracle_match(const void* stack0, const void* stack1, int n, int rows, int cols,
                        int depth, const bicos_oracle_config* cfg, void* disp_out,
                        float* corrmap, int nthreads);
+
+/* Precision::DOUBLE. The reference has it only in its CUDA build (include/impl/cuda/
+ * agree.cuh:35-65 nxcorrd, :110-259 the two kernels with TPrecision = double), so no
+ * reference binary stands behind these: they state agree.cuh's operation order in IEEE
+ * double (fma() from <math.h>, '/' and sqrt()), with the float quadratic, the narrowing and
+ * the output typing of the CPU path above, and are held bit for bit to an exact-rational
+ * restatement (oracle/ref_exact.py, tests/test_oracle_f64.py). minvar_scaled and threshold
+ * arrive as the floats the match computes and are widened (src/impl/cuda.cu:455). */
+double bicos_oracle_nxcorr_f64(const void* pix0, const void* pix1, int n, int depth,
+                               int has_minvar, float minvar_scaled);
+
+/* corrmap: rows*cols doubles, NaN-initialised by the caller. */
+void bicos_oracle_agree_f64(int16_t* disp, const void* stack0, const void* stack1, int n,
+                            int rows, int cols, int depth, float threshold, int has_minvar,
+                            float minvar_scaled, double* corrmap, int nthreads);
+
+void bicos_oracle_agree_subpixel_f64(const int16_t* disp, const void* stack0, const void* stack1,
+                                     int n, int rows, int cols, int depth, float threshold,
+                                     float step, int has_minvar, float minvar_scaled, float* out,
+                                     double* corrmap, int nthreads);
+
+/* bicos_oracle_match with Precision::DOUBLE: same transform and search, the _f64 agree
+ * stage, a double corrmap (may be NULL). */
+int bicos_oracle_match_f64(const void* stack0, const void* stack1, int n, int rows, int cols,
+                           int depth, const bicos_oracle_config* cfg, void* disp_out,
+                           double* corrmap, int nthreads);
 
 #ifdef __cplusplus
 }

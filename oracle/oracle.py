@@ -89,6 +89,14 @@ def lib(variant: str = "") -> ctypes.CDLL:
     L.bicos_oracle_nxcorr.restype = F
     L.bicos_oracle_match.argtypes = [P, P, I, I, I, I, ctypes.POINTER(_Cfg), P, P, I]
     L.bicos_oracle_match.restype = I
+    L.bicos_oracle_nxcorr_f64.argtypes = L.bicos_oracle_nxcorr.argtypes
+    L.bicos_oracle_nxcorr_f64.restype = ctypes.c_double
+    L.bicos_oracle_agree_f64.argtypes = L.bicos_oracle_agree.argtypes
+    L.bicos_oracle_agree_f64.restype = None
+    L.bicos_oracle_agree_subpixel_f64.argtypes = L.bicos_oracle_agree_subpixel.argtypes
+    L.bicos_oracle_agree_subpixel_f64.restype = None
+    L.bicos_oracle_match_f64.argtypes = L.bicos_oracle_match.argtypes
+    L.bicos_oracle_match_f64.restype = I
     _LIBS[name] = L
     return L
 
@@ -170,6 +178,45 @@ def nxcorr(pix0, pix1, minvar_scaled: Optional[float] = None) -> float:
                                      int(minvar_scaled is not None), float(minvar_scaled or 0.0))
 
 
+# ---- Precision::DOUBLE (reference include/impl/cuda/agree.cuh:35-65, :110-259): the float
+# functions' conventions, a float64 corrmap; `variant` picks the oracle build.
+def nxcorr_f64(pix0, pix1, minvar_scaled: Optional[float] = None, variant: str = "") -> float:
+    a = np.ascontiguousarray(pix0)
+    b = np.ascontiguousarray(pix1, a.dtype)
+    return lib(variant).bicos_oracle_nxcorr_f64(_ptr(a), _ptr(b), a.size, a.itemsize,
+                                                int(minvar_scaled is not None),
+                                                float(minvar_scaled or 0.0))
+
+
+def agree_f64(disp: np.ndarray, stack0, stack1, threshold: float,
+              minvar_scaled: Optional[float], nthreads=None, variant: str = ""
+              ) -> Tuple[np.ndarray, np.ndarray]:
+    s0, s1 = _stack(stack0), _stack(stack1)
+    n, h, w = s0.shape
+    d = np.array(disp, np.int16, copy=True, order="C")
+    corr = np.full((h, w), np.nan, np.float64)
+    lib(variant).bicos_oracle_agree_f64(_ptr(d), _ptr(s0), _ptr(s1), n, h, w, s0.itemsize,
+                                        threshold, int(minvar_scaled is not None),
+                                        float(minvar_scaled or 0.0), _ptr(corr),
+                                        _threads(nthreads))
+    return d, corr
+
+
+def agree_subpixel_f64(disp: np.ndarray, stack0, stack1, threshold: float, step: float,
+                       minvar_scaled: Optional[float], nthreads=None, variant: str = ""
+                       ) -> Tuple[np.ndarray, np.ndarray]:
+    s0, s1 = _stack(stack0), _stack(stack1)
+    n, h, w = s0.shape
+    d = np.ascontiguousarray(disp, np.int16)
+    out = np.empty((h, w), np.float32)
+    corr = np.full((h, w), np.nan, np.float64)
+    lib(variant).bicos_oracle_agree_subpixel_f64(
+        _ptr(d), _ptr(s0), _ptr(s1), n, h, w, s0.itemsize, threshold, step,
+        int(minvar_scaled is not None), float(minvar_scaled or 0.0), _ptr(out), _ptr(corr),
+        _threads(nthreads))
+    return out, corr
+
+
 class OracleError(RuntimeError):
     pass
 
@@ -189,6 +236,27 @@ def match(stack0, stack1, cfg: Optional[OracleConfig] = None, nthreads=None,
     kind = lib(variant).bicos_oracle_match(_ptr(s0), _ptr(s1), n, h, w, s0.itemsize,
                                            ctypes.byref(c), _ptr(buf), _ptr(corr),
                                            _threads(nthreads))
+    if kind < 0:
+        raise OracleError({-1: "need at least two images", -2: "bad input depths",
+                           -3: "input stacks too large"}[kind])
+    if kind == 0:
+        return buf.view(np.int16).reshape(-1)[: h * w].reshape(h, w).copy(), None
+    return buf, corr
+
+
+def match_f64(stack0, stack1, cfg: Optional[OracleConfig] = None, nthreads=None,
+              variant: str = "") -> Tuple[np.ndarray, Optional[np.ndarray]]:
+    """match() with Precision::DOUBLE: the same transform and search, the float64 agree
+    stage (agree_f64 / agree_subpixel_f64), a float64 corrmap."""
+    cfg = cfg or OracleConfig()
+    s0, s1 = _stack(stack0), _stack(stack1)
+    n, h, w = s0.shape
+    buf = np.empty((h, w), np.float32)
+    corr = np.empty((h, w), np.float64)
+    c = cfg.to_c()
+    kind = lib(variant).bicos_oracle_match_f64(_ptr(s0), _ptr(s1), n, h, w, s0.itemsize,
+                                               ctypes.byref(c), _ptr(buf), _ptr(corr),
+                                               _threads(nthreads))
     if kind < 0:
         raise OracleError({-1: "need at least two images", -2: "bad input depths",
                            -3: "input stacks too large"}[kind])

@@ -181,6 +181,26 @@ def _narrow(v: np.ndarray, dtype) -> np.ndarray:
     return (i & (0xFF if dtype == np.uint8 else 0xFFFF)).astype(np.int64)
 
 
+def quadratic(p0: np.ndarray, p1: np.ndarray, p2: np.ndarray):
+    """The float32 coefficients of the parabola through the right samples at col1 - 1, col1,
+    col1 + 1 (agree.hpp:159-161): integer arrays of one shape -> (A, B, C)."""
+    y0 = p0.astype(np.float32)
+    y1 = p1.astype(np.float32)
+    y2 = p2.astype(np.float32)
+    A = (f32(0.5) * ((y0 - f32(2.0) * y1).astype(np.float32) + y2)).astype(np.float32)
+    B = (f32(0.5) * (-p0.astype(np.int64) + p2.astype(np.int64)).astype(np.float32)
+         ).astype(np.float32)
+    return A, B, y1
+
+
+def interpolate(A, B, C, x, dtype) -> np.ndarray:
+    """(TInput)roundevenf(A x x + B x + C), every float op rounded (agree.hpp:170)."""
+    ax = (A * x).astype(np.float32)
+    v = (((ax * x).astype(np.float32) + (B * x).astype(np.float32)).astype(np.float32)
+         + C).astype(np.float32)
+    return _narrow(v, dtype)
+
+
 def agree_subpixel(disp, s0, s1, thr: float, step: float, minvar):
     n, H, W = s0.shape
     out = np.full((H, W), np.nan, np.float32)
@@ -203,20 +223,11 @@ def agree_subpixel(disp, s0, s1, thr: float, step: float, minvar):
     ir, ic, i1 = rr[~edge], cc[~edge], col1[~edge]
     if ir.size:
         left = s0[:, ir, ic]
-        y0 = s1[:, ir, i1 - 1].astype(np.float32)
-        y1 = s1[:, ir, i1].astype(np.float32)
-        y2 = s1[:, ir, i1 + 1].astype(np.float32)
-        A = (f32(0.5) * ((y0 - f32(2.0) * y1).astype(np.float32) + y2)).astype(np.float32)
-        B = (f32(0.5) * (-s1[:, ir, i1 - 1].astype(np.int64)
-                         + s1[:, ir, i1 + 1].astype(np.int64)).astype(np.float32)).astype(np.float32)
-        C = y1
+        A, B, C = quadratic(s1[:, ir, i1 - 1], s1[:, ir, i1], s1[:, ir, i1 + 1])
         best_x = np.zeros(ir.size, np.float32)
         best = np.full(ir.size, -1.0, np.float32)
         for x in x_steps(step):
-            ax = (A * x).astype(np.float32)
-            v = (((ax * x).astype(np.float32) + (B * x).astype(np.float32)).astype(np.float32)
-                 + C).astype(np.float32)
-            interp = _narrow(v, s0.dtype)
+            interp = interpolate(A, B, C, x, s0.dtype)
             nxc = nxcorr(left, interp, minvar)
             win = best < nxc
             best_x = np.where(win, x, best_x)

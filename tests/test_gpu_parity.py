@@ -2,8 +2,11 @@
 
 Bar (north star): integer disparities bit-exact; nxcorr / subpixel floats within
 1e-4 -- the kernels are written to be bit-exact there too, and these tests
-demand exact equality (the tolerance is only used for Precision::DOUBLE, which
-has no CPU oracle: |corr - float64 numpy| <= 1e-12).
+demand exact equality. Precision::DOUBLE is held to the float64 oracle
+(oracle/bicos_oracle.c *_f64: agree.cuh's operation order, itself pinned to exact
+rational arithmetic by tests/test_oracle_f64.py) byte for byte as well, here and in
+tests/test_double_gpu.py; the 1e-12 comparisons with a float64 numpy formula that
+remain below are a third, differently rounded witness, not the bar.
 """
 import contextlib
 import numpy as np
@@ -12,6 +15,7 @@ import pytest
 from libbicos_amd import _lib
 from libbicos_amd.synthetic import random_stack, stereo_stack
 from oracle import ref_numpy as N
+from tests.double_cases import same as same_bits  # bit equality, NaN payloads apart
 
 pytestmark = pytest.mark.gpu
 
@@ -687,8 +691,9 @@ def test_pybicos_errors(gpu):
 
 
 def test_double_precision(gpu, oracle):
-    """Precision::DOUBLE (CUDA-build feature, agree.cuh:35-65): no CPU oracle; compare
-    the float64 correlation with a float64 numpy restatement (no fma there: 1e-12)."""
+    """Precision::DOUBLE (CUDA-build feature, agree.cuh:35-65): the disparity and the
+    float64 correlation byte for byte against the float64 oracle, and the correlation
+    against a float64 numpy restatement (no fma there: 1e-12)."""
     L, R = stereo_stack(33, 8, 512)
     d32, c32 = gpu_match(gpu, L, R, nxcorr_threshold=0.5)
     d64, c64 = gpu_match(gpu, L, R, nxcorr_threshold=0.5, precision=1)
@@ -707,6 +712,9 @@ def test_double_precision(gpu, oracle):
     fin = np.isfinite(ref)
     assert np.abs(got[fin] - ref[fin]).max() < 1e-12
     assert np.abs(c32[rr, cc][fin] - ref[fin]).max() < FLOAT_TOL
+    od, oc = oracle.match_f64(L, R, oracle.OracleConfig(nxcorr_threshold=0.5))
+    same_bits(d64, od)
+    same_bits(c64, oc)
 
 
 def _subpixel_f64(L, R, raw, thr, step, minvar):
@@ -782,6 +790,9 @@ def test_double_subpixel_exact_depths(gpu, oracle, n, step, minvar):
     assert (np.isfinite(got_c) == fin).all()
     assert np.abs(got_c[fin] - ref_c[fin]).max() < 1e-12
     same(host(out), ref_d)
+    ora_d, ora_c = oracle.agree_subpixel_f64(raw, L, R, 0.5, step, mv)
+    same_bits(host(out), ora_d)
+    same_bits(got_c, ora_c)
 
 
 def test_deterministic(gpu):

@@ -239,8 +239,9 @@ def test_match_plan_is_unchanged_by_the_feature(gpu):
 
 
 def test_match_double_precision_with_a_range(gpu):
-    """Precision::DOUBLE: no CPU oracle -- the float64 restatement of the subpixel refine that
-    tests/test_gpu_parity.py test_double_subpixel_exact_depths uses, and its 1e-12 bound"""
+    """Precision::DOUBLE: byte equality with the float64 oracle (agree_subpixel_f64 on the
+    restated ranged search), and, as a differently rounded witness, the numpy float64
+    restatement of tests/test_gpu_parity.py test_double_subpixel_exact_depths within 1e-12"""
     from libbicos_amd.device import MatchConfig
     from oracle import oracle as O
     from tests.test_gpu_parity import _subpixel_f64
@@ -257,6 +258,10 @@ def test_match_double_precision_with_a_range(gpu):
     assert (np.isfinite(got_c) == fin).all()
     assert np.abs(got_c[fin] - ref_c[fin]).max() < 1e-12
     same(host(out), ref_d, "disparity")
+    ora_d, ora_c = O.agree_subpixel_f64(raw, L, R, 0.5, step, None)
+    from tests.double_cases import same as same_bits
+    same_bits(host(out), ora_d)
+    same_bits(got_c, ora_c)
 
 
 # -------------------------------------------------------------------- host path
