@@ -356,6 +356,56 @@ int bicos_reproject_host(bicos_engine* e, const void* disparity, int disp_type, 
 /* Pixels per segment of the point list's count / scan / write launches (tests). */
 int bicos_reproject_segment(void);
 
+/* -------------------------------------------------------- speckle filter */
+/* Removes the small islands of disparities that disagree with their surroundings from a dense
+ * rows x cols map (BICOS_CV_16S or BICOS_CV_32F), on the GPU. The reference has no such step.
+ *     valid pixel  an int16 that is not -32768; a float that is not NaN and, with
+ *                  BICOS_SPECKLE_F32_SENTINEL, not -32768.0f either (the notion of
+ *                  BICOS_REPROJECT_F32_SENTINEL). Infinities are valid numbers.
+ *     link         two 4-neighbours p, q are linked iff both are valid and
+ *                      fabsf((float)d_p - (float)d_q) <= max_diff
+ *                  with one IEEE float subtraction: exact for int16, symmetric, and false when
+ *                  the difference is NaN (inf - inf).
+ *     component    a connected component of the valid pixels under links. Its label is the
+ *                  smallest linear index row*cols + col in it: canonical, independent of any
+ *                  execution order.
+ *     removal      a component with size <= max_size is removed: its pixels become int16
+ *                  -32768, float NaN, or float -32768.0f under the sentinel flag (a sentinel
+ *                  map stays one). Every other pixel, invalid ones included, is copied bit for
+ *                  bit. max_size = 0 removes nothing.
+ * max_diff must be >= 0 and not NaN; +inf is legal. max_size must not be negative.
+ * Outputs:
+ *     out     same type and shape as the map; may be the map itself (in place). Any other
+ *             overlap of the two is an argument error.
+ *     labels  optional, int32 [rows][cols]: the component label of every pixel that was valid
+ *             on input, removed ones included, and -1 where the pixel was invalid.
+ *     counts  optional, uint32[4]: {kept, removed, invalid, removed_components}; the first
+ *             three sum to rows*cols.
+ * The results are exact and deterministic: integers and copied bits.
+ * rows*cols must fit int32. rows == 0 or cols == 0 is legal (counts all zero, nothing launched).
+ * Argument errors (a type other than 16S / 32F, a negative size, too many pixels, unknown flag
+ * bits, a negative or NaN max_diff, a negative max_size, a NULL map or out on a non-empty map,
+ * a partial overlap of map and out, a NULL engine on the device entry) are BICOS_E_ARG before
+ * any HIP call.
+ * For int16 maps and an integral max_diff this is cv::filterSpeckles(img, newVal = -32768,
+ * maxSpeckleSize = max_size, maxDiff = max_diff) on a map whose invalid pixels already hold
+ * newVal -- a statement from reading that function's definition (regions of pixels != newVal
+ * grown over 4-neighbours with |difference| <= maxDiff, filled with newVal when their pixel
+ * count is <= maxSpeckleSize), not from a test against it. */
+#define BICOS_SPECKLE_F32_SENTINEL 1
+/* device: asynchronous on `stream`. The label and size arrays live in e's workspace (labels,
+ * when given, is used directly as the label array). */
+int bicos_speckle_device(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                         int max_size, float max_diff, int flags, void* out, int32_t* labels,
+                         uint32_t* counts, void* stream);
+/* host buffers, synchronous, e NULL = default engine: uploads the map, runs the same launches,
+ * downloads the map, and the counts and the labels where asked. */
+int bicos_speckle_host(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                       int max_size, float max_diff, int flags, void* out, int32_t* labels,
+                       uint32_t counts[4]);
+/* The tile (rows, cols) one workgroup labels in LDS (tests). Returns BICOS_OK. */
+int bicos_speckle_tile(int* rows, int* cols);
+
 /* Build identification (arch, flags) for reports. */
 const char* bicos_build_info(void);
 

@@ -62,6 +62,7 @@ EXPORTS = (
     "bicos_match_plan", "bicos_search_agree_device", "bicos_search_packed",
     "bicos_match_device_range", "bicos_match_host_range", "bicos_search_device_range",
     "bicos_reproject_device", "bicos_reproject_host", "bicos_reproject_segment",
+    "bicos_speckle_device", "bicos_speckle_host", "bicos_speckle_tile",
 )
 
 # bicos_match_plan bits (include/bicos_c.h)
@@ -76,6 +77,9 @@ PLAN_CONSISTENCY_ONE_PASS = 64
 # bicos_reproject_* flags (include/bicos_c.h)
 REPROJECT_ALLOW_NEGATIVE_Z = 1
 REPROJECT_F32_SENTINEL = 2
+
+# bicos_speckle_* flag (include/bicos_c.h)
+SPECKLE_F32_SENTINEL = 1
 
 
 def build(verbose: bool = False, jobs: int = 4) -> str:
@@ -181,6 +185,12 @@ def lib() -> ctypes.CDLL:
     L.bicos_reproject_host.restype = I
     L.bicos_reproject_segment.argtypes = []
     L.bicos_reproject_segment.restype = I
+    L.bicos_speckle_device.argtypes = [P, P, I, I, I, I, F, I, P, P, P, P]
+    L.bicos_speckle_device.restype = I
+    L.bicos_speckle_host.argtypes = [P, P, I, I, I, I, F, I, P, P, P]
+    L.bicos_speckle_host.restype = I
+    L.bicos_speckle_tile.argtypes = [PI, PI]
+    L.bicos_speckle_tile.restype = I
     L.bicos_build_info.restype = ctypes.c_char_p
     L.bicos_build_info.argtypes = []
     _lib = L
@@ -220,6 +230,24 @@ def reproject_q(Q):
 def reproject_flags(allow_negative_z: bool, sentinel: bool) -> int:
     return (REPROJECT_ALLOW_NEGATIVE_Z if allow_negative_z else 0) | \
         (REPROJECT_F32_SENTINEL if sentinel else 0)
+
+
+def speckle_params(max_size, max_diff):
+    """(int max_size, float max_diff) as the bicos_speckle_* entries take them (ValueError for
+    what they would refuse: a negative max_size, a negative or NaN max_diff)."""
+    size, diff = int(max_size), float(max_diff)
+    if size != max_size or size < 0 or size > 2 ** 31 - 1:
+        raise ValueError("max_size must be an integer in [0, 2^31 - 1], got %r" % (max_size,))
+    if not diff >= 0:
+        raise ValueError("max_diff must be >= 0 and not NaN, got %r" % (max_diff,))
+    return size, diff
+
+
+def speckle_tile():
+    """(rows, cols) of the tile one workgroup labels (bicos_speckle_tile)."""
+    r, c = ctypes.c_int(0), ctypes.c_int(0)
+    lib().bicos_speckle_tile(ctypes.byref(r), ctypes.byref(c))
+    return r.value, c.value
 
 
 def check(rc: int, what: str = "bicos") -> None:

@@ -50,6 +50,11 @@ const char* USAGE =
     "  -q, --qmatrix FILE      OpenCV FileStorage (YAML/XML) with a 4x4 matrix \"Q\":\n"
     "                          also write a point cloud (.xyz)\n"
     "      --allow-negative-z  keep points with negative Z in the point cloud\n"
+    "      --speckle-size N    speckle filter: invalidate every 4-connected region of similar\n"
+    "                          disparity with at most N pixels, before the disparity is\n"
+    "                          saved and reprojected (default: off)\n"
+    "      --speckle-diff F    largest disparity difference of two neighbours in one region\n"
+    "                          (1; only with --speckle-size)\n"
     "  -m, --lr-maxdiff N      maximum left-right disparity difference (Consistency\n"
     "                          variant; disables duplicate filtering)\n"
     "      --double            double precision correlation\n"
@@ -72,7 +77,7 @@ Args parse(int argc, char** argv) {
         {"threshold", true}, {"variance", true}, {"step", true}, {"out", true},
         {"stacksize", true}, {"qmatrix", true}, {"lr-maxdiff", true}, {"help", false},
         {"allow-negative-z", false}, {"double", false}, {"limited", false},
-        {"corrmap", false}, {"no-dupes", false}};
+        {"corrmap", false}, {"no-dupes", false}, {"speckle-size", true}, {"speckle-diff", true}};
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i];
@@ -194,6 +199,22 @@ int run(int argc, char** argv) {
     const auto tick = std::chrono::high_resolution_clock::now();
     BICOS::match(s0, s1, disp, c, need_corrmap ? &corrmap : nullptr);
     std::cout << "Latency:\t" << ms_since(tick) << "ms" << std::endl;
+
+    if (args.has("speckle-size")) {
+        // on the GPU, in place; the flags are those of the reprojection call below (a float
+        // -32768.0 is a number like any other); the corrmap is left alone
+        const unsigned max_size = as_uint(args, "speckle-size");
+        if (max_size > (unsigned)INT32_MAX) throw std::invalid_argument("--speckle-size: too large");
+        const float max_diff = args.has("speckle-diff") ? as_float(args, "speckle-diff") : 1.0f;
+        uint32_t counts[4] = {0, 0, 0, 0};  // kept, removed, invalid, removed_components
+        if (bicos_speckle_host(nullptr, disp.data(), disp.type(), disp.rows(), disp.cols(),
+                               (int)max_size, max_diff, 0, disp.data(), nullptr, counts) != BICOS_OK)
+            throw std::runtime_error(std::string("speckle filter failed: ") + bicos_last_error());
+        std::cout << "Speckle filter:\tremoved " << counts[1] << " pixels in " << counts[3]
+                  << " regions" << std::endl;
+    } else if (args.has("speckle-diff")) {
+        std::cerr << "'speckle-diff' has no effect without 'speckle-size'.\n";
+    }
 
     save_image(disp, outfile, bicos_cli::Colormap::Turbo);
     if (need_corrmap)

@@ -3,6 +3,7 @@
 //   BICOS::match   <- reference BICOS::match (src/lib.cpp:31-49) and the backend entry
 //                     impl::cpu::match (src/impl/cpu.cpp:100-159)
 //   BICOS::reproject  (bicos/reproject.hpp; no reference counterpart in its library)
+//   BICOS::filter_speckles  (bicos/speckle.hpp; no reference counterpart)
 #include "engine.hpp"
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include "../../include/bicos/match.hpp"
 #include "../../include/bicos/hip.hpp"
 #include "../../include/bicos/reproject.hpp"
+#include "../../include/bicos/speckle.hpp"
 
 using bicos_impl::check_hip;
 
@@ -297,6 +299,63 @@ ReprojectStats reproject(const Image& disparity, const Matx44d& Q, std::vector<f
     points.resize(3 * (size_t)counts[0]);
     if (index) index->resize(counts[0]);
     return ReprojectStats{counts[0], counts[1], counts[2], counts[3]};
+}
+
+// ---------------------------------------------------------- BICOS::filter_speckles
+// over the C entries (entries.cpp), which validate, lock the engine and launch
+
+namespace {
+
+void check_speckle_map(const Image& disparity) {
+    if (disparity.type() != S16 && disparity.type() != F32)
+        throw Exception("filter_speckles: the disparity map must be S16 or F32");
+    if (disparity.step() != (size_t)disparity.cols() * disparity.elemSize() && disparity.rows() > 1)
+        throw Exception("filter_speckles: the disparity map must be dense");
+}
+
+}  // namespace
+
+void filter_speckles(const Image& disparity, Image& out, int max_size, float max_diff, int flags,
+                     int32_t* labels, uint32_t* counts, hipStream_t stream) {
+    check_speckle_map(disparity);
+    if (disparity.memory() != Memory::Device)
+        throw Exception("filter_speckles: device buffers need a device map");
+    const void* map = disparity.data();  // (out may be the same header)
+    const int rows = disparity.rows(), cols = disparity.cols(), type = disparity.type();
+    out.create(rows, cols, type, Memory::Device);
+    throw_rc(bicos_speckle_device(current_engine(), map, type, rows, cols, max_size, max_diff,
+                                  flags, out.data(), labels, counts, stream));
+}
+
+SpeckleStats filter_speckles(const Image& disparity, Image& out, int max_size, float max_diff,
+                             int flags, std::vector<int32_t>* labels) {
+    check_speckle_map(disparity);
+    const void* map = disparity.data();
+    const int rows = disparity.rows(), cols = disparity.cols(), type = disparity.type();
+    const Memory mem = disparity.memory();
+    const size_t pixels = (size_t)(rows > 0 ? rows : 0) * (size_t)(cols > 0 ? cols : 0);
+    uint32_t counts[4] = {0, 0, 0, 0};
+    out.create(rows, cols, type, mem);
+    if (labels) labels->resize(pixels);
+    if (mem == Memory::Host) {
+        throw_rc(bicos_speckle_host(nullptr, map, type, rows, cols, max_size, max_diff, flags,
+                                    out.data(), labels ? labels->data() : nullptr, counts));
+    } else {
+        // counts | labels in one device allocation, downloaded after the launches
+        void* raw = nullptr;
+        throw_rc(check_hip(hipMalloc(&raw, (4 + (labels ? pixels : 0)) * 4), "hipMalloc(labels)"));
+        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
+        uint32_t* d_counts = (uint32_t*)raw;
+        int32_t* d_labels = labels ? (int32_t*)raw + 4 : nullptr;
+        throw_rc(bicos_speckle_device(current_engine(), map, type, rows, cols, max_size, max_diff,
+                                      flags, out.data(), d_labels, d_counts, nullptr));
+        throw_rc(check_hip(hipMemcpy(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost),
+                           "counts download"));
+        if (labels && pixels)
+            throw_rc(check_hip(hipMemcpy(labels->data(), d_labels, pixels * sizeof(int32_t),
+                                         hipMemcpyDeviceToHost), "labels download"));
+    }
+    return SpeckleStats{counts[0], counts[1], counts[2], counts[3]};
 }
 
 }  // namespace BICOS

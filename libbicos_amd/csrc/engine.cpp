@@ -6,6 +6,7 @@
 // API cxxapi.cpp (engine.hpp).
 #include "engine.hpp"
 #include "reproject.hpp"
+#include "speckle.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -602,6 +603,59 @@ int reproject_device(bicos_engine* e, const ReprojectJob& j, hipStream_t st) {
     if (int rc = ws.acquire()) return rc;
     carve();
     return check_hip(bicos_hip::launch_reproject_points(a, f32, st), "reproject launches");
+}
+
+// ------------------------------------------------------------ speckle filter
+
+int check_speckle(const SpeckleJob& j, const bicos_engine* e, bool needs_engine) {
+    if (j.disp_type != BICOS_CV_16S && j.disp_type != BICOS_CV_32F)
+        return fail(BICOS_E_ARG, "speckle: the disparity map must be CV_16S or CV_32F");
+    if (j.rows < 0 || j.cols < 0) return fail(BICOS_E_ARG, "speckle: negative image size");
+    if ((int64_t)j.rows * j.cols > INT32_MAX)
+        return fail(BICOS_E_ARG, "speckle: rows * cols exceeds int32");
+    if (j.flags & ~BICOS_SPECKLE_F32_SENTINEL)
+        return fail(BICOS_E_ARG, "speckle: unknown flag bits");
+    if (!(j.max_diff >= 0.0f))
+        return fail(BICOS_E_ARG, "speckle: max_diff must be >= 0 and not NaN");
+    if (j.max_size < 0) return fail(BICOS_E_ARG, "speckle: negative max_size");
+    if (needs_engine && !e) return fail(BICOS_E_ARG, "speckle: null engine (workspace)");
+    if (j.rows > 0 && j.cols > 0) {
+        if (!j.disp) return fail(BICOS_E_ARG, "speckle: null disparity map");
+        if (!j.out) return fail(BICOS_E_ARG, "speckle: null out");
+        const uintptr_t a = (uintptr_t)j.disp, b = (uintptr_t)j.out;
+        const uintptr_t bytes = (uintptr_t)j.rows * j.cols * (j.disp_type == BICOS_CV_32F ? 4 : 2);
+        if (a != b && a < b + bytes && b < a + bytes)
+            return fail(BICOS_E_ARG, "speckle: out overlaps the map partially (in place: out == map)");
+    }
+    return BICOS_OK;
+}
+
+int speckle_device(bicos_engine* e, const SpeckleJob& j, hipStream_t st) {
+    const size_t pixels = (size_t)j.rows * j.cols;
+    if (pixels == 0)  // nothing to launch: the counts are all zero
+        return j.counts ? check_hip(hipMemsetAsync(j.counts, 0, 4 * sizeof(uint32_t), st),
+                                    "hipMemsetAsync(counts)")
+                        : (int)BICOS_OK;
+    bicos_hip::SpeckleArgs a{};
+    a.disp = j.disp;
+    a.out = j.out;
+    a.rows = j.rows;
+    a.cols = j.cols;
+    a.max_size = (uint32_t)j.max_size;
+    a.max_diff = j.max_diff;
+    a.flags = j.flags;
+    a.counts = j.counts;
+    a.final_labels = j.labels != nullptr;
+    Lease ws(e, e->ws, e->ws_bytes, st);
+    auto carve = [&] {
+        a.sizes = ws.take<uint32_t>(pixels);
+        a.labels = j.labels ? j.labels : ws.take<int32_t>(pixels);
+    };
+    carve();
+    if (int rc = ws.acquire()) return rc;
+    carve();
+    return check_hip(bicos_hip::launch_speckle(a, j.disp_type == BICOS_CV_32F, st),
+                     "speckle launches");
 }
 
 // ------------------------------------------------------- process-wide engines

@@ -5,11 +5,13 @@
 // optional agree / subpixel. All launches are asynchronous on one HIP stream.
 //
 //   engine.cpp  errors, the workspace lease, engine resources, the plans, the search driver
-//               and match_device; reproject_device (disparity map -> 3-D points)
-//   host.cpp    the banded host-buffer pipeline (HostPool, match_host); reproject_host
+//               and match_device; reproject_device (disparity map -> 3-D points);
+//               speckle_device (the speckle filter of a disparity map)
+//   host.cpp    the banded host-buffer pipeline (HostPool, match_host); reproject_host;
+//               speckle_host
 //   entries.cpp the bicos_* extern "C" entries (bicos_c.h) but the multi-GPU ones
 //   multi.cpp   bicos_match_host_multi, bicos_match_bands_device
-//   cxxapi.cpp  namespace BICOS (HipImage, match, reproject)
+//   cxxapi.cpp  namespace BICOS (HipImage, match, reproject, filter_speckles)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -289,6 +291,28 @@ int reproject_device(bicos_engine* e, const ReprojectJob& j, hipStream_t st);
 // Host buffers: the map uploaded into the engine's staging, the same launches on the engine's
 // own stream, the counts and then min(kept, capacity) points downloaded. Synchronous.
 int reproject_host(bicos_engine* e, const ReprojectJob& j);
+
+// One speckle filter (bicos_c.h "speckle filter"): the arguments of bicos_speckle_device /
+// bicos_speckle_host, the pointers all in device or all in host memory.
+struct SpeckleJob {
+    const void* disp;
+    int disp_type, rows, cols;
+    int max_size;
+    float max_diff;
+    int flags;
+    void* out;
+    int32_t* labels;
+    uint32_t* counts;
+};
+// BICOS_E_ARG (with a message) for what the entries refuse; no HIP call. needs_engine: a NULL
+// engine is an error (the device entry; the host entry has a default engine).
+int check_speckle(const SpeckleJob& j, const bicos_engine* e, bool needs_engine);
+// The launches on `st` (validated arguments): tile, border, resolve, apply, with the label
+// array (unless j.labels is given) and the size array in the engine's workspace.
+int speckle_device(bicos_engine* e, const SpeckleJob& j, hipStream_t st);
+// Host buffers: the map uploaded into the engine's staging, the same launches on the engine's
+// own stream, the map, the counts and the labels downloaded. Synchronous.
+int speckle_host(bicos_engine* e, const SpeckleJob& j);
 
 // Process-wide engine for `device` (created on first use).
 bicos_engine* default_engine(int device);

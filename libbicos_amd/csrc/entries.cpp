@@ -2,6 +2,7 @@
 // (engine.hpp); the multi-GPU entries are multi.cpp, the reference's ctypes ABI capi.cpp.
 #include "engine.hpp"
 #include "reproject.hpp"
+#include "speckle.hpp"
 
 #include <cmath>
 #include <vector>
@@ -367,6 +368,43 @@ int bicos_reproject_host(bicos_engine* e, const void* disparity, int disp_type, 
 }
 
 int bicos_reproject_segment(void) { return bicos_hip::REPROJECT_SEGMENT; }
+
+int bicos_speckle_device(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                         int max_size, float max_diff, int flags, void* out, int32_t* labels,
+                         uint32_t* counts, void* stream) {
+    const SpeckleJob job{disparity, disp_type, rows, cols, max_size, max_diff, flags, out, labels,
+                         counts};
+    if (int rc0 = check_speckle(job, e, true)) return rc0;
+    return guarded([&]() -> int {
+        std::lock_guard<std::mutex> g(e->lock);
+        return speckle_device(e, job, (hipStream_t)stream);
+    });
+}
+
+int bicos_speckle_host(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                       int max_size, float max_diff, int flags, void* out, int32_t* labels,
+                       uint32_t counts[4]) {
+    const SpeckleJob job{disparity, disp_type, rows, cols, max_size, max_diff, flags, out, labels,
+                         counts};
+    if (int rc0 = check_speckle(job, e, false)) return rc0;
+    return guarded([&]() -> int {
+        if (!e) {
+            int dev = 0;
+            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
+            if (rc) return rc;
+            e = default_engine(dev);
+            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        }
+        std::lock_guard<std::mutex> g(e->lock);
+        return speckle_host(e, job);
+    });
+}
+
+int bicos_speckle_tile(int* rows, int* cols) {
+    if (rows) *rows = bicos_hip::SPECKLE_TILE_ROWS;
+    if (cols) *cols = bicos_hip::SPECKLE_TILE_COLS;
+    return BICOS_OK;
+}
 
 const char* bicos_build_info(void) {
     return "libbicos_amd: gfx950 HIP kernels (transform, mx search: FP4 MFMA Hamming products "

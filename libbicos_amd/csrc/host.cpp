@@ -409,4 +409,42 @@ int reproject_host(bicos_engine* e, const ReprojectJob& j) {
     return rc ? rc : rc2;
 }
 
+int speckle_host(bicos_engine* e, const SpeckleJob& j) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    if (int rc0 = check_speckle(j, e, false)) return rc0;
+    const size_t pixels = (size_t)j.rows * j.cols;
+    if (pixels == 0) {
+        if (j.counts) std::fill(j.counts, j.counts + 4, 0u);
+        return BICOS_OK;
+    }
+    hipStream_t st = e->own_stream;
+    const size_t esz = j.disp_type == BICOS_CV_32F ? 4 : 2;
+    SpeckleJob d = j;  // the same job on staged device buffers, filtered in place
+    Lease stage(e, e->stage, e->stage_bytes, st);
+    auto carve = [&] {
+        d.out = stage.take(pixels * esz);
+        d.disp = d.out;
+        d.labels = j.labels ? stage.take<int32_t>(pixels) : nullptr;
+        d.counts = j.counts ? stage.take<uint32_t>(4) : nullptr;
+    };
+    carve();
+    int rc = stage.acquire();
+    if (rc) return rc;
+    carve();
+    rc = check_hip(hipMemcpyAsync(d.out, j.disp, pixels * esz, hipMemcpyHostToDevice, st),
+                   "disparity upload");
+    if (!rc) rc = speckle_device(e, d, st);
+    if (!rc)
+        rc = check_hip(hipMemcpyAsync(j.out, d.out, pixels * esz, hipMemcpyDeviceToHost, st),
+                       "filtered map download");
+    if (!rc && j.labels)
+        rc = check_hip(hipMemcpyAsync(j.labels, d.labels, pixels * sizeof(int32_t),
+                                      hipMemcpyDeviceToHost, st), "labels download");
+    if (!rc && j.counts)
+        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 4 * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, st), "counts download");
+    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    return rc ? rc : rc2;
+}
+
 }  // namespace bicos_impl

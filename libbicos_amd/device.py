@@ -319,6 +319,65 @@ class Engine:
                                % (capacity, kept))
         return out[:kept], (index[:kept] if index is not None else None), stats
 
+    # ---------------------------------------------------------- speckle filter
+    def filter_speckles(self, disp: torch.Tensor, max_size: int, max_diff: float = 1.0, *,
+                        sentinel: bool = True, out: Optional[torch.Tensor] = None,
+                        labels=False, counts: Optional[torch.Tensor] = None, stream=None):
+        """bicos_speckle_device: removes every 4-connected component of similar disparity
+        (neighbours differing by at most max_diff) that has at most max_size pixels from an
+        int16 or float32 map [rows, cols]; include/bicos_c.h, "speckle filter". Removed pixels
+        become invalid (int16 -32768; float NaN, or -32768.0 with `sentinel`, which also makes
+        that value invalid on input, as match() writes it without a subpixel step); every
+        other pixel keeps its bits. max_size = 0 removes nothing.
+
+        Returns the filtered map -- `out` if given (it may be `disp` itself: in place), else a
+        new tensor -- or, with `labels`, the pair (map, labels): int32 [rows, cols], every
+        pixel's component label (the smallest row * cols + col in its component; -1 where the
+        pixel was invalid on input). `labels` may be True or an int32 tensor to fill.
+        `counts`, an int32 [4] tensor on the map's device, receives {kept, removed, invalid,
+        removed_components} (uint32 bits).
+
+        The call NEVER synchronises: everything is enqueued on `stream` (default: torch's
+        current stream). Reading `counts` (`counts.tolist()`) is where the caller does."""
+        if not disp.is_cuda:
+            raise ValueError("device API needs CUDA/HIP tensors")
+        if disp.dim() != 2:
+            raise ValueError("disparity map must be [rows, cols]")
+        if disp.dtype not in (torch.int16, torch.float32):
+            raise ValueError("disparity map must be int16 or float32, got %s" % disp.dtype)
+        if not disp.is_contiguous():
+            raise ValueError("disparity map must be contiguous (dense rows)")
+        rows, cols = disp.shape
+        if rows * cols >= 2 ** 31:
+            raise ValueError("disparity map has more than 2^31 - 1 pixels")
+        size, diff = _lib.speckle_params(max_size, max_diff)
+        dev = disp.device
+        if out is None:
+            out = torch.empty_like(disp)
+        _check_out(out, "out", (rows, cols), (disp.dtype,), dev)
+        lab = None
+        if labels is True:
+            lab = torch.empty((rows, cols), dtype=torch.int32, device=dev)
+        elif labels is not False and labels is not None:
+            lab = labels
+            _check_out(lab, "labels", (rows, cols), (torch.int32,), dev)
+        if counts is not None:
+            _check_out(counts, "counts", (4,), (torch.int32,), dev)
+        if rows * cols == 0:  # (an empty tensor has no pointer to hand over)
+            if counts is not None:
+                s = stream if stream is not None else torch.cuda.current_stream(dev)
+                with torch.cuda.stream(s):
+                    counts.zero_()
+            return out if lab is None else (out, lab)
+        typ = _lib.CV_32F if disp.dtype == torch.float32 else _lib.CV_16S
+        rc = self._L.bicos_speckle_device(
+            self._h, disp.data_ptr(), typ, rows, cols, size, diff,
+            _lib.SPECKLE_F32_SENTINEL if sentinel else 0, out.data_ptr(),
+            lab.data_ptr() if lab is not None else None,
+            counts.data_ptr() if counts is not None else None, _stream(dev, stream))
+        _lib.check(rc, "bicos_speckle_device")
+        return out if lab is None else (out, lab)
+
     # ----------------------------------------------------------------- stages
     def transform(self, stack: torch.Tensor, mode: int = 0, words: Optional[int] = None,
                   out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:

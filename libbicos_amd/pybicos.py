@@ -263,6 +263,35 @@ def reproject(disparity, Q, allow_negative_z=False, sentinel=True):
     return points[:counts[0]].copy()
 
 
+def filter_speckles(disparity, max_size, max_diff=1.0, sentinel=True):
+    """An extension (the reference has no such step; cv2.filterSpeckles is the CPU
+    counterpart): removes from a disparity map of match() -- int16 or float32, [rows, cols] --
+    every 4-connected component of similar disparity (neighbours differing by at most
+    max_diff) that has at most max_size pixels (bicos_speckle_host, include/bicos_c.h "speckle
+    filter": on the GPU, exact). Removed pixels become invalid: int16 -32768, float NaN, or
+    with `sentinel` the float -32768.0 of a match without subpixel step, which is then also
+    invalid on input. Returns (filtered, stats) with stats = dict(kept, removed, invalid,
+    removed_components); the input is left as it is."""
+    d = np.ascontiguousarray(disparity)
+    if d.ndim != 2:
+        raise ValueError("disparity map must be 2-D")
+    if d.dtype != np.int16 and d.dtype != np.float32:
+        raise ValueError(f"Unsupported disparity dtype: {d.dtype}")
+    size, diff = _lib.speckle_params(max_size, max_diff)
+    rows, cols = d.shape
+    out = np.empty_like(d)
+    counts = (ctypes.c_uint32 * 4)()
+    L = _lib.lib()
+    rc = L.bicos_speckle_host(None, d.ctypes.data, _get_cv_type(d.dtype), rows, cols, size, diff,
+                              _lib.SPECKLE_F32_SENTINEL if sentinel else 0, out.ctypes.data,
+                              None, counts)
+    if rc != 0:
+        raise RuntimeError("BICOS speckle filter failed: " +
+                           L.bicos_last_error().decode(errors="replace"))
+    return out, dict(kept=counts[0], removed=counts[1], invalid=counts[2],
+                     removed_components=counts[3])
+
+
 def invalid_disparity(dtype):
     """reference pybicos/__init__.py:246-252."""
     L = _lib.lib()
