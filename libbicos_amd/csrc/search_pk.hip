@@ -39,11 +39,12 @@
 // of every accumulator hold 0x4B00 + 32 + ham_lo (C carries + 64, each word adds ham_w - 16),
 // and the final field is 0x4B00 + ham with ham >= ham_lo. The packed tree of these partial keys,
 // combined over the lane halves as in pair_step, is tested per field against thr = R +
-// 0x00200020 as UNSIGNED 16-BIT INTEGERS (not f16: PK_PAD + 0x20 is a NaN pattern): reach is
-// ham_lo <= running minimum, "<=" because a tie must never be pruned (NoDuplicates needs
-// it). The decision is per wide tile (the ballot's halves): a tile none of whose 64 col0
-// reaches skips its MFMAs of words 2 and 3 and its tree; it enters the pair step, if the
-// other tile takes one, with its partial keys. That is safe under lazy drops: a pruned
+// 0x00210021 as UNSIGNED 16-BIT INTEGERS (not f16: PK_PAD + 0x21 is a NaN pattern) by one
+// saturating subtraction, thr - key != 0 (v_pk_sub_u16 clamp; neither field of thr wraps: R <=
+// 0x7BFF): reach is ham_lo <= running minimum, "<=" because a tie must never be pruned
+// (NoDuplicates needs it). The decision is per wide tile (the ballot's halves): a tile none of
+// whose 64 col0 reaches skips its MFMAs of words 2 and 3 and its tree; it enters the pair step,
+// if the other tile takes one, with its partial keys. That is safe under lazy drops: a pruned
 // tile-block has block minimum > R for every col0, and R only falls, so the block is neither
 // a drop nor a tie now or later; its partial keys lie above R too, so all they can give M is
 // a positive value, which never decides anything -- `ok` tests M == 0 only, and a later drop
@@ -79,11 +80,17 @@
 // EOR also requests the raw right row and the lane's two left descriptors before the barrier
 // that waits for the workgroup's slowest wave, and writes the row to LDS behind it.
 //
-// ST (search_pkp_kernel only; the plan guarantees chunk = 2 * blockDim.x and cols > chunk): the
+// ST (search_pkp_kernel only; the plan guarantees chunk = 2 * blockDim.x = PKP_ST_CHUNK and
+// cols > chunk -- a tuned geometry with another chunk takes the chunk loop): the
 // right row streamed exactly as search_mx_kernel ST does -- the workgroup's own chunk
 // expanded whole, the rest of the row in stages of half a chunk alternating between the two
 // halves of the chunk region, the next stage's raw descriptor held in four VGPRs across the
 // block loop, one barrier per stage. Same LDS layout; only the expansion table differs.
+//
+// The block loops of search_pkp_kernel name a block by the LDS address of the lane's word-0
+// fragment of it and step that address by a scalar delta (-512 bytes, or back up to the step's
+// last full block at the wrap); words 1-3 lie 16 chunk bytes apart, at immediate offsets in
+// the streamed instantiations, whose chunk is the constant PKP_ST_CHUNK.
 #include "search_dev.hpp"
 
 #include <cstdlib>
@@ -104,6 +111,14 @@ constexpr uint32_t PK_PAD = 0x7BFF7BFFu;
 #define BICOS_PKP_EARLY 1
 #endif
 constexpr bool PKP_EARLY = BICOS_PKP_EARLY != 0;
+// search_pkp_kernel ST: the chunk is PKP_ST_CHUNK (search_plan.hpp: the default geometry's, 8
+// waves over a 64 KiB stage), a constant of those instantiations so that a block's words 1-3
+// are read at immediate offsets (16, 32, 48 KiB: the ds_read offset field has 16 bits) from
+// the address of its word-0 fragment. plan_mx (search_plan.cpp) streams the packed search at
+// that geometry only; launch_pk_variant refuses a streamed launch with any other.
+// search_pkp_kernel's reach test: thr = R + 33 per field, so that the saturated thr - lb is 0
+// exactly where ham_lo lies above the running minimum
+constexpr uint32_t PKP_THR = 0x00210021u;
 // Lazy drops (round 6). A strict drop of the running minimum used to branch into (distance,
 // row) key trees that found its first row and whether the block holds it twice -- one
 // wave-uniform branch whenever any of the wave's 128 col0 dropped, ~150 VALU; on random
@@ -128,6 +143,10 @@ __device__ __forceinline__ uint32_t pkminu(uint32_t a, uint32_t b) {  // v_pk_mi
 }
 __device__ __forceinline__ uint32_t pksub(uint32_t a, uint32_t b) {  // v_pk_sub_u16 (wraps)
     return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2, a) - __builtin_bit_cast(u16x2, b));
+}
+__device__ __forceinline__ uint32_t pksubsat(uint32_t a, uint32_t b) {  // v_pk_sub_u16 clamp: max(a - b, 0)
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(u16x2, a),
+                                                                      __builtin_bit_cast(u16x2, b)));
 }
 __device__ __forceinline__ uint32_t pksign(uint32_t a) {  // 0xFFFF per field with its top bit set
     return __builtin_bit_cast(uint32_t, __builtin_bit_cast(i16x2, a) >> (short)15);
@@ -481,12 +500,21 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     const int h = lane >> 5;
     const int j = lane & 31;
     const int cols = a.cols;
-    const int chunk = a.chunk;
+    const int chunk = ST ? PKP_ST_CHUNK : a.chunk;
     const int waves = blockDim.x >> 6;
     const int c0_wave = (tile * waves + wave) * (T * 64);
 
     const uint32_t* __restrict__ row0 = a.desc0 + (size_t)row * a.desc_pitch;
     const uint32_t* __restrict__ row1 = a.desc1 + (size_t)row * a.desc_pitch;
+
+    // the fragment of word w of the block whose word-0 fragment this lane reads at LDS address
+    // ad (ST: at an immediate offset). LDS addresses as integers, lds0 the chunk region's: with
+    // the region's pointer in the sum the compiler adds its address, 0, to ad at every read.
+    typedef const __attribute__((address_space(3))) v4i* lds_frag_ptr;
+    const uint32_t lds0 = (uint32_t) reinterpret_cast<uintptr_t>((lds_frag_ptr)lds_mx);
+    auto frag = [&](uint32_t ad, int w) {
+        return *reinterpret_cast<lds_frag_ptr>(ad + (uint32_t)(w * chunk * 16));
+    };
 
     // ST: the raw right descriptor of col1 (zero past the image), and the own chunk's two
     // columns of this thread, requested ahead of the B-fragment loads below
@@ -530,10 +558,10 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     for (int r = 0; r < 16; ++r) cb[r] = CBIAS;
 
     // lanes 0-31: tile 0, lanes 32-63: tile 1 -- running minimum, tie marker, block base of
-    // the last drop; the reach test's threshold R + 32 per field; the fallback's state
+    // the last drop; the reach test's threshold R + 33 per field; the fallback's state
     // (wave-uniform)
     uint32_t R = PK_PAD, M = 0xFFFFFFFFu, C = 0u;
-    uint32_t thr = PK_PAD + 0x00200020u;
+    uint32_t thr = PK_PAD + PKP_THR;
     bool prune_on = true;
     int wblocks = 0, wreach = 0;
     auto rrow = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
@@ -561,7 +589,7 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
             R = bfi(mi, comb, R);
             asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(C) : "v"(mi), "s"((uint32_t)B * 0x10001u));
         }
-        thr = R + 0x00200020u;
+        thr = R + PKP_THR;
     };
 
     const bool idle = c0_wave >= cols;  // wave-uniform; still joins the barriers
@@ -608,15 +636,17 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         if (idle) continue;
 
         const int nfull = ncols / 32;
-        // (block indices: LDS blocks of the chunk region, the step's first one b0)
-        // a block in full: the partial last block (pad) and the fallback's loop
-        auto block = [&](int b, bool pad) {
-            const int B = base + 32 * b;
+        // (block indices: LDS blocks of the chunk region, the step's first one b0; the loops
+        // name block b by ad, the LDS address of this lane's word-0 fragment of it: lds0 +
+        // 16 (32 b + j))
+        // a block in full, at col1 B, the step's block bi: the partial last block (pad) and the
+        // fallback's loop
+        auto block = [&](uint32_t ad, int B, int bi, bool pad) {
             // (C kept in VGPRs: left alone the compiler re-copies it from SGPRs every block)
             asm volatile("" : "+v"(cb));
             v4i af[WORDS];
 #pragma unroll
-            for (int w = 0; w < WORDS; ++w) af[w] = lds_mx[w * chunk + 32 * b + j];
+            for (int w = 0; w < WORDS; ++w) af[w] = frag(ad, w);
             v16f dx = mfma_pk(af[0], bf[0][0], cb, sb);
             v16f dy = mfma_pk(af[0], bf[1][0], cb, sb);
 #pragma unroll
@@ -627,38 +657,41 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
             if (pad) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const bool in = 32 * (b - b0) + rrow(r) < ncols;
+                    const bool in = 32 * bi + rrow(r) < ncols;
                     dx[r] = in ? dx[r] : bitsf(PK_PAD);
                     dy[r] = in ? dy[r] : bitsf(PK_PAD);
                 }
             }
             pair_update(B, pk_tree(dx), pk_tree(dy));
         };
-        // a full block with words 2 and 3 only for the wide tiles that can reach (see the
-        // header). af0 holds the block's word-0 fragment on entry and block nb's (the next
-        // one) on return, read once the probe products are issued; the other words' fragments
-        // are read here, at the top of the block. Counts the reaching wide tiles into wreach.
-        auto block_pr = [&](int b, v4i& af0, int nb) {
-            const int B = base + 32 * b;
+        // a full block, at col1 B, with words 2 and 3 only for the wide tiles that can reach
+        // (see the header). af0 holds the block's word-0 fragment on entry and the next
+        // block's on return, read once the probe products are issued; the other words'
+        // fragments are read here, at the top of the block, and ad then steps by d bytes to the
+        // next block. Counts the reaching wide tiles into wreach.
+        auto block_pr = [&](int B, uint32_t& ad, v4i& af0, int d) {
             asm volatile("" : "+v"(cb));
-            const v4i af1 = lds_mx[chunk + 32 * b + j];
+            const v4i af1 = frag(ad, 1);
             // (words 2 and 3 read here too: read only in the blocks that reach, the fused
             // cfg2 launch took 275.9 instead of 273.5 us)
-            const v4i af2 = lds_mx[2 * chunk + 32 * b + j];
-            const v4i af3 = lds_mx[3 * chunk + 32 * b + j];
+            const v4i af2 = frag(ad, 2);
+            const v4i af3 = frag(ad, 3);
+            // (one v_add_u32 with the scalar step: kept a value of its own, or the compiler
+            // rebuilds the address of every word from the scalar block offset)
+            ad += (uint32_t)d;
+            asm volatile("" : "+v"(ad));
             v16f dx = mfma_pk(af0, bf[0][0], cb, sb);
             v16f dy = mfma_pk(af0, bf[1][0], cb, sb);
             dx = mfma_pk(af1, bf[0][1], dx, sb);
             dy = mfma_pk(af1, bf[1][1], dy, sb);
             // (both tiles' probe products go out before the first key is read)
             __builtin_amdgcn_sched_barrier(0);
-            af0 = lds_mx[32 * nb + j];
+            af0 = frag(ad, 0);
             uint32_t x = pk_tree(dx), y = pk_tree(dy);
             const auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);
-            // ham_lo <= running minimum in either field, as u16: thr - lb does not wrap
-            // below zero ("<=": a tie reaches)
-            const uint32_t under = pksub(thr, pkminu(sw[0], sw[1])) & 0x80008000u;
-            const uint64_t bal = __builtin_amdgcn_ballot_w64(under != 0x80008000u);
+            // ham_lo <= running minimum in either field, as u16 ("<=": a tie reaches): thr
+            // is R + 33, so the saturated thr - lb is 0 exactly where lb > R + 32
+            const uint64_t bal = __builtin_amdgcn_ballot_w64(pksubsat(thr, pkminu(sw[0], sw[1])) != 0u);
             if (bal) {
                 uint32_t lo = (uint32_t)bal, hi = (uint32_t)(bal >> 32);
                 asm volatile("" : "+s"(lo), "+s"(hi));
@@ -677,26 +710,34 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
                 pair_update(B, x, y);
             }
         };
-        if ((ncols & 31) != 0) block(b0 + nfull, true);
+        const int Bs = base + 32 * b0;  // col1 of the step's first block
+        if ((ncols & 31) != 0)
+            block(lds0 + 16u * (uint32_t)(32 * (b0 + nfull) + j), Bs + 32 * nfull, nfull, true);
         // full blocks downwards from the one holding the wave's highest col0 (clamped)
         const int sb0 = max(0, min(nfull - 1, (min(cols - 1, c0_wave + 64 * T - 1) - base - 32 * b0) / 32));
+        // The visiting order as one carried address: so = 512 x the step's block index (a
+        // block's word-0 fragments are 512 bytes), stepped by -512, or from block 0 back up to
+        // the last full block; ad follows it by the same scalar step. A read never leaves
+        // the step's nfull blocks.
+        int so = 512 * sb0;
+        const int wrap = 512 * (nfull - 1);
+        uint32_t ad = lds0 + 16u * (uint32_t)(32 * b0 + j) + (uint32_t)so;
         // The pruned loop over the first i0 blocks of the visiting order -- all of them unless
         // a window sends the wave to the unpruned loop below for the rest of the row. Shaped
         // as search_mx_kernel's: an inner run of blocks up to the window's end that only steps
-        // the (wrapping) block index, the next block's word-0 fragment read unconditionally
-        // (behind the last block: the wrapped index, a block nobody uses)
+        // the (wrapping) block offset, the next block's word-0 fragment read unconditionally
+        // (behind the last block: the wrapped offset, a block nobody uses)
         int i0 = 0;
         if (prune_on && nfull > 0) {
-            int b = sb0;
-            v4i af0 = lds_mx[32 * (b0 + b) + j];
+            v4i af0 = frag(ad, 0);
             while (i0 < nfull) {
                 int n = min(nfull - i0, PRUNE_WINDOW - wblocks);
                 i0 += n;
                 wblocks += n;
                 for (; n > 0; --n) {
-                    const int nb = b > 0 ? b - 1 : nfull - 1;
-                    block_pr(b0 + b, af0, b0 + nb);
-                    b = nb;
+                    const int d = so > 0 ? -512 : wrap;
+                    block_pr(Bs + (so >> 4), ad, af0, d);
+                    so += d;
                 }
                 if (wblocks == PRUNE_WINDOW) {
                     const bool fall = 8 * wreach >= 7 * PRUNE_WINDOW * T;
@@ -709,9 +750,10 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
             }
         }
         for (int i = i0; i < nfull; ++i) {
-            int b = sb0 - i;
-            if (b < 0) b += nfull;
-            block(b0 + b, false);
+            const int d = so > 0 ? -512 : wrap;
+            block(ad, Bs + (so >> 4), 0, false);
+            ad += (uint32_t)d;
+            so += d;
         }
     }
     // The workgroup's integer results (AG) and the right row's raw words for the rescans go
@@ -931,6 +973,8 @@ hipError_t launch_pk_variant(const SearchLaunch& l, const SearchArgs& a, const A
     if (!PK_LAZY && v.lazy) return hipErrorInvalidValue;
     if (v.prune || v.stream) {  // search_pkp_kernel: the pruned 128-bit lazy search, streamed or not
         if (!v.prune || !v.lazy || v.words != 4 || v.T != 2 || v.tail || v.list) return hipErrorInvalidValue;
+        // (the streamed instantiations are built for one chunk: two columns per thread)
+        if (v.stream && (a.chunk != PKP_ST_CHUNK || l.block * 2 != PKP_ST_CHUNK)) return hipErrorInvalidValue;
         // clang-format off
         return pick<bool, false, true>(v.agree, [&](auto agree) {
         return pick<bool, false, true>(v.stream, [&](auto stream) {

@@ -157,6 +157,8 @@ SearchLaunchPlan plan_mx(const SearchArgs& a, const MxGeometry& g, int words, bo
         v.stream = mx_streamable(a.cols, g.chunk, g.waves, g.stream != 0);
         v.prune = g.prune != 0;
         v.packed = packed_search(g, v, a.cols);
+        // (the packed kernel streams at one chunk only; at any other it runs its chunk loop)
+        if (v.packed && (g.chunk != PKP_ST_CHUNK || 128 * g.waves != PKP_ST_CHUNK)) v.stream = false;
     }
     SearchLaunchPlan p;
     p.launch[p.n++] = make_launch(v, a.rows, g.waves, 32, 2 * v.ksteps, g.chunk, tiles_per_row, tail_col0, tail_T);

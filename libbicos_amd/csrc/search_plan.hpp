@@ -22,6 +22,12 @@ constexpr int LR_KSTEPS = 3;
 // The pruned 128-bit searches' fallback (search_mx.hip PRUNE, search_pk.hip search_pkp_kernel): visited
 // blocks per window
 constexpr int PRUNE_WINDOW = 8;
+// The one chunk search_pkp_kernel's streamed instantiations are built for (search_pk.hip: words
+// 1-3 of a block at immediate offsets from its word-0 fragment): the default geometry's, 8
+// waves over a 64 KiB stage. mx_streamable alone allows any chunk of two columns per thread
+// (a tuned engine: 512 with 4 waves over 32 KiB); plan_mx gives the packed search of such a
+// geometry the chunk loop, and launch_pk_variant refuses what it did not plan.
+constexpr int PKP_ST_CHUNK = 1024;
 
 // Lazy drops of the packed-key search (search_pk.hip; BICOS_PK_LAZY=0 builds the branch
 // only, A/B). They pay a fixed rescan per col0 (~32 popcounts of WORDS words); the drop
