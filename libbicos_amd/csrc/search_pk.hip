@@ -7,90 +7,22 @@
 // per two keys, one key per accumulator register. Here every accumulator register carries
 // TWO Hamming distances, and the tree runs on gfx950's v_pk_minimum3_f16 (half rate, four
 // keys per instruction; profiles/valu_rates_r03.jsonl), so the reduction per pair halves.
+// The keys carry no column: per col0 a wave keeps the running minimum, a tie marker and the
+// block that holds the minimum, and finds the column inside that block.
 //
-// Operands: right A = 1 - 2b in {+1, -1}, left B = -(1 - 2a) / 2 in {-0.5, +0.5} (both exact
-// FP4 e2m1), so one K position contributes -(1 - 2a)(1 - 2b) / 2 and K positions sum to
-// ham - K / 2 (K = 32 WORDS, the zero bits past the used ones included: they add the same
-// -1/2 to every pair). One MFMA multiplies ONE descriptor word: the B lanes of K-half 0 hold
-// word w of col0 P, those of K-half 1 word w of col0 Q = P + 32, and the E8M0 scale of the
-// K-half-0 lanes is 2^16. With C = 2^23 + 2^16 (K/2) + 0x4B00 + K/2 every D is an integer in
-// [2^23, 2^24) (ulp 1), so
-//     bits(D) = 0x4B000000 + 2^16 ham(P, col1) + 0x4B00 + ham(Q, col1)
-// exactly: the high half is 0x4B00 + ham_P, the low half 0x4B00 + ham_Q, both positive normal
-// f16 values whose order is the order of the distances (ham <= 127 keeps each in 7 bits; the
-// partial sums of the first words stay inside [0, 127] too). WORDS MFMAs cover 32 col1 x 64
-// col0 pairs: the same matrix-core work per pair as the one-product keys.
-//
-// The keys carry no column. Per wide tile (64 col0) and block (32 col1) the tree gives the
-// block's minimum distance per col0 (both lane halves combined by one v_permlane32_swap per
-// two tiles, as in pair_reduce); against the running minimum R (packed, per col0):
-//   block > R: nothing;  block == R: a second column at the running minimum -> duplicate
-//   (tracked as M = min over blocks of (block - R), packed; 0 = tie); block < R: a new
-//   minimum: the rare branch finds its first column in the block and whether the block holds
-//   it twice ((distance, row) keys through v_perm + v_pk_min_u16, first and reversed rows),
-//   and resets M. Any block order gives the same result (a tie with a later-improved minimum
-//   is forgotten on the improvement, exactly as the reference's strict '<' scan would).
-// Columns beyond the image in the partial block are set to 0x7BFF (the largest finite f16)
-// before the tree.
-//
-// search_pkp_kernel (128-bit descriptors, two wide tiles per wave, lazy drops, main launches
-// over every col0; a kernel of its own, so that search_pk_kernel's instantiations stay as they
-// are): words 2 and 3 only where they can matter. After the MFMAs of words 0 and 1 both fields
-// of every accumulator hold 0x4B00 + 32 + ham_lo (C carries + 64, each word adds ham_w - 16),
-// and the final field is 0x4B00 + ham with ham >= ham_lo. The packed tree of these partial keys,
-// combined over the lane halves as in pair_step, is tested per field against thr = R +
-// 0x00210021 as UNSIGNED 16-BIT INTEGERS (not f16: PK_PAD + 0x21 is a NaN pattern) by one
-// saturating subtraction, thr - key != 0 (v_pk_sub_u16 clamp; neither field of thr wraps: R <=
-// 0x7BFF): reach is ham_lo <= running minimum, "<=" because a tie must never be pruned
-// (NoDuplicates needs it). The decision is per wide tile (the ballot's halves): a tile none of
-// whose 64 col0 reaches skips its MFMAs of words 2 and 3 and its tree; it enters the pair step,
-// if the other tile takes one, with its partial keys. That is safe under lazy drops: a pruned
-// tile-block has block minimum > R for every col0, and R only falls, so the block is neither
-// a drop nor a tie now or later; its partial keys lie above R too, so all they can give M is
-// a positive value, which never decides anything -- `ok` tests M == 0 only, and a later drop
-// resets M. thr is renewed only where R may have changed. The partial last block never
-// prunes. Fallback as search_mx_kernel's: over windows of PRUNE_WINDOW visited blocks a wave
-// counts its reaching wide-tile-blocks from the branch's own ballots; >= 7/8 of them (14 of
-// 16) send it to the unpruned loop for the rest of the row. (Lazy drops stay under pruning:
-// with the drop branch in the reaching blocks instead of the rescans the fused cfg2 launch
-// took 313.8 instead of 276.2 us.)
-//
-// EOR (search_pkp_kernel only; BICOS_PKP_EOR=0 launches the instantiations without it): a
-// shorter end of row. A lazy drop also records WHICH LANE HALF of the block holds the new
-// minimum. In pair_update sw[0] / sw[1] are the block minima of the lane's tile over the rows
-// of lane half 0 / 1 (rrow(r) = (r & 3) + 8 (r >> 2) + 4 h: half 0 owns rows 0-3, 8-11, 16-19,
-// 24-27 of the block, half 1 the others). On a strict drop of a field:
-//   sw[0] != sw[1]: every column of the block at the new minimum lies in the half with the
-//     smaller value; bit 15 of the field of C (block bases stay below 2^15) takes the sign of
-//     sw[1] - sw[0], and M takes sw[0] ^ sw[1], some value != 0: "no tie seen since".
-//   sw[0] == sw[1]: the block holds the new minimum in two rows of different halves, that is
-//     in two different columns -- exactly what a tie in a later block would have meant. M
-//     takes sw[0] ^ sw[1] = 0, the tie marker, and no rescan is needed for this col0.
-// Why that is exact: R ends as the row's minimum distance hm, and reaches it by a strict drop
-// in the first visited block whose minimum is hm; C holds that block and half. If M ends 0,
-// either a later block had minimum hm too (as before) or both halves of C's block did: a
-// second column at hm either way, invalid. A later strict drop overwrites M and C as a whole,
-// so a duplicate of a minimum that was improved on is forgotten, as before. If M ends != 0,
-// every column at hm lies in the recorded half of C's block, and the rescan of its 16 rows
-// counts them and finds the first: the same answer as the rescan of all 32. The rescan runs
-// in two levels: ham_lo (words 0 and 1) of the 16 rows against hm, then the full distance of
-// the candidates only (ham >= ham_lo, so a column at hm is always a candidate), one per lane
-// and trip of a loop that runs the wave's largest candidate count. A pruned tile's partial
-// keys lie above R in every field, so they never take the drop's side of any of this.
-// EOR also requests the raw right row and the lane's two left descriptors before the barrier
-// that waits for the workgroup's slowest wave, and writes the row to LDS behind it.
-//
-// ST (search_pkp_kernel only; the plan guarantees chunk = 2 * blockDim.x = PKP_ST_CHUNK and
-// cols > chunk -- a tuned geometry with another chunk takes the chunk loop): the
-// right row streamed exactly as search_mx_kernel ST does -- the workgroup's own chunk
-// expanded whole, the rest of the row in stages of half a chunk alternating between the two
-// halves of the chunk region, the next stage's raw descriptor held in four VGPRs across the
-// block loop, one barrier per stage. Same LDS layout; only the expansion table differs.
-//
-// The block loops of search_pkp_kernel name a block by the LDS address of the lane's word-0
-// fragment of it and step that address by a scalar delta (-512 bytes, or back up to the step's
-// last full block at the wrap); words 1-3 lie 16 chunk bytes apart, at immediate offsets in
-// the streamed instantiations, whose chunk is the constant PKP_ST_CHUNK.
+// The map -- each scheme is described once, at the function that implements it:
+//   mfma_pk                 packed keys and operands: what one product leaves in an accumulator
+//   pk_tree, pk_row_keys    the block's minimum; (distance, row) keys of the drop branch
+//   pk_bfrags, pk_cb, pk_rrow, pk_pad, pk_product
+//                           the prologue and the full product of a block, for both kernels
+//   lazy_drop               the pair step: block minimum against running minimum; lazy drops
+//   pk_rescan, pk_copy_row, pk_result, pk_agree, pk_end_of_row
+//                           the end of a row, for both kernels
+//   search_pk_kernel        1/2/4 words, 1/2/4 wide tiles, tail and list launches, the drop
+//                           branch (pair_step) or lazy drops
+//   search_pkp_kernel       the pruned 128-bit search: ST at its staging (raw_col), pruning and
+//                           the fallback at block_pr, EOR at pair_update and its end of row
+//   launch_pk_variant       the instantiations that are built
 #include "search_dev.hpp"
 
 #include <cstdlib>
@@ -104,29 +36,10 @@ namespace {
 constexpr uint32_t LUT_PA = 0xAAA22A22u;  // right: bit 0 -> +1.0 (0x2), 1 -> -1.0 (0xA)
 constexpr uint32_t LUT_PB = 0x11199199u;  // left: bit 0 -> -0.5 (0x9), 1 -> +0.5 (0x1)
 constexpr int PK_SCALE_HI = 127 + 16;     // E8M0 2^16 for the K-half-0 (col0 P) lanes
-constexpr uint32_t PK_PAD = 0x7BFF7BFFu;
-// search_pkp_kernel EOR: the end-of-row loads requested ahead of the barrier behind the scan
-// (BICOS_PKP_EARLY=0 builds them behind it: A/B of the two parts of EOR)
-#ifndef BICOS_PKP_EARLY
-#define BICOS_PKP_EARLY 1
-#endif
-constexpr bool PKP_EARLY = BICOS_PKP_EARLY != 0;
-// search_pkp_kernel ST: the chunk is PKP_ST_CHUNK (search_plan.hpp: the default geometry's, 8
-// waves over a 64 KiB stage), a constant of those instantiations so that a block's words 1-3
-// are read at immediate offsets (16, 32, 48 KiB: the ds_read offset field has 16 bits) from
-// the address of its word-0 fragment. plan_mx (search_plan.cpp) streams the packed search at
-// that geometry only; launch_pk_variant refuses a streamed launch with any other.
+constexpr uint32_t PK_PAD = 0x7BFF7BFFu;  // the largest finite f16 in both fields
 // search_pkp_kernel's reach test: thr = R + 33 per field, so that the saturated thr - lb is 0
 // exactly where ham_lo lies above the running minimum
 constexpr uint32_t PKP_THR = 0x00210021u;
-// Lazy drops (round 6). A strict drop of the running minimum used to branch into (distance,
-// row) key trees that found its first row and whether the block holds it twice -- one
-// wave-uniform branch whenever any of the wave's 128 col0 dropped, ~150 VALU; on random
-// descriptors most blocks of a scan take it. Now a drop only records the block base (C) and
-// clears the tie marker, and each col0 rescans its final block once after the scan, from the
-// right row's raw words staged in LDS: 32 popcounts of WORDS words, the first col1 at the
-// minimum and whether it occurs twice (rescan). The plan chooses per shape (PK_LAZY_MIN_COLS,
-// search_plan.hpp); BICOS_PK_LAZY=0 builds the branch only (A/B).
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
@@ -153,6 +66,24 @@ __device__ __forceinline__ uint32_t pksign(uint32_t a) {  // 0xFFFF per field wi
 }
 __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) {
     return (a & mask) | (b & ~mask);
+}
+
+// Packed keys and operands. Right A = 1 - 2b in {+1, -1}, left B = -(1 - 2a) / 2 in {-0.5,
+// +0.5} (both exact FP4 e2m1), so one K position contributes -(1 - 2a)(1 - 2b) / 2 and K
+// positions sum to ham - K / 2 (K = 32 WORDS, the zero bits past the used ones included: they
+// add the same -1/2 to every pair). One MFMA multiplies ONE descriptor word: the B lanes of
+// K-half 0 hold word w of col0 P, those of K-half 1 word w of col0 Q = P + 32, and the E8M0
+// scale sb of the K-half-0 lanes is 2^16. With C = 2^23 + 2^16 (K/2) + 0x4B00 + K/2 (pk_cb)
+// every D is an integer in [2^23, 2^24) (ulp 1), so
+//     bits(D) = 0x4B000000 + 2^16 ham(P, col1) + 0x4B00 + ham(Q, col1)
+// exactly: the high half is 0x4B00 + ham_P, the low half 0x4B00 + ham_Q, both positive normal
+// f16 values whose order is the order of the distances (ham <= 127 keeps each in 7 bits; the
+// partial sums of the first words stay inside [0, 127] too). WORDS MFMAs cover 32 col1 x 64
+// col0 pairs: the same matrix-core work per pair as the one-product keys.
+__device__ __forceinline__ v16f mfma_pk(v4i a, v4i b, v16f c, int sb) {
+    const v8i a8 = {a[0], a[1], a[2], a[3], 0, 0, 0, 0};
+    const v8i b8 = {b[0], b[1], b[2], b[3], 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, 127, 0, sb);
 }
 
 // minimum over the 16 packed keys of a D tile (v_pk_minimum3_f16 tree, 8 instructions)
@@ -186,16 +117,230 @@ __device__ __forceinline__ uint32_t pk_row_keys(const v16f& d) {
 constexpr uint32_t PK_SEL_P = 0x06010600u;
 constexpr uint32_t PK_SEL_Q = 0x04010400u;
 
-__device__ __forceinline__ v16f mfma_pk(v4i a, v4i b, v16f c, int sb) {
-    const v8i a8 = {a[0], a[1], a[2], a[3], 0, 0, 0, 0};
-    const v8i b8 = {b[0], b[1], b[2], b[3], 0, 0, 0, 0};
-    return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, 127, 0, sb);
+// ---- the prologue and the full product of a block
+
+// B fragments: wide tile t, word w; this lane's col0 is entry c0_wave + 64 t + lane of the
+// row's lcols, column lcol(entry) (K-half h: P = lanes 0-31, Q = lanes 32-63)
+template <int WORDS, int T, class LCOL>
+__device__ __forceinline__ void pk_bfrags(v4i (&bf)[T][WORDS], const uint32_t* __restrict__ row0,
+                                          int c0_wave, int lane, int lcols, LCOL lcol) {
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+        const int c0 = c0_wave + 64 * t + lane;
+        const int cl = c0 < lcols ? lcol(c0) : 0;
+#pragma unroll
+        for (int w = 0; w < WORDS; ++w) {
+            const uint32_t x = c0 < lcols ? row0[(size_t)cl * WORDS + w] : 0u;
+            bf[t][w] = expand_bits(x, LUT_PB);
+        }
+    }
+}
+// the products' C (see mfma_pk), in all 16 accumulator registers
+template <int WORDS>
+constexpr float PK_CBIAS = 8388608.f + 65536.f * (16 * WORDS) + (float)(0x4B00 + 16 * WORDS);
+template <int WORDS>
+__device__ __forceinline__ v16f pk_cb() {
+    v16f cb;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) cb[r] = PK_CBIAS<WORDS>;
+    return cb;
+}
+// the block row (col1 offset in the block) of accumulator register r in lane half h: half 0
+// owns rows 0-3, 8-11, 16-19, 24-27 of the block, half 1 the others: bit 2 of the row. (As
+// an OR: with "+ 4 h" the compiler folds the sum into pk_pad's compare, and the registers of
+// all but a few instantiations move, next_free_vgpr 80 -> 96 for <2, 2, *, *, false, true>.)
+__device__ __forceinline__ int pk_rrow(int r, int h) { return ((r & 3) + 8 * (r >> 2)) | (4 * h); }
+// Columns beyond the image in the partial block (block bi of a step with ncols columns) are set
+// to 0x7BFF (the largest finite f16) before the tree.
+__device__ __forceinline__ void pk_pad(v16f& dx, v16f& dy, int bi, int ncols, int h) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const bool in = 32 * bi + pk_rrow(r, h) < ncols;
+        dx[r] = in ? dx[r] : bitsf(PK_PAD);
+        dy[r] = in ? dy[r] : bitsf(PK_PAD);
+    }
+}
+// the full product of one block (its fragments af) for a pair of wide tiles x / y: WORDS
+// MFMAs per tile (TWO false: one tile, dy = dx)
+template <int WORDS, bool TWO>
+__device__ __forceinline__ void pk_product(const v4i (&af)[WORDS], const v4i (&bx)[WORDS],
+                                           const v4i (&by)[WORDS], const v16f& cb, int sb, v16f& dx,
+                                           v16f& dy) {
+    dx = mfma_pk(af[0], bx[0], cb, sb);
+    dy = dx;
+    if constexpr (TWO) dy = mfma_pk(af[0], by[0], cb, sb);
+#pragma unroll
+    for (int w = 1; w < WORDS; ++w) {
+        dx = mfma_pk(af[w], bx[w], dx, sb);
+        if constexpr (TWO) dy = mfma_pk(af[w], by[w], dy, sb);
+    }
+}
+
+// ---- the pair step
+
+// Per wide tile (64 col0) and block (32 col1) the tree gives the block's minimum distance per
+// col0 (both lane halves combined by one v_permlane32_swap per two tiles, as in pair_reduce):
+// comb, and diff = comb - R against the running minimum R (packed, per col0):
+//   block > R: nothing;  block == R: a second column at the running minimum -> duplicate
+//   (tracked as M = min over blocks of (block - R), packed; 0 = tie); block < R: a new
+//   minimum, a strict drop, which resets M. Any block order gives the same result (a tie with
+//   a later-improved minimum is forgotten on the improvement, exactly as the reference's
+//   strict '<' scan would).
+// Lazy drops (round 6). A strict drop of the running minimum used to branch into (distance,
+// row) key trees that found its first row and whether the block holds it twice (the drop
+// branch of search_pk_kernel's pair_step) -- one wave-uniform branch whenever any of the
+// wave's 128 col0 dropped, ~150 VALU; on random descriptors most blocks of a scan take it. A
+// lazy drop only records the block base B in C and clears the tie marker, branch-free, and
+// each col0 rescans its final block once after the scan, from the right row's raw words staged
+// in LDS: 32 popcounts of WORDS words, the first col1 at the minimum and whether it occurs
+// twice (pk_rescan). The plan chooses per shape (PK_LAZY_MIN_COLS, search_plan.hpp).
+__device__ __forceinline__ void lazy_drop(uint32_t& M, uint32_t& R, uint32_t& C, uint32_t comb,
+                                          uint32_t diff, int B) {
+    const uint32_t mi = pksign(diff);
+    M = pkminu(M, diff) | mi;  // a drop: no tie seen since
+    // (bfi(mi, comb, R) as the one v_bitop3_b32 it should be: from bfi()'s and/or form the
+    // compiler rebuilt the per-field select here from two compares, two cndmasks and a v_perm,
+    // and from the xor form it kept a v_xor_b32 beside the v_bitop3_b32 in the 4-tile loops)
+    R = __builtin_amdgcn_bitop3_b32(comb, R, mi, 0xe4);
+    // (one v_bfi_b32 with the block base as an SGPR operand: left alone, the compiler rebuilt
+    // this select the same way)
+    asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(C) : "v"(mi), "s"((uint32_t)B * 0x10001u));
+}
+
+// ---- the end of a row
+
+// a wave's place in its row, as the end of row needs it: image row; lane half, lane within it;
+// first col0 (LIST: entry) of the wave / of the workgroup, the row's count of them; no col0 in
+// this wave (wave-uniform); the row's left / right descriptors
+struct PkWave {
+    int row, h, j, c0_wave, wg_c0, lcols;
+    bool idle;
+    const uint32_t* __restrict__ row0;
+    const uint32_t* __restrict__ row1;
+};
+// bytes of the chunk region ahead of the staged raw right row: the workgroup's int16 results
+__device__ __forceinline__ int pk_row_off(int waves, int T) { return (waves * T * 64 * 2 + 15) & ~15; }
+
+// col0 c's final block (base Bb, minimum distance hm) rescanned by popcounts -- the first col1
+// at hm, and whether it occurs twice there; src = the right row's words, staged or in HBM.
+// (row0 without __restrict__: with it the two calls' loads of the left descriptor differ in
+// their alias scopes, the compiler no longer hoists them above the staged / unstaged branch,
+// and every rescan starts by waiting for its own load: random 32-bit NoDuplicates +1 %)
+template <int WORDS>
+__device__ __forceinline__ void pk_rescan(const uint32_t* src, const uint32_t* row0, int cols,
+                                          int c, int Bb, uint32_t hm, int& best, bool& uniq) {
+    uint32_t aw[WORDS];
+#pragma unroll
+    for (int w = 0; w < WORDS; ++w) aw[w] = row0[(size_t)c * WORDS + w];
+    uint32_t eq = 0;
+#pragma unroll 4
+    for (int r = 0; r < 32; ++r) {
+        const int c1 = Bb + r;
+        const int cc = min(c1, cols - 1);  // (past the row: never counted, read in bounds)
+        uint32_t hsum = 0;
+#pragma unroll
+        for (int w = 0; w < WORDS; ++w) hsum = __popc(aw[w] ^ src[(size_t)cc * WORDS + w]) + hsum;
+        eq |= (c1 < cols && hsum == hm) ? (1u << r) : 0u;
+    }
+    best = Bb + (int)__builtin_ctz(eq | 0x80000000u);
+    uniq = __popc(eq) == 1;
+}
+// the right row's nw raw words into LDS: one coalesced copy per workgroup, L2-resident
+// (WORDS == 4: nw is a multiple of 4 and the tail loop is empty)
+__device__ __forceinline__ void pk_copy_row(uint32_t* row_lds, const uint32_t* __restrict__ row1, int nw) {
+    if ((reinterpret_cast<uintptr_t>(row1) & 15u) == 0) {
+        for (int i = threadIdx.x; i < nw / 4; i += blockDim.x)
+            reinterpret_cast<v4i*>(row_lds)[i] = reinterpret_cast<const v4i*>(row1)[i];
+        for (int i = nw / 4 * 4 + threadIdx.x; i < nw; i += blockDim.x) row_lds[i] = row1[i];
+    } else {
+        for (int i = threadIdx.x; i < nw; i += blockDim.x) row_lds[i] = row1[i];
+    }
+}
+// one col0's result, column c0 of the 32-col0 tile at c0_tile: col1 `best` where ok. The dense-row
+// fast path's valid count of the tile (every lane of the half joins), then the disparity or
+// the column to the output row, or (AG) to the workgroup's results in LDS
+template <bool LIST, bool AG>
+__device__ __forceinline__ void pk_result(const SearchArgs& a, int row, int c0_tile, int c0, bool live,
+                                          bool ok, int best, bool writer, int16_t* raw_lds, int wg_c0) {
+    if constexpr (!LIST && !AG) {
+        if (a.row_valid) tile_valid_store(a, row, c0_tile, live && ok, best, writer);
+    }
+    if (!live) return;
+    int16_t v;
+    if (a.out_mode == 0)
+        v = ok ? (int16_t)(c0 - best) : INVALID_I16;
+    else
+        v = ok ? (int16_t)best : (int16_t)-1;
+    if constexpr (AG)
+        raw_lds[c0 - wg_c0] = v;
+    else
+        (a.out + (size_t)row * a.out_pitch)[c0] = v;
+}
+// AG: the fused agree over the workgroup's wg_cols col0 from wg_c0, whose integer results
+// raw_lds holds (n = 8 with 32-bit descriptors, cfg1; n = 33 with 128-bit, cfg2 / cfg5)
+template <int WORDS, bool AG, class KA>
+__device__ __forceinline__ void pk_agree(const KA& ka, int row, int wg_c0, int wg_cols, const int16_t* raw_lds) {
+    if constexpr (AG) {
+        __syncthreads();
+        fused_agree<WORDS == 1 ? FUSED_AGREE_N_PK : FUSED_AGREE_N>(
+            ka.ag, row, wg_c0, min(wg_cols, search_part(ka).cols - wg_c0), raw_lds);
+    }
+}
+// The end of a row behind the block loops, from the pairs' R, M and C (NP of each). AG: the
+// workgroup's integer results go through LDS to the fused agree (as in search_mx_kernel); the
+// chunk region is reused once every wave is done with its blocks. LAZY: each col0 without a
+// tie since its last drop counts its final block's minima (pk_rescan), from the right row's
+// raw words copied past those results (staged: they fit the chunk region), else from HBM.
+template <int WORDS, int T, bool LIST, bool AG, bool LAZY, class KA, class LCOL>
+__device__ __forceinline__ void pk_end_of_row(const KA& ka, const PkWave& w, v4i* lds_mx, bool staged,
+                                              const uint32_t* R, const uint32_t* M, const uint32_t* C,
+                                              LCOL lcol) {
+    constexpr int NP = T == 1 ? 1 : T / 2;
+    const SearchArgs& a = search_part(ka);
+    const int cols = a.cols;
+    const int waves = blockDim.x >> 6;
+    int16_t* raw_lds = reinterpret_cast<int16_t*>(lds_mx);
+    uint32_t* row_lds = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds_mx) + pk_row_off(waves, T));
+    if (!AG && !staged && w.idle) return;
+    if (AG || staged) __syncthreads();
+    if (staged) {
+        pk_copy_row(row_lds, w.row1, cols * WORDS);
+        __syncthreads();
+        if (!AG && w.idle) return;
+    }
+    int jo = w.j;
+    asm volatile("" : "+v"(jo));
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        if (T == 1 && w.h) continue;  // one tile: lanes 0-31 hold it
+        const int t = T == 1 ? 0 : 2 * p + w.h;
+#pragma unroll
+        for (int f = 0; f < 2; ++f) {  // f = 0: high field (col0 P), 1: low field (Q = P + 32)
+            const int c0i = w.c0_wave + 64 * t + 32 * f + jo;
+            const int sh = f ? 0 : 16;
+            const bool live = !w.idle && c0i < w.lcols;
+            int best = (int)((C[p] >> sh) & 0xFFFFu);
+            bool ok = ((M[p] >> sh) & 0xFFFFu) != 0u;
+            if constexpr (LAZY) {
+                if (live && ok) {
+                    const uint32_t hm = ((R[p] >> sh) & 0xFFFFu) - 0x4B00u;
+                    if (staged)
+                        pk_rescan<WORDS>(row_lds, w.row0, cols, lcol(c0i), best, hm, best, ok);
+                    else
+                        pk_rescan<WORDS>(w.row1, w.row0, cols, lcol(c0i), best, hm, best, ok);
+                }
+            }
+            pk_result<LIST, AG>(a, w.row, w.c0_wave + 64 * t + 32 * f, live ? lcol(c0i) : 0, live, ok, best,
+                                jo == 0, raw_lds, w.wg_c0);
+        }
+    }
+    pk_agree<WORDS, AG>(ka, w.row, w.wg_c0, waves * T * 64, raw_lds);
 }
 
 // T wide tiles (64 col0 each) per wave; T = 1 or an even count (tiles reduced in pairs);
 // TAIL: the col0 range starts at a.tail_col0 (the tail launch, as search_mx_kernel's);
-// LIST: compacted col0 entries (as search_mx_kernel's)
-template <int WORDS, int T, bool TAIL, bool LIST, bool AG = false, bool LAZY = PK_LAZY>
+// LIST: compacted col0 entries (as search_mx_kernel's); LAZY: lazy drops (lazy_drop)
+template <int WORDS, int T, bool TAIL, bool LIST, bool AG, bool LAZY>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
 void search_pk_kernel(typename SearchKArgs<AG>::type ka) {
     const SearchArgs& a = search_part(ka);
@@ -243,24 +388,10 @@ void search_pk_kernel(typename SearchKArgs<AG>::type ka) {
     const uint32_t* __restrict__ row0 = a.desc0 + (size_t)row * a.desc_pitch;
     const uint32_t* __restrict__ row1 = a.desc1 + (size_t)row * a.desc_pitch;
 
-    // B fragments: wide tile t, word w; this lane's col0 is c0_wave + 64 t + lane (K-half h:
-    // P = lanes 0-31, Q = lanes 32-63)
     v4i bf[T][WORDS];
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        const int c0 = c0_wave + 64 * t + lane;
-        const int cl = c0 < lcols ? lcol(c0) : 0;
-#pragma unroll
-        for (int w = 0; w < WORDS; ++w) {
-            const uint32_t x = c0 < lcols ? row0[(size_t)cl * WORDS + w] : 0u;
-            bf[t][w] = expand_bits(x, LUT_PB);
-        }
-    }
+    pk_bfrags<WORDS, T>(bf, row0, c0_wave, lane, lcols, lcol);
     const int sb = h ? 127 : PK_SCALE_HI;
-    constexpr float CBIAS = 8388608.f + 65536.f * (16 * WORDS) + (float)(0x4B00 + 16 * WORDS);
-    v16f cb;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cb[r] = CBIAS;
+    v16f cb = pk_cb<WORDS>();
 
     // per pair p (lanes 0-31: tile 2p, lanes 32-63: tile 2p+1; T = 1: all lanes tile 0):
     // running minimum, tie marker, first column of the minimum
@@ -271,9 +402,8 @@ void search_pk_kernel(typename SearchKArgs<AG>::type ka) {
         M[p] = 0xFFFFFFFFu;
         C[p] = 0u;
     }
-    auto rrow = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
 
-    // one pair's block minima x (tile 2p) / y (tile 2p+1) at block base B
+    // one pair's block minima x (tile 2p) / y (tile 2p+1) at block base B (see lazy_drop)
     auto pair_step = [&](int p, int B, const v16f& dx, const v16f& dy) {
         const uint32_t x = pk_tree(dx);
         const uint32_t y = T == 1 ? x : pk_tree(dy);
@@ -281,23 +411,15 @@ void search_pk_kernel(typename SearchKArgs<AG>::type ka) {
         const uint32_t comb = pkminu(sw[0], sw[1]);
         const uint32_t diff = pksub(comb, R[p]);
         if constexpr (LAZY) {
-            // a strict drop only records the block (branch-free); its first row and whether
-            // it holds the minimum twice are found once, after the scan (pk_rescan)
-            const uint32_t mi = pksign(diff);
-            M[p] = pkminu(M[p], diff) | mi;  // a drop: no tie seen since
-            R[p] = bfi(mi, comb, R[p]);
-            // (one v_bfi_b32 with the block base as an SGPR operand: left alone, the compiler
-            // rebuilt the per-field select from two compares, two cndmasks and a v_perm)
-            uint32_t c = C[p];
-            asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(c) : "v"(mi), "s"((uint32_t)B * 0x10001u));
-            C[p] = c;
+            lazy_drop(M[p], R[p], C[p], comb, diff, B);
             return;
         }
         M[p] = pkminu(M[p], diff);
         const bool imp = (diff & 0x80008000u) != 0u;
         if (__builtin_amdgcn_ballot_w64(imp)) {
             // a new running minimum somewhere in the pair: per (tile, distance field) that
-            // holds one, the first row at it and whether the block holds it twice
+            // holds one, the first row at it and whether the block holds it twice ((distance,
+            // row) keys through v_perm + v_pk_min_u16, first and reversed rows)
             const uint32_t mi = pksign(diff);
             const uint32_t hoff = h ? 0xFFFC0004u : 0u;  // rows + 4h (low), 31 - rows - 4h (high)
             auto field = [&](auto sel_tag, uint32_t top, int sh) {
@@ -362,22 +484,9 @@ void search_pk_kernel(typename SearchKArgs<AG>::type ka) {
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
                 const int tx = T == 1 ? 0 : 2 * p, ty = T == 1 ? 0 : 2 * p + 1;
-                v16f dx = mfma_pk(af[0], bf[tx][0], cb, sb);
-                v16f dy = dx;
-                if constexpr (T != 1) dy = mfma_pk(af[0], bf[ty][0], cb, sb);
-#pragma unroll
-                for (int w = 1; w < WORDS; ++w) {
-                    dx = mfma_pk(af[w], bf[tx][w], dx, sb);
-                    if constexpr (T != 1) dy = mfma_pk(af[w], bf[ty][w], dy, sb);
-                }
-                if (pad) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const bool in = 32 * b + rrow(r) < ncols;
-                        dx[r] = in ? dx[r] : bitsf(PK_PAD);
-                        dy[r] = in ? dy[r] : bitsf(PK_PAD);
-                    }
-                }
+                v16f dx, dy;
+                pk_product<WORDS, T != 1>(af, bf[tx], bf[ty], cb, sb, dx, dy);
+                if (pad) pk_pad(dx, dy, b, ncols, h);
                 pair_step(p, B, dx, dy);
             }
         };
@@ -389,102 +498,53 @@ void search_pk_kernel(typename SearchKArgs<AG>::type ka) {
             block(b, false);
         }
     }
-    // AG: the workgroup's integer results go through LDS to the fused agree (as in
-    // search_mx_kernel); the chunk region is reused once every wave is done with its blocks.
-    // PK_LAZY: the right row's raw words are staged past those results when they fit (one
-    // coalesced copy per workgroup, L2-resident), for the rescans below; else read from HBM.
-    int16_t* raw_lds = reinterpret_cast<int16_t*>(lds_mx);
-    const int wg_c0 = c0_base + tile * waves * T * 64;
-    const int row_off = (waves * T * 64 * 2 + 15) & ~15;  // bytes: past raw_lds
-    const bool staged = LAZY && (size_t)WORDS * chunk * 16 >= (size_t)row_off + (size_t)cols * WORDS * 4;
-    if (!AG && !staged && idle) return;
-    if (AG || staged) __syncthreads();
-    uint32_t* row_lds = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds_mx) + row_off);
-    if (staged) {
-        const int nw = cols * WORDS;
-        if ((reinterpret_cast<uintptr_t>(row1) & 15u) == 0) {
-            for (int i = threadIdx.x; i < nw / 4; i += blockDim.x)
-                reinterpret_cast<v4i*>(row_lds)[i] = reinterpret_cast<const v4i*>(row1)[i];
-            for (int i = nw / 4 * 4 + threadIdx.x; i < nw; i += blockDim.x) row_lds[i] = row1[i];
-        } else {
-            for (int i = threadIdx.x; i < nw; i += blockDim.x) row_lds[i] = row1[i];
-        }
+    const bool staged =
+        LAZY && (size_t)WORDS * chunk * 16 >= (size_t)pk_row_off(waves, T) + (size_t)cols * WORDS * 4;
+    if constexpr (AG && WORDS == 4 && T == 1) {
+        // pk_end_of_row written out for the fused one-tile 128-bit instantiations (BICOS_PK128,
+        // narrow bands): through the function the same statements leave fused_agree scheduled
+        // with more loads in flight, next_free_vgpr 96 -> 104 (branch) and 83 -> 102 (lazy),
+        // 5 -> 4 waves per SIMD by the compiler's count
+        int16_t* raw_lds = reinterpret_cast<int16_t*>(lds_mx);
+        uint32_t* row_lds = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds_mx) + pk_row_off(waves, T));
         __syncthreads();
-        if (!AG && idle) return;
-    }
-    // PK_LAZY: col0 c's final block (base Bb, minimum distance hm) rescanned by popcounts --
-    // the first col1 at hm, and whether it occurs twice there; src = the right row's words
-    auto rescan = [&](const uint32_t* src, int c, int Bb, uint32_t hm, int& best, bool& uniq) {
-        uint32_t aw[WORDS];
-#pragma unroll
-        for (int w = 0; w < WORDS; ++w) aw[w] = row0[(size_t)c * WORDS + w];
-        uint32_t eq = 0;
-#pragma unroll 4
-        for (int r = 0; r < 32; ++r) {
-            const int c1 = Bb + r;
-            const int cc = min(c1, cols - 1);  // (past the row: never counted, read in bounds)
-            uint32_t hsum = 0;
-#pragma unroll
-            for (int w = 0; w < WORDS; ++w) hsum = __popc(aw[w] ^ src[(size_t)cc * WORDS + w]) + hsum;
-            eq |= (c1 < cols && hsum == hm) ? (1u << r) : 0u;
+        if (staged) {
+            pk_copy_row(row_lds, row1, cols * WORDS);
+            __syncthreads();
         }
-        best = Bb + (int)__builtin_ctz(eq | 0x80000000u);
-        uniq = __popc(eq) == 1;
-    };
-
-    int16_t* out = a.out + (size_t)row * a.out_pitch;
-    int jo = j;
-    asm volatile("" : "+v"(jo));
+        int jo = j;
+        asm volatile("" : "+v"(jo));
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        if (T == 1 && h) continue;  // one tile: lanes 0-31 hold it
-        const int t = T == 1 ? 0 : 2 * p + h;
-#pragma unroll
-        for (int f = 0; f < 2; ++f) {  // f = 0: high field (col0 P), 1: low field (Q = P + 32)
-            const int c0i = c0_wave + 64 * t + 32 * f + jo;
+        for (int f = 0; f < 2; ++f) {  // lanes 0-31 hold the tile; f as in pk_end_of_row
+            if (h) continue;
+            const int c0 = c0_wave + 32 * f + jo;
             const int sh = f ? 0 : 16;
-            const bool live = !idle && c0i < lcols;
-            int best = (int)((C[p] >> sh) & 0xFFFFu);
-            bool ok = ((M[p] >> sh) & 0xFFFFu) != 0u;
+            const bool live = !idle && c0 < lcols;
+            int best = (int)((C[0] >> sh) & 0xFFFFu);
+            bool ok = ((M[0] >> sh) & 0xFFFFu) != 0u;
             if constexpr (LAZY) {
-                // no tie in another block since the drop: count the final block's minima
                 if (live && ok) {
-                    const uint32_t hm = ((R[p] >> sh) & 0xFFFFu) - 0x4B00u;
+                    const uint32_t hm = ((R[0] >> sh) & 0xFFFFu) - 0x4B00u;
                     if (staged)
-                        rescan(row_lds, lcol(c0i), best, hm, best, ok);
+                        pk_rescan<WORDS>(row_lds, row0, cols, c0, best, hm, best, ok);
                     else
-                        rescan(row1, lcol(c0i), best, hm, best, ok);
+                        pk_rescan<WORDS>(row1, row0, cols, c0, best, hm, best, ok);
                 }
             }
-            if constexpr (!LIST && !AG) {  // dense-row fast path: this tile's valid count
-                if (a.row_valid)
-                    tile_valid_store(a, row, c0_wave + 64 * t + 32 * f, live && ok, best, jo == 0);
-            }
-            if (!live) continue;
-            const int c0 = lcol(c0i);
-            int16_t v;
-            if (a.out_mode == 0)
-                v = ok ? (int16_t)(c0 - best) : INVALID_I16;
-            else
-                v = ok ? (int16_t)best : (int16_t)-1;
-            if constexpr (AG)
-                raw_lds[c0 - wg_c0] = v;
-            else
-                out[c0] = v;
+            pk_result<LIST, AG>(a, row, c0_wave + 32 * f, c0, live, ok, best, jo == 0, raw_lds, e0);
         }
-    }
-    if constexpr (AG) {
-        __syncthreads();
-        // (n = 8 with 32-bit descriptors, cfg1; n = 33 with 128-bit, cfg2 / cfg5)
-        fused_agree<WORDS == 1 ? FUSED_AGREE_N_PK : FUSED_AGREE_N>(
-            ka.ag, row, wg_c0, min(waves * T * 64, cols - wg_c0), raw_lds);
+        pk_agree<WORDS, AG>(ka, row, e0, waves * T * 64, raw_lds);
+    } else {
+        const PkWave pw{row, h, j, c0_wave, e0, lcols, idle, row0, row1};
+        pk_end_of_row<WORDS, T, LIST, AG, LAZY>(ka, pw, lds_mx, staged, R, M, C, lcol);
     }
 }
 
-// The pruned 128-bit search (see the header): WORDS = 4, one pair of wide tiles per wave, lazy
-// drops, every col0 of the row (no tail, no list); ST: the right row streamed. Prologue, pair
-// step, rescans and epilogue are search_pk_kernel<4, 2, false, false, AG, true>'s; EOR: the
-// drop's lane half recorded, 16-row two-level rescans, early end-of-row loads (see the header).
+// The pruned 128-bit search: WORDS = 4, one pair of wide tiles per wave, lazy drops, every
+// col0 of the row (no tail, no list), main launches only; words 2 and 3 only where they can
+// matter (block_pr). ST: the right row streamed (raw_col); EOR: a shorter end of row
+// (pair_update, and the end of the kernel). Prologue, lazy step and, without EOR, the end of
+// row are search_pk_kernel<4, 2, false, false, AG, true>'s.
 template <bool AG, bool ST, bool EOR>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
 void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
@@ -500,6 +560,11 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     const int h = lane >> 5;
     const int j = lane & 31;
     const int cols = a.cols;
+    // ST: the chunk is PKP_ST_CHUNK (search_plan.hpp: the default geometry's, 8 waves over a 64
+    // KiB stage), a constant of those instantiations so that a block's words 1-3 are read at
+    // immediate offsets (16, 32, 48 KiB: the ds_read offset field has 16 bits) from the address
+    // of its word-0 fragment. plan_mx (search_plan.cpp) streams the packed search at that
+    // geometry only; launch_pk_variant refuses a streamed launch with any other.
     const int chunk = ST ? PKP_ST_CHUNK : a.chunk;
     const int waves = blockDim.x >> 6;
     const int c0_wave = (tile * waves + wave) * (T * 64);
@@ -507,17 +572,26 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     const uint32_t* __restrict__ row0 = a.desc0 + (size_t)row * a.desc_pitch;
     const uint32_t* __restrict__ row1 = a.desc1 + (size_t)row * a.desc_pitch;
 
-    // the fragment of word w of the block whose word-0 fragment this lane reads at LDS address
-    // ad (ST: at an immediate offset). LDS addresses as integers, lds0 the chunk region's: with
-    // the region's pointer in the sum the compiler adds its address, 0, to ad at every read.
+    // The block loops name a block by the LDS address of the lane's word-0 fragment of it and
+    // step that address by a scalar delta (-512 bytes, or back up to the step's last full block
+    // at the wrap); words 1-3 lie 16 chunk bytes apart. frag: the fragment of word w of the
+    // block whose word-0 fragment this lane reads at LDS address ad (ST: at an immediate
+    // offset). LDS addresses as integers, lds0 the chunk region's: with the region's pointer in
+    // the sum the compiler adds its address, 0, to ad at every read.
     typedef const __attribute__((address_space(3))) v4i* lds_frag_ptr;
     const uint32_t lds0 = (uint32_t) reinterpret_cast<uintptr_t>((lds_frag_ptr)lds_mx);
     auto frag = [&](uint32_t ad, int w) {
         return *reinterpret_cast<lds_frag_ptr>(ad + (uint32_t)(w * chunk * 16));
     };
 
-    // ST: the raw right descriptor of col1 (zero past the image), and the own chunk's two
-    // columns of this thread, requested ahead of the B-fragment loads below
+    // ST (the plan guarantees chunk = 2 * blockDim.x = PKP_ST_CHUNK and cols > chunk -- a tuned
+    // geometry with another chunk takes the chunk loop): the right row streamed exactly as
+    // search_mx_kernel ST does -- the workgroup's own chunk expanded whole, the rest of the row
+    // in stages of half a chunk alternating between the two halves of the chunk region, the
+    // next stage's raw descriptor held in four VGPRs across the block loop, one barrier per
+    // stage. Same LDS layout; only the expansion table differs.
+    // raw_col: the raw right descriptor of col1 (zero past the image); the own chunk's two
+    // columns of this thread are requested ahead of the B-fragment loads below
     auto raw_col = [&](int c1) {
         v4i x = {0, 0, 0, 0};
         if (c1 < cols) {
@@ -540,22 +614,10 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         raw_hi = raw_col(cstart * chunk + half + (int)threadIdx.x);
     }
 
-    // B fragments: wide tile t, word w; this lane's col0 is c0_wave + 64 t + lane
     v4i bf[T][WORDS];
-#pragma unroll
-    for (int t = 0; t < T; ++t) {
-        const int c0 = c0_wave + 64 * t + lane;
-#pragma unroll
-        for (int w = 0; w < WORDS; ++w) {
-            const uint32_t x = c0 < cols ? row0[(size_t)c0 * WORDS + w] : 0u;
-            bf[t][w] = expand_bits(x, LUT_PB);
-        }
-    }
+    pk_bfrags<WORDS, T>(bf, row0, c0_wave, lane, cols, [](int i) { return i; });
     const int sb = h ? 127 : PK_SCALE_HI;
-    constexpr float CBIAS = 8388608.f + 65536.f * (16 * WORDS) + (float)(0x4B00 + 16 * WORDS);
-    v16f cb;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cb[r] = CBIAS;
+    v16f cb = pk_cb<WORDS>();
 
     // lanes 0-31: tile 0, lanes 32-63: tile 1 -- running minimum, tie marker, block base of
     // the last drop; the reach test's threshold R + 33 per field; the fallback's state
@@ -564,19 +626,28 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     uint32_t thr = PK_PAD + PKP_THR;
     bool prune_on = true;
     int wblocks = 0, wreach = 0;
-    auto rrow = [&](int r) { return (r & 3) + 8 * (r >> 2) + 4 * h; };
 
     // the lazy pair step from the two trees' results x (tile 0) / y (tile 1) in this lane half
-    // at block base B (a pruned tile passes its partial one); renews thr
+    // at block base B (a pruned tile passes its partial one); renews thr.
+    // EOR: a lazy drop also records WHICH LANE HALF of the block holds the new minimum. sw[0] /
+    // sw[1] are the block minima of the lane's tile over the rows of lane half 0 / 1 (pk_rrow).
+    // On a strict drop of a field:
+    //   sw[0] != sw[1]: every column of the block at the new minimum lies in the half with the
+    //     smaller value; bit 15 of the field of C (block bases stay below 2^15) takes the sign of
+    //     sw[1] - sw[0], and M takes sw[0] ^ sw[1], some value != 0: "no tie seen since".
+    //   sw[0] == sw[1]: the block holds the new minimum in two rows of different halves, that is
+    //     in two different columns -- exactly what a tie in a later block would have meant. M
+    //     takes sw[0] ^ sw[1] = 0, the tie marker, and no rescan is needed for this col0.
+    // (Why that is exact: at the EOR end of row below.)
     auto pair_update = [&](int B, uint32_t x, uint32_t y) {
         const auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);
         const uint32_t comb = pkminu(sw[0], sw[1]);
         const uint32_t diff = pksub(comb, R);
-        const uint32_t mi = pksign(diff);
         if constexpr (EOR) {
+            const uint32_t mi = pksign(diff);
             // a drop: the tie marker restarts from the two halves' minima (0: the block holds
             // the new minimum in both), and bit 15 of C's field says which half holds it
-            // (v_bfi_b32 by hand, as below: left alone the compiler selects per field)
+            // (v_bfi_b32 by hand, as in lazy_drop: left alone the compiler selects per field)
             uint32_t m = pkminu(M, diff);
             asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(m) : "v"(mi), "v"(sw[0] ^ sw[1]));
             M = m;
@@ -585,9 +656,7 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
             asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(bh) : "v"(0x7FFF7FFFu), "s"((uint32_t)B * 0x10001u));
             asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(C) : "v"(mi), "v"(bh));
         } else {
-            M = pkminu(M, diff) | mi;  // a drop: no tie seen since
-            R = bfi(mi, comb, R);
-            asm("v_bfi_b32 %0, %1, %2, %0" : "+v"(C) : "v"(mi), "s"((uint32_t)B * 0x10001u));
+            lazy_drop(M, R, C, comb, diff, B);
         }
         thr = R + PKP_THR;
     };
@@ -647,28 +716,35 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
             v4i af[WORDS];
 #pragma unroll
             for (int w = 0; w < WORDS; ++w) af[w] = frag(ad, w);
-            v16f dx = mfma_pk(af[0], bf[0][0], cb, sb);
-            v16f dy = mfma_pk(af[0], bf[1][0], cb, sb);
-#pragma unroll
-            for (int w = 1; w < WORDS; ++w) {
-                dx = mfma_pk(af[w], bf[0][w], dx, sb);
-                dy = mfma_pk(af[w], bf[1][w], dy, sb);
-            }
-            if (pad) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const bool in = 32 * bi + rrow(r) < ncols;
-                    dx[r] = in ? dx[r] : bitsf(PK_PAD);
-                    dy[r] = in ? dy[r] : bitsf(PK_PAD);
-                }
-            }
+            v16f dx, dy;
+            pk_product<WORDS, true>(af, bf[0], bf[1], cb, sb, dx, dy);
+            if (pad) pk_pad(dx, dy, bi, ncols, h);
             pair_update(B, pk_tree(dx), pk_tree(dy));
         };
-        // a full block, at col1 B, with words 2 and 3 only for the wide tiles that can reach
-        // (see the header). af0 holds the block's word-0 fragment on entry and the next
-        // block's on return, read once the probe products are issued; the other words'
-        // fragments are read here, at the top of the block, and ad then steps by d bytes to the
-        // next block. Counts the reaching wide tiles into wreach.
+        // A full block, at col1 B, with words 2 and 3 only for the wide tiles that can reach.
+        // After the MFMAs of words 0 and 1 both fields of every accumulator hold 0x4B00 + 32 +
+        // ham_lo (C carries + 64, each word adds ham_w - 16), and the final field is 0x4B00 +
+        // ham with ham >= ham_lo. The packed tree of these partial keys, combined over the lane
+        // halves as in the pair step, is tested per field against thr = R + 0x00210021 as
+        // UNSIGNED 16-BIT INTEGERS (not f16: PK_PAD + 0x21 is a NaN pattern) by one saturating
+        // subtraction, thr - key != 0 (v_pk_sub_u16 clamp; neither field of thr wraps: R <=
+        // 0x7BFF): reach is ham_lo <= running minimum, "<=" because a tie must never be pruned
+        // (NoDuplicates needs it). The decision is per wide tile (the ballot's halves): a tile
+        // none of whose 64 col0 reaches skips its MFMAs of words 2 and 3 and its tree; it
+        // enters the pair step, if the other tile takes one, with its partial keys. That is
+        // safe under lazy drops: a pruned tile-block has block minimum > R for every col0, and
+        // R only falls, so the block is neither a drop nor a tie now or later; its partial keys
+        // lie above R too, so all they can give M is a positive value, which never decides
+        // anything -- `ok` tests M == 0 only, and a later drop resets M. thr is renewed only
+        // where R may have changed. The partial last block never prunes. Fallback as
+        // search_mx_kernel's: over windows of PRUNE_WINDOW visited blocks a wave counts its
+        // reaching wide-tile-blocks (wreach) from the branch's own ballots; >= 7/8 of them (14
+        // of 16) send it to the unpruned loop for the rest of the row. (Lazy drops stay under
+        // pruning: with the drop branch in the reaching blocks instead of the rescans the fused
+        // cfg2 launch took 313.8 instead of 276.2 us.)
+        // af0 holds the block's word-0 fragment on entry and the next block's on return, read
+        // once the probe products are issued; the other words' fragments are read here, at the
+        // top of the block, and ad then steps by d bytes to the next block.
         auto block_pr = [&](int B, uint32_t& ad, v4i& af0, int d) {
             asm volatile("" : "+v"(cb));
             const v4i af1 = frag(ad, 1);
@@ -759,21 +835,29 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     // The workgroup's integer results (AG) and the right row's raw words for the rescans go
     // into the chunk region once every wave is done with its blocks (the plan guarantees that
     // the row fits: packed_search, search_plan.cpp)
-    int16_t* raw_lds = reinterpret_cast<int16_t*>(lds_mx);
     const int wg_c0 = tile * waves * T * 64;
-    const int row_off = (waves * T * 64 * 2 + 15) & ~15;  // bytes: past raw_lds
-    uint32_t* row_lds = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds_mx) + row_off);
     if constexpr (EOR) {
-        int16_t* out = a.out + (size_t)row * a.out_pitch;
+        // EOR: a shorter end of row, from the lane half that pair_update recorded with every
+        // drop. Why that is exact: R ends as the row's minimum distance hm, and reaches it by a
+        // strict drop in the first visited block whose minimum is hm; C holds that block and
+        // half. If M ends 0, either a later block had minimum hm too (as without EOR) or both
+        // halves of C's block did: a second column at hm either way, invalid. A later strict
+        // drop overwrites M and C as a whole, so a duplicate of a minimum that was improved on
+        // is forgotten, as before. If M ends != 0, every column at hm lies in the recorded half
+        // of C's block, and the rescan of its 16 rows counts them and finds the first: the same
+        // answer as the rescan of all 32. A pruned tile's partial keys lie above R in every
+        // field, so they never take the drop's side of any of this.
+        int16_t* raw_lds = reinterpret_cast<int16_t*>(lds_mx);
+        uint32_t* row_lds = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lds_mx) + pk_row_off(waves, T));
         // The raw row's first EARLY * blockDim columns (one dwordx4 each) and this lane's two
         // left descriptors are requested here, behind the wave's own last block; they arrive
-        // while the barrier waits for the workgroup's slowest wave. (k * blockDim < cols is
-        // workgroup-uniform: a scalar branch around each load, none waits for another.)
+        // while the barrier waits for the workgroup's slowest wave, and the row is written to
+        // LDS behind it. (k * blockDim < cols is workgroup-uniform: a scalar branch around each
+        // load, none waits for another.)
         constexpr int EARLY = 8;
         const bool al16 = (reinterpret_cast<uintptr_t>(row1) & 15u) == 0;
         const int bd = (int)blockDim.x;
         v4i early[EARLY];
-        if constexpr (!PKP_EARLY) __syncthreads();
         if (al16) {
 #pragma unroll
             for (int k = 0; k < EARLY; ++k) {
@@ -789,7 +873,7 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
 #pragma unroll
             for (int w = 0; w < WORDS; ++w) aw[f][w] = (int)row0[(size_t)c * WORDS + w];
         }
-        if constexpr (PKP_EARLY) __syncthreads();
+        __syncthreads();
         if (al16) {
 #pragma unroll
             for (int k = 0; k < EARLY; ++k) {
@@ -805,10 +889,12 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         if (!AG && idle) return;
 
         // col0's final block rescanned in the recorded half only (16 rows from col1 B0 = block
-        // base + 4 half, at (k & 3) + 8 (k >> 2)), in two levels: ham_lo of the 16 rows, then
-        // the full distance of the rows with ham_lo <= hm. Masks are indexed by the row's
-        // offset from B0. CLAMP: the block may reach past the row (the partial last block) --
-        // those rows are read in bounds and never counted.
+        // base + 4 half, at (k & 3) + 8 (k >> 2)), in two levels: ham_lo (words 0 and 1) of the
+        // 16 rows against hm, then the full distance of the candidates only (ham >= ham_lo, so
+        // a column at hm is always a candidate), one per lane and trip of a loop that runs the
+        // wave's largest candidate count. Masks are indexed by the row's offset from B0. CLAMP:
+        // the block may reach past the row (the partial last block) -- those rows are read in
+        // bounds and never counted.
         auto rescan = [&](auto clamp_tag, const v4i& x, int B0, uint32_t hm, int& best, bool& uniq) {
             constexpr bool CLAMP = decltype(clamp_tag)::value;
             uint32_t cand = 0;
@@ -867,87 +953,12 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
                 else
                     rescan(std::false_type{}, aw[f], B0, hm, best, ok);
             }
-            if constexpr (!AG) {  // dense-row fast path: this tile's valid count
-                if (a.row_valid) tile_valid_store(a, row, c0_wave + 64 * h + 32 * f, live && ok, best, jo == 0);
-            }
-            if (!live) continue;
-            int16_t v;
-            if (a.out_mode == 0)
-                v = ok ? (int16_t)(c0 - best) : INVALID_I16;
-            else
-                v = ok ? (int16_t)best : (int16_t)-1;
-            if constexpr (AG)
-                raw_lds[c0 - wg_c0] = v;
-            else
-                out[c0] = v;
+            pk_result<false, AG>(a, row, c0_wave + 64 * h + 32 * f, c0, live, ok, best, jo == 0, raw_lds, wg_c0);
         }
-        if constexpr (AG) {
-            __syncthreads();
-            fused_agree<FUSED_AGREE_N>(ka.ag, row, wg_c0, min(waves * T * 64, cols - wg_c0), raw_lds);
-        }
-        return;
-    }
-    __syncthreads();
-    {
-        const int nw = cols * WORDS;
-        if ((reinterpret_cast<uintptr_t>(row1) & 15u) == 0) {
-            for (int i = threadIdx.x; i < nw / 4; i += blockDim.x)
-                reinterpret_cast<v4i*>(row_lds)[i] = reinterpret_cast<const v4i*>(row1)[i];
-        } else {
-            for (int i = threadIdx.x; i < nw; i += blockDim.x) row_lds[i] = row1[i];
-        }
-        __syncthreads();
-        if (!AG && idle) return;
-    }
-    // col0 c's final block (base Bb, minimum distance hm) rescanned by popcounts: the first
-    // col1 at hm, and whether it occurs twice there (as search_pk_kernel's rescan)
-    auto rescan = [&](int c, int Bb, uint32_t hm, int& best, bool& uniq) {
-        uint32_t aw[WORDS];
-#pragma unroll
-        for (int w = 0; w < WORDS; ++w) aw[w] = row0[(size_t)c * WORDS + w];
-        uint32_t eq = 0;
-#pragma unroll 4
-        for (int r = 0; r < 32; ++r) {
-            const int c1 = Bb + r;
-            const int cc = min(c1, cols - 1);  // (past the row: never counted, read in bounds)
-            uint32_t hsum = 0;
-#pragma unroll
-            for (int w = 0; w < WORDS; ++w) hsum = __popc(aw[w] ^ row_lds[(size_t)cc * WORDS + w]) + hsum;
-            eq |= (c1 < cols && hsum == hm) ? (1u << r) : 0u;
-        }
-        best = Bb + (int)__builtin_ctz(eq | 0x80000000u);
-        uniq = __popc(eq) == 1;
-    };
-
-    int16_t* out = a.out + (size_t)row * a.out_pitch;
-    int jo = j;
-    asm volatile("" : "+v"(jo));
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {  // f = 0: high field (col0 P), 1: low field (Q = P + 32)
-        const int c0 = c0_wave + 64 * h + 32 * f + jo;
-        const int sh = f ? 0 : 16;
-        const bool live = !idle && c0 < cols;
-        int best = (int)((C >> sh) & 0xFFFFu);
-        bool ok = ((M >> sh) & 0xFFFFu) != 0u;
-        // no tie in another block since the drop: count the final block's minima
-        if (live && ok) rescan(c0, best, ((R >> sh) & 0xFFFFu) - 0x4B00u, best, ok);
-        if constexpr (!AG) {  // dense-row fast path: this tile's valid count
-            if (a.row_valid) tile_valid_store(a, row, c0_wave + 64 * h + 32 * f, live && ok, best, jo == 0);
-        }
-        if (!live) continue;
-        int16_t v;
-        if (a.out_mode == 0)
-            v = ok ? (int16_t)(c0 - best) : INVALID_I16;
-        else
-            v = ok ? (int16_t)best : (int16_t)-1;
-        if constexpr (AG)
-            raw_lds[c0 - wg_c0] = v;
-        else
-            out[c0] = v;
-    }
-    if constexpr (AG) {
-        __syncthreads();
-        fused_agree<FUSED_AGREE_N>(ka.ag, row, wg_c0, min(waves * T * 64, cols - wg_c0), raw_lds);
+        pk_agree<WORDS, AG>(ka, row, wg_c0, waves * T * 64, raw_lds);
+    } else {
+        const PkWave pw{row, h, j, c0_wave, wg_c0, cols, idle, row0, row1};
+        pk_end_of_row<WORDS, T, false, AG, true>(ka, pw, lds_mx, true, &R, &M, &C, [](int i) { return i; });
     }
 }
 
@@ -970,7 +981,6 @@ bool pkp_eor() {
 hipError_t launch_pk_variant(const SearchLaunch& l, const SearchArgs& a, const AgreeArgs* ag,
                              hipStream_t st) {
     const SearchVariant& v = l.v;
-    if (!PK_LAZY && v.lazy) return hipErrorInvalidValue;
     if (v.prune || v.stream) {  // search_pkp_kernel: the pruned 128-bit lazy search, streamed or not
         if (!v.prune || !v.lazy || v.words != 4 || v.T != 2 || v.tail || v.list) return hipErrorInvalidValue;
         // (the streamed instantiations are built for one chunk: two columns per thread)
@@ -989,7 +999,7 @@ hipError_t launch_pk_variant(const SearchLaunch& l, const SearchArgs& a, const A
     return pick<bool, false, true>(v.tail, [&](auto tail) {
     return pick<bool, false, true>(v.list, [&](auto list) {
     return pick<bool, false, true>(v.agree, [&](auto agree) {
-    return pick<bool, false, PK_LAZY>(v.lazy, [&](auto lazy) {
+    return pick<bool, false, true>(v.lazy, [&](auto lazy) {
         constexpr int W = words.value, TW = T.value;
         constexpr bool built = agree.value ? !tail.value && !list.value && (W == 1 ? TW == 1 : W == 4 && TW <= 2)
                                : tail.value ? TW == 1 : TW <= 2 || W <= 2;

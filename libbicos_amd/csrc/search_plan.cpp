@@ -35,7 +35,7 @@ bool mx_streamable(int cols, int chunk, int waves, bool stream) {
 // behind the workgroup's results for the lazy rescans (8 waves: 3968 columns). The geometry
 // is the one-product kernel's: the same workgroups, threads, chunk and LDS bytes.
 bool packed_search(const MxGeometry& g, const SearchVariant& v, int cols) {
-    if (!PK_LAZY || !g.packed || !v.prune || v.T != 4 || v.words != 4 || v.keys != 2 || v.list) return false;
+    if (!g.packed || !v.prune || v.T != 4 || v.words != 4 || v.keys != 2 || v.list) return false;
     const long row_off = (64L * g.waves * v.T + 15) & ~15L;  // the results: int16 per col0
     return (long)g.chunk * v.words * 16 >= row_off + (long)cols * v.words * 4;
 }
@@ -111,7 +111,7 @@ SearchLaunchPlan plan_pk(const SearchArgs& a, const MxGeometry& g, int words, bo
     v.T = T;
     v.list = a.keep != nullptr;
     v.agree = agree;
-    v.lazy = PK_LAZY && a.cols >= PK_LAZY_MIN_COLS;
+    v.lazy = a.cols >= PK_LAZY_MIN_COLS;
     SearchLaunchPlan p;
     p.launch[p.n++] = make_launch(v, a.rows, g.waves, 64, words, g.pk_chunk, g.pk_tiles_per_row,
                                   agree ? a.cols : g.pk_tail_col0, 0);
@@ -247,7 +247,7 @@ MxGeometry search_mx_geometry(int rows, int cols, int words, int lds_bytes, int 
         const char* v = std::getenv("BICOS_PK128");
         return v && !std::strcmp(v, "1");
     }();
-    g.pk = (keys == 4 || (keys == 0 && (words <= 2 || (words == 4 && PK_LAZY && pk128)))) &&
+    g.pk = (keys == 4 || (keys == 0 && (words <= 2 || (words == 4 && pk128)))) &&
            (words <= 2 || (bits > 0 && bits <= PK_MAX_BITS)) && bits <= 32 * words &&
            (words == 1 || words == 2 || words == 4) && cols <= PK_MAX_COLS;
     g.pk_T = g.T >= 2 ? g.T / 2 : 1;

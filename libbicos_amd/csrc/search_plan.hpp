@@ -29,16 +29,11 @@ constexpr int PRUNE_WINDOW = 8;
 // geometry the chunk loop, and launch_pk_variant refuses what it did not plan.
 constexpr int PKP_ST_CHUNK = 1024;
 
-// Lazy drops of the packed-key search (search_pk.hip; BICOS_PK_LAZY=0 builds the branch
-// only, A/B). They pay a fixed rescan per col0 (~32 popcounts of WORDS words); the drop
-// branch pays per drop. Narrow rows (few blocks, few drops on stereo input) keep the branch:
-// cfg1 (640 columns) 13391 vs 12478-12791 Mpix/s; 3208-3300-column rows take the lazy form:
-// random 32-bit NoDuplicates 0.66 vs 1.12-1.14 ms, FULL n = 6 +5 % (FULL n = 8 -1.7 %);
-// profiles/pk_lazy_r06.jsonl
-#ifndef BICOS_PK_LAZY
-#define BICOS_PK_LAZY 1
-#endif
-constexpr bool PK_LAZY = BICOS_PK_LAZY != 0;
+// Lazy drops of the packed-key search (search_pk.hip lazy_drop). They pay a fixed rescan per
+// col0 (~32 popcounts of WORDS words); the drop branch pays per drop. Narrow rows (few blocks,
+// few drops on stereo input) keep the branch: cfg1 (640 columns) 13391 vs 12478-12791 Mpix/s;
+// 3208-3300-column rows take the lazy form: random 32-bit NoDuplicates 0.66 vs 1.12-1.14 ms,
+// FULL n = 6 +5 % (FULL n = 8 -1.7 %); profiles/pk_lazy_r06.jsonl
 constexpr int PK_LAZY_MIN_COLS = 1024;
 
 // The tail launch's shape: one workgroup per row with only the waves its columns need and a

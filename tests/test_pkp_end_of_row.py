@@ -4,9 +4,10 @@ the rescan visits that half's 16 rows in two levels (ham_lo, then the candidates
 distance), and the raw right row and the left descriptors are requested before the barrier
 behind the scan. tests/test_pk_half_rule.py holds the argument as a CPU model; here the kernel
 itself, byte for byte against the CPU oracle, against the end of row as it was
-(BICOS_PKP_EOR=0: rescans of all 32 rows) and against the chunk loop (BICOS_MX_STREAM=0), and
-at match level against the separate agree launch (BICOS_FUSE_AGREE=0). The switches are read
-once per process: one child process per setting computes every case.
+(BICOS_PKP_EOR=0: rescans of all 32 rows), against the chunk loop (BICOS_MX_STREAM=0) and
+against both together, and at match level against the separate agree launch
+(BICOS_FUSE_AGREE=0). The switches are read once per process: one child process per setting
+computes every case.
 
 Shapes: 256 rows (4 tiles per wave planned) x 1056, 1100 (a partial last block of 12 columns;
 its last 76 col0 go to the tail launch, another kernel), 1612 (the same partial block, and no
@@ -153,10 +154,13 @@ def _child(tmp_path_factory, name, **switches):
 
 @pytest.fixture(scope="module")
 def others(gpu, tmp_path_factory):
-    """The same inputs with the end of row as it was, through the chunk loop, and with the
-    separate agree launch."""
+    """The same inputs with the end of row as it was, through the chunk loop, with both (the
+    shared end of row behind the pruned kernel's chunk loop: search_pkp_kernel<AG, false,
+    false>), and with the separate agree launch."""
     return {"eor0": _child(tmp_path_factory, "eor0", BICOS_PKP_EOR="0"),
             "chunk_loop": _child(tmp_path_factory, "chunk_loop", BICOS_MX_STREAM="0"),
+            "eor0_chunk_loop": _child(tmp_path_factory, "eor0_chunk_loop", BICOS_PKP_EOR="0",
+                                      BICOS_MX_STREAM="0"),
             "agree_launch": _child(tmp_path_factory, "agree_launch", BICOS_FUSE_AGREE="0")}
 
 
@@ -196,7 +200,8 @@ def test_end_of_row_fused_match_equals_oracle_and_agree_launch(gpu, oracle, othe
 
 
 if __name__ == "__main__":
-    # child of the `others` fixture: every case through this process's library switch
+    # child of the `others` fixture: every case through this process's library switches (one of
+    # them, or BICOS_PKP_EOR and BICOS_MX_STREAM together)
     assert sys.argv[1] == "--child"
     assert "0" in (os.environ.get("BICOS_PKP_EOR"), os.environ.get("BICOS_MX_STREAM"),
                    os.environ.get("BICOS_FUSE_AGREE"))
