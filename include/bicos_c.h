@@ -406,6 +406,91 @@ int bicos_speckle_host(bicos_engine* e, const void* disparity, int disp_type, in
 /* The tile (rows, cols) one workgroup labels in LDS (tests). Returns BICOS_OK. */
 int bicos_speckle_tile(int* rows, int* cols);
 
+/* --------------------------------------------------------- rectification */
+/* The stage before match(): raw camera frames -> row-aligned (rectified) stacks, on the GPU. Two
+ * operations: the lookup maps of one camera from its calibration, and the bilinear remap of a
+ * whole stack through one pair of maps. The reference starts at rectified imagery and has neither.
+ *
+ * MAPS FROM CALIBRATION: cv::initUndistortRectifyMap's camera model with CV_32FC1 maps (a
+ * statement from reading that function's definition, not from a test against it).
+ *     K   9 doubles, row-major: fx = K[0], cx = K[2], fy = K[4], cy = K[5]. The skew K[1] is
+ *         ignored, as OpenCV ignores it.
+ *     D   nd in {0, 4, 5, 8} doubles k1 k2 p1 p2 [k3 [k4 k5 k6]]; missing coefficients are 0
+ *         (D may be NULL with nd = 0).
+ *     R   9 doubles, row-major, or NULL for the identity.
+ *     P   3 rows of p_cols in {3, 4} doubles, row-major; only the left 3x3 is used.
+ * On the host, in IEEE double without contraction:
+ *     M[i][j] = ((P[i][0]*R[0][j] + P[i][1]*R[1][j]) + P[i][2]*R[2][j])
+ *     det = (M00*(M11*M22 - M12*M21) - M01*(M10*M22 - M12*M20)) + M02*(M10*M21 - M11*M20)
+ *     iM  = inverse(M) by cofactors, each element its cofactor divided by det:
+ *         iM00 = (M11*M22 - M12*M21)/det  iM01 = (M02*M21 - M01*M22)/det  iM02 = (M01*M12 - M02*M11)/det
+ *         iM10 = (M12*M20 - M10*M22)/det  iM11 = (M00*M22 - M02*M20)/det  iM12 = (M02*M10 - M00*M12)/det
+ *         iM20 = (M10*M21 - M11*M20)/det  iM21 = (M01*M20 - M00*M21)/det  iM22 = (M00*M11 - M01*M10)/det
+ * On the device, for output pixel (row v, column u), u and v converted to double, all in IEEE
+ * double without contraction:
+ *     X = (iM00*u + iM01*v) + iM02     Y = (iM10*u + iM11*v) + iM12     W = (iM20*u + iM21*v) + iM22
+ *     x = X/W   y = Y/W   r2 = x*x + y*y
+ *     kr = (1 + ((k3*r2 + k2)*r2 + k1)*r2) / (1 + ((k6*r2 + k5)*r2 + k4)*r2)
+ *     xd = (x*kr + p1*((2*x)*y)) + p2*(r2 + (2*x)*x)
+ *     yd = (y*kr + p1*(r2 + (2*y)*y)) + p2*((2*x)*y)
+ *     map_x = (float)(fx*xd + cx)      map_y = (float)(fy*yd + cy)
+ * Nonfinite results are stored as they come; the remap treats them as outside. The maps are dense
+ * float32 [rows][cols]. A determinant that is 0 or not finite, any nonfinite input, an nd or p_cols
+ * outside its set, a size < 1 or a NULL K, P, map (or D with nd > 0) is BICOS_E_ARG before any HIP
+ * call.
+ *
+ * REMAP OF A STACK:
+ *     src    n planes of src_rows x src_cols, u8 (depth 1) or u16 (depth 2), element (t, y, x) at
+ *            base[t*src_plane_pitch + y*src_row_pitch + x]: pitches in ELEMENTS, exactly as
+ *            bicos_match_device takes them
+ *     map_x, map_y   float32 [rows][cols], absolute source coordinates (column, row); map_pitch is
+ *            the BYTES between their rows (0 = dense, else a multiple of 4 and >= 4*cols)
+ *     border 0 <= border <= 255 (u8) or 65535 (u16)
+ *     dst    n planes of rows x cols of the same depth with pitches of its own (elements)
+ *     valid  optional, uint8 [rows][cols] dense
+ * Per output pixel, with x = map_x and y = map_y as float32:
+ *     inside = x > -1 && x < src_cols && y > -1 && y < src_rows      (false for NaN; float32
+ *            comparisons, the sizes converted to float32)
+ *     not inside: every plane gets `border`, valid = 0. Otherwise
+ *     x0 = floorf(x), fx = x - x0 (one float32 subtraction); y0, fy likewise
+ *     p00 p01 p10 p11 = the taps at (y0, x0) (y0, x0+1) (y0+1, x0) (y0+1, x0+1), converted to
+ *            float32; a tap outside the image has the value (float)border
+ *     top = p00 + fx*(p01 - p00)   bot = p10 + fx*(p11 - p10)   v = top + fy*(bot - top)
+ *            every operation rounded to float32 on its own, no fma
+ *     out = (T)min(max(rintf(v), 0), max of the depth)               (ties to even)
+ *     valid = 1 iff every tap with a nonzero weight lies in the image: column x0 and row y0
+ *            always count, column x0+1 only if fx != 0, row y0+1 only if fy != 0
+ * An identity map therefore reproduces the image byte for byte with valid all ones. The fractions
+ * are full float32: finer than cv::remap's INTER_LINEAR, which quantises them to 1/32 pixel, so
+ * the two differ in the last level here and there. Nothing here is tested against OpenCV.
+ * Argument errors are BICOS_E_ARG (bicos_last_error says which) before any HIP call: n < 1; a
+ * size < 1; depth not 1 or 2; a pitch smaller than a row; a map_pitch or host step that is not a
+ * multiple of its element size; border out of range; a NULL src, dst or map; dst == src; a plane
+ * that spans more than 2^32 - 1 elements. */
+/* device: asynchronous on `stream`, no workspace, nothing allocated. */
+int bicos_rectify_maps_device(const double K[9], const double* D, int nd, const double* R,
+                              const double* P, int p_cols, int rows, int cols, float* map_x,
+                              float* map_y, void* stream);
+/* host maps, synchronous, through the current device's default engine. */
+int bicos_rectify_maps_host(const double K[9], const double* D, int nd, const double* R,
+                            const double* P, int p_cols, int rows, int cols, float* map_x,
+                            float* map_y);
+/* device: asynchronous on `stream`, one launch, no workspace: e may be NULL. */
+int bicos_rectify_device(bicos_engine* e, const void* src, int n, int src_rows, int src_cols,
+                         size_t src_row_pitch, size_t src_plane_pitch, int depth,
+                         const float* map_x, const float* map_y, size_t map_pitch, int rows,
+                         int cols, void* dst, size_t dst_row_pitch, size_t dst_plane_pitch,
+                         int border, uint8_t* valid, void* stream);
+/* host buffers, synchronous, e NULL = default engine: n image pointers in (src_rows x src_cols,
+ * src_step BYTES per row, 0 = dense) and n out (rows x cols, dst_step likewise); the maps
+ * (map_pitch as above) and valid in host memory. Uploads, runs the same launch, downloads. */
+int bicos_rectify_host(bicos_engine* e, const void* const* src, int n, int src_rows, int src_cols,
+                       size_t src_step, int depth, const float* map_x, const float* map_y,
+                       size_t map_pitch, int rows, int cols, void* const* dst, size_t dst_step,
+                       int border, uint8_t* valid);
+/* The tile (rows, cols) of output pixels one workgroup remaps (tests). Returns BICOS_OK. */
+int bicos_rectify_tile(int* rows, int* cols);
+
 /* Build identification (arch, flags) for reports. */
 const char* bicos_build_info(void);
 

@@ -63,6 +63,8 @@ EXPORTS = (
     "bicos_match_device_range", "bicos_match_host_range", "bicos_search_device_range",
     "bicos_reproject_device", "bicos_reproject_host", "bicos_reproject_segment",
     "bicos_speckle_device", "bicos_speckle_host", "bicos_speckle_tile",
+    "bicos_rectify_maps_device", "bicos_rectify_maps_host", "bicos_rectify_device",
+    "bicos_rectify_host", "bicos_rectify_tile",
 )
 
 # bicos_match_plan bits (include/bicos_c.h)
@@ -191,6 +193,16 @@ def lib() -> ctypes.CDLL:
     L.bicos_speckle_host.restype = I
     L.bicos_speckle_tile.argtypes = [PI, PI]
     L.bicos_speckle_tile.restype = I
+    L.bicos_rectify_maps_device.argtypes = [PD, PD, I, PD, PD, I, I, I, P, P, P]
+    L.bicos_rectify_maps_device.restype = I
+    L.bicos_rectify_maps_host.argtypes = [PD, PD, I, PD, PD, I, I, I, P, P]
+    L.bicos_rectify_maps_host.restype = I
+    L.bicos_rectify_device.argtypes = [P, P, I, I, I, Z, Z, I, P, P, Z, I, I, P, Z, Z, I, P, P]
+    L.bicos_rectify_device.restype = I
+    L.bicos_rectify_host.argtypes = [P, PP, I, I, I, Z, I, P, P, Z, I, I, PP, Z, I, P]
+    L.bicos_rectify_host.restype = I
+    L.bicos_rectify_tile.argtypes = [PI, PI]
+    L.bicos_rectify_tile.restype = I
     L.bicos_build_info.restype = ctypes.c_char_p
     L.bicos_build_info.argtypes = []
     _lib = L
@@ -248,6 +260,45 @@ def speckle_tile():
     r, c = ctypes.c_int(0), ctypes.c_int(0)
     lib().bicos_speckle_tile(ctypes.byref(r), ctypes.byref(c))
     return r.value, c.value
+
+
+def rectify_tile():
+    """(rows, cols) of the output tile one workgroup remaps (bicos_rectify_tile)."""
+    r, c = ctypes.c_int(0), ctypes.c_int(0)
+    lib().bicos_rectify_tile(ctypes.byref(r), ctypes.byref(c))
+    return r.value, c.value
+
+
+def rectify_camera(K, D, R, P, size):
+    """The calibration of one camera as the bicos_rectify_maps_* entries take it: (K, D, nd, R,
+    P, p_cols, rows, cols) with ctypes double arrays (R None for the identity). K is 3x3, D
+    None or 0, 4, 5 or 8 coefficients, R None or 3x3, P 3x3 or 3x4, size (rows, cols).
+    ValueError for other shapes; the values are checked by the library."""
+    import numpy as np
+
+    def arr(a, name, shapes):
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape not in shapes:
+            raise ValueError("%s must have shape %s, got %s"
+                             % (name, " or ".join(str(s) for s in shapes), a.shape))
+        return (ctypes.c_double * a.size)(*a.ravel().tolist())
+
+    k = arr(K, "K", ((3, 3),))
+    d = np.zeros(0) if D is None else np.asarray(D, dtype=np.float64).ravel()
+    if d.size not in (0, 4, 5, 8):
+        raise ValueError("D must hold 0, 4, 5 or 8 coefficients, got %d" % d.size)
+    dd = (ctypes.c_double * d.size)(*d.tolist()) if d.size else None
+    r = None if R is None else arr(R, "R", ((3, 3),))
+    p = np.asarray(P, dtype=np.float64)
+    pp = arr(p, "P", ((3, 3), (3, 4)))
+    try:
+        rows, cols = size
+        rows, cols = int(rows), int(cols)
+    except (TypeError, ValueError):
+        raise ValueError("size must be a pair (rows, cols)") from None
+    if rows < 1 or cols < 1 or rows * cols >= 2 ** 31:
+        raise ValueError("size must be positive with fewer than 2^31 pixels, got %r" % (size,))
+    return k, dd, int(d.size), r, pp, int(p.shape[1]), rows, cols
 
 
 def check(rc: int, what: str = "bicos") -> None:

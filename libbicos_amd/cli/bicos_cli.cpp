@@ -55,6 +55,10 @@ const char* USAGE =
     "                          saved and reprojected (default: off)\n"
     "      --speckle-diff F    largest disparity difference of two neighbours in one region\n"
     "                          (1; only with --speckle-size)\n"
+    "      --rectify FILE      the inputs are raw frames: OpenCV FileStorage (YAML/XML) with\n"
+    "                          the matrices M1 D1 R1 P1 M2 D2 R2 P2 of cv::stereoRectify;\n"
+    "                          both stacks are rectified to their own size before the match.\n"
+    "                          A \"Q\" in FILE is used when -q is not given\n"
     "  -m, --lr-maxdiff N      maximum left-right disparity difference (Consistency\n"
     "                          variant; disables duplicate filtering)\n"
     "      --double            double precision correlation\n"
@@ -77,7 +81,8 @@ Args parse(int argc, char** argv) {
         {"threshold", true}, {"variance", true}, {"step", true}, {"out", true},
         {"stacksize", true}, {"qmatrix", true}, {"lr-maxdiff", true}, {"help", false},
         {"allow-negative-z", false}, {"double", false}, {"limited", false},
-        {"corrmap", false}, {"no-dupes", false}, {"speckle-size", true}, {"speckle-diff", true}};
+        {"corrmap", false}, {"no-dupes", false}, {"speckle-size", true}, {"speckle-diff", true},
+        {"rectify", true}};
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i];
@@ -140,6 +145,42 @@ void save_image(const Image& img, fs::path out, bicos_cli::Colormap cmap) {
     std::cout << "Saved floating-point disparity to\t" << out << std::endl;
 }
 
+// --rectify: the images of one camera (side "1" or "2": M, D, R, P of that name in `file`, as
+// OpenCV's stereo calibration sample writes them) remapped in place to their own size
+void rectify_stack(const std::string& file, const std::string& side, std::vector<bicos_cli::Gray>& stack) {
+    const std::vector<double> M = bicos_cli::read_filestorage_matrix(file, "M" + side, 3, 3);
+    const std::vector<double> R = bicos_cli::read_filestorage_matrix(file, "R" + side, 3, 3);
+    const auto D = bicos_cli::find_filestorage_matrix(file, "D" + side);
+    const auto P = bicos_cli::find_filestorage_matrix(file, "P" + side);
+    if (!D) throw std::runtime_error(file + ": no matrix \"D" + side + "\"");
+    if (!P || P->rows != 3) throw std::runtime_error(file + ": no 3-row matrix \"P" + side + "\"");
+    const int rows = stack.front().rows, cols = stack.front().cols, type = stack.front().type;
+    const size_t pixels = (size_t)rows * cols;
+    std::vector<float> map_x(pixels), map_y(pixels);
+    if (bicos_rectify_maps_host(M.data(), D->data.empty() ? nullptr : D->data.data(),
+                                (int)D->data.size(), R.data(), P->data.data(), P->cols, rows, cols,
+                                map_x.data(), map_y.data()) != BICOS_OK)
+        throw std::runtime_error(std::string("rectification maps failed: ") + bicos_last_error());
+    std::vector<bicos_cli::Gray> out(stack.size());
+    std::vector<const void*> src;
+    std::vector<void*> dst;
+    for (size_t t = 0; t < stack.size(); ++t) {
+        if (stack[t].rows != rows || stack[t].cols != cols || stack[t].type != type)
+            throw std::runtime_error("--rectify: all images must share size and type");
+        out[t].rows = rows;
+        out[t].cols = cols;
+        out[t].type = type;
+        out[t].pixels.resize(stack[t].pixels.size());
+        src.push_back(stack[t].pixels.data());
+        dst.push_back(out[t].pixels.data());
+    }
+    if (bicos_rectify_host(nullptr, src.data(), (int)stack.size(), rows, cols, 0, type == U16 ? 2 : 1,
+                           map_x.data(), map_y.data(), 0, rows, cols, dst.data(), 0, 0,
+                           nullptr) != BICOS_OK)
+        throw std::runtime_error(std::string("rectification failed: ") + bicos_last_error());
+    stack.swap(out);
+}
+
 int run(int argc, char** argv) {
     const Args args = parse(argc, argv);
     if (args.has("help") || args.pos.empty()) {
@@ -174,6 +215,17 @@ int run(int argc, char** argv) {
     if (left.empty()) throw std::invalid_argument("no input images");
     std::cout << "Loaded " << left.size() + right.size() << " "
               << (left.front().type == U16 ? 16 : 8) << "-bit images in total" << std::endl;
+
+    if (args.has("rectify")) {
+        // raw frames: both stacks through their camera's maps, on the GPU, to the input size
+        const std::string file = args.val.at("rectify");
+        if (!fs::exists(file)) throw std::invalid_argument("'" + file + "' does not exist");
+        const auto tick = std::chrono::high_resolution_clock::now();
+        rectify_stack(file, "1", left);
+        rectify_stack(file, "2", right);
+        std::cout << "Rectified:\t" << ms_since(tick) << "ms" << std::endl;
+        if (!q_store && bicos_cli::find_filestorage_matrix(file, "Q")) q_store = file;
+    }
 
     Config c;
     c.nxcorr_threshold = args.has("threshold") ? as_float(args, "threshold") : 0.75f;

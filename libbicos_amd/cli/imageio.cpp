@@ -388,7 +388,7 @@ std::vector<uint8_t> colorize(const BICOS::Image& img, Colormap cmap) {
     return rgb;
 }
 
-std::array<double, 16> read_filestorage_matrix(const std::string& path, const std::string& name) {
+std::optional<Matrix> find_filestorage_matrix(const std::string& path, const std::string& name) {
     const std::vector<uint8_t> b = slurp(path);
     const std::string s(b.begin(), b.end());
     const bool xml = s.find("<opencv_storage>") != std::string::npos;
@@ -403,9 +403,35 @@ std::array<double, 16> read_filestorage_matrix(const std::string& path, const st
                 break;
             }
     }
-    if (at == std::string::npos) throw std::runtime_error(path + ": no matrix \"" + name + "\"");
-    const std::vector<double> v = numbers_after(s, at, xml);
-    if (v.size() != 16) throw std::runtime_error("matrix \"" + name + "\" is not 4x4");
+    if (at == std::string::npos) return std::nullopt;
+    Matrix m;
+    m.data = numbers_after(s, at, xml);
+    // <rows>3</rows> / "rows: 3", between the name and the data
+    const size_t end = xml ? s.find("<data>", at) : s.find("data", at);
+    auto dim = [&](const std::string& key) {
+        const size_t p = s.find(xml ? "<" + key + ">" : key + ":", at);
+        if (p == std::string::npos || p > end) throw std::runtime_error("matrix \"" + name + "\" has no " + key);
+        return std::atoi(s.c_str() + p + key.size() + (xml ? 2 : 1));
+    };
+    m.rows = dim("rows");
+    m.cols = dim("cols");
+    if (m.rows < 0 || m.cols < 0 || (size_t)m.rows * (size_t)m.cols != m.data.size())
+        throw std::runtime_error("matrix \"" + name + "\": rows x cols disagrees with its data");
+    return m;
+}
+
+std::vector<double> read_filestorage_matrix(const std::string& path, const std::string& name,
+                                            int rows, int cols) {
+    const std::optional<Matrix> m = find_filestorage_matrix(path, name);
+    if (!m) throw std::runtime_error(path + ": no matrix \"" + name + "\"");
+    if (m->rows != rows || m->cols != cols)
+        throw std::runtime_error("matrix \"" + name + "\" is not " + std::to_string(rows) + "x" +
+                                 std::to_string(cols));
+    return m->data;
+}
+
+std::array<double, 16> read_filestorage_matrix(const std::string& path, const std::string& name) {
+    const std::vector<double> v = read_filestorage_matrix(path, name, 4, 4);
     std::array<double, 16> q;
     std::copy(v.begin(), v.end(), q.begin());
     return q;

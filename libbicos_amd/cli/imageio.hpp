@@ -51,8 +51,20 @@ enum class Colormap { Turbo, Viridis };
 std::vector<uint8_t> colorize(const BICOS::Image& img, Colormap cmap);
 std::array<uint8_t, 3> colormap_rgb(Colormap cmap, uint8_t v);
 
-// The 4x4 matrix named `name` in an OpenCV FileStorage file (YAML "!!opencv-matrix" or XML
-// type_id="opencv-matrix"), row-major.
+// A matrix of an OpenCV FileStorage file (YAML "!!opencv-matrix" or XML type_id="opencv-matrix"),
+// row-major.
+struct Matrix {
+    int rows = 0, cols = 0;
+    std::vector<double> data;
+};
+// The matrix named `name`, or nothing when the file has none of that name. Throws
+// std::runtime_error for a matrix whose rows x cols disagrees with its data.
+std::optional<Matrix> find_filestorage_matrix(const std::string& path, const std::string& name);
+// The matrix named `name` of the stated shape; std::runtime_error when it is absent or not
+// rows x cols.
+std::vector<double> read_filestorage_matrix(const std::string& path, const std::string& name,
+                                            int rows, int cols);
+// The 4x4 matrix named `name` (the stereo Q).
 std::array<double, 16> read_filestorage_matrix(const std::string& path, const std::string& name);
 
 struct XyzStats {

@@ -4,6 +4,7 @@
 //                     impl::cpu::match (src/impl/cpu.cpp:100-159)
 //   BICOS::reproject  (bicos/reproject.hpp; no reference counterpart in its library)
 //   BICOS::filter_speckles  (bicos/speckle.hpp; no reference counterpart)
+//   BICOS::rectify_maps, BICOS::rectify  (bicos/rectify.hpp; no reference counterpart)
 #include "engine.hpp"
 
 #include <algorithm>
@@ -17,6 +18,7 @@
 #include "../../include/bicos/hip.hpp"
 #include "../../include/bicos/reproject.hpp"
 #include "../../include/bicos/speckle.hpp"
+#include "../../include/bicos/rectify.hpp"
 
 using bicos_impl::check_hip;
 
@@ -356,6 +358,104 @@ SpeckleStats filter_speckles(const Image& disparity, Image& out, int max_size, f
                                          hipMemcpyDeviceToHost), "labels download"));
     }
     return SpeckleStats{counts[0], counts[1], counts[2], counts[3]};
+}
+
+// ------------------------------------------------- BICOS::rectify_maps, BICOS::rectify
+// over the C entries (entries.cpp), which validate and launch
+
+void rectify_maps(const RectifyCamera& camera, int rows, int cols, Image& map_x, Image& map_y,
+                  Memory mem, hipStream_t stream) {
+    const size_t np = camera.P.size();
+    if (np != 9 && np != 12) throw Exception("rectify_maps: P must hold 3x3 or 3x4 values");
+    if (rows < 1 || cols < 1) throw Exception("rectify_maps: the output size must be positive");
+    map_x.create(rows, cols, F32, mem);
+    map_y.create(rows, cols, F32, mem);
+    const double* D = camera.D.empty() ? nullptr : camera.D.data();
+    if (mem == Memory::Host)
+        throw_rc(bicos_rectify_maps_host(camera.K, D, (int)camera.D.size(), camera.R,
+                                         camera.P.data(), (int)np / 3, rows, cols,
+                                         (float*)map_x.data(), (float*)map_y.data()));
+    else
+        throw_rc(bicos_rectify_maps_device(camera.K, D, (int)camera.D.size(), camera.R,
+                                           camera.P.data(), (int)np / 3, rows, cols,
+                                           (float*)map_x.data(), (float*)map_y.data(), stream));
+}
+
+namespace {
+
+// The distance in bytes between the images when they form one planar buffer (one step, equally
+// spaced, ascending), 0 when they do not; a single image is planar with any distance.
+size_t planar_pitch(const std::vector<Image>& s) {
+    const size_t row = (size_t)s[0].cols() * s[0].elemSize();
+    if (s.size() == 1) return s[0].step() * (size_t)s[0].rows() + row;
+    const char* base = (const char*)s[0].data();
+    if ((const char*)s[1].data() <= base) return 0;
+    const size_t pitch = (size_t)((const char*)s[1].data() - base);
+    if (pitch % s[0].elemSize() || pitch < row) return 0;
+    for (size_t t = 0; t < s.size(); ++t)
+        if (s[t].step() != s[0].step() || (const char*)s[t].data() != base + t * pitch) return 0;
+    return pitch;
+}
+
+}  // namespace
+
+void rectify(const std::vector<Image>& stack, const Image& map_x, const Image& map_y,
+             std::vector<Image>& out_stack, int border, Image* valid, hipStream_t stream) {
+    if (stack.empty()) throw Exception("rectify: empty image stack");
+    const Image& f = stack[0];
+    const int type = f.type(), rows = map_x.rows(), cols = map_x.cols();
+    if (type != U8 && type != U16) throw Exception("rectify: the images must be U8 or U16");
+    const Memory mem = f.memory();
+    for (const Image& im : stack)
+        if (im.rows() != f.rows() || im.cols() != f.cols() || im.type() != type ||
+            im.memory() != mem || !im.data())
+            throw Exception("rectify: all images must share size, type and memory");
+    if (map_x.type() != F32 || map_y.type() != F32 || map_y.rows() != rows || map_y.cols() != cols ||
+        map_x.step() != map_y.step() || map_x.memory() != mem || map_y.memory() != mem)
+        throw Exception("rectify: the maps must be F32 images of one shape and step in the "
+                        "memory of the stack");
+    if (rows < 1 || cols < 1) throw Exception("rectify: empty maps");
+    if (&out_stack == &stack) throw Exception("rectify: the output must not be the source");
+    const size_t n = stack.size(), depth = f.elemSize();
+    out_stack.resize(n);
+    for (Image& o : out_stack) o.create(rows, cols, type, mem);
+    if (valid) valid->create(rows, cols, U8, mem);
+    uint8_t* vp = valid ? (uint8_t*)valid->data() : nullptr;
+    const float* mx = (const float*)map_x.data();
+    const float* my = (const float*)map_y.data();
+    if (mem == Memory::Host) {
+        std::vector<const void*> src(n);
+        std::vector<void*> dst(n);
+        for (size_t t = 0; t < n; ++t) {
+            if (stack[t].step() != f.step() || out_stack[t].step() != out_stack[0].step())
+                throw Exception("rectify: host images of one stack must share one step");
+            src[t] = stack[t].data();
+            dst[t] = out_stack[t].data();
+        }
+        throw_rc(bicos_rectify_host(nullptr, src.data(), (int)n, f.rows(), f.cols(), f.step(),
+                                    (int)depth, mx, my, map_x.step(), rows, cols, dst.data(),
+                                    out_stack[0].step(), border, vp));
+        return;
+    }
+    if (f.step() % depth || out_stack[0].step() % depth)
+        throw Exception("rectify: an image step is not a multiple of the pixel size");
+    const size_t sp = planar_pitch(stack), dp = planar_pitch(out_stack);
+    if (sp && dp) {
+        throw_rc(bicos_rectify_device(current_engine(), f.data(), (int)n, f.rows(), f.cols(),
+                                      f.step() / depth, sp / depth, (int)depth, mx, my,
+                                      map_x.step(), rows, cols, out_stack[0].data(),
+                                      out_stack[0].step() / depth, dp / depth, border, vp, stream));
+        return;
+    }
+    for (size_t t = 0; t < n; ++t) {
+        const Image &s = stack[t], &o = out_stack[t];
+        if (s.step() % depth || o.step() % depth)
+            throw Exception("rectify: an image step is not a multiple of the pixel size");
+        throw_rc(bicos_rectify_device(current_engine(), s.data(), 1, s.rows(), s.cols(),
+                                      s.step() / depth, s.step() / depth * s.rows(), (int)depth, mx,
+                                      my, map_x.step(), rows, cols, o.data(), o.step() / depth,
+                                      o.step() / depth * o.rows(), border, t ? nullptr : vp, stream));
+    }
 }
 
 }  // namespace BICOS

@@ -658,6 +658,131 @@ int speckle_device(bicos_engine* e, const SpeckleJob& j, hipStream_t st) {
                      "speckle launches");
 }
 
+// ------------------------------------------------------------- rectification
+
+int check_rectify(const RectifyJob& j) {
+    if (j.n < 1) return fail(BICOS_E_ARG, "rectify: need at least one image");
+    if (j.src_rows < 1 || j.src_cols < 1)
+        return fail(BICOS_E_ARG, "rectify: the source size must be positive");
+    if (j.rows < 1 || j.cols < 1)
+        return fail(BICOS_E_ARG, "rectify: the output size must be positive");
+    if (j.depth != 1 && j.depth != 2)
+        return fail(BICOS_E_ARG, "rectify: depth must be 1 (u8) or 2 (u16)");
+    if (j.src_row_pitch < (size_t)j.src_cols || j.src_plane_pitch < (size_t)j.src_cols)
+        return fail(BICOS_E_ARG, "rectify: a source pitch is smaller than a row");
+    if (j.dst_row_pitch < (size_t)j.cols || j.dst_plane_pitch < (size_t)j.cols)
+        return fail(BICOS_E_ARG, "rectify: an output pitch is smaller than a row");
+    if (j.map_pitch % sizeof(float))
+        return fail(BICOS_E_ARG, "rectify: map_pitch must be a multiple of 4 bytes");
+    if (j.map_pitch && j.map_pitch < (size_t)j.cols * sizeof(float))
+        return fail(BICOS_E_ARG, "rectify: map_pitch is smaller than a row");
+    if (j.border < 0 || j.border > (j.depth == 1 ? 255 : 65535))
+        return fail(BICOS_E_ARG, "rectify: border is outside the range of the depth");
+    if (!j.src) return fail(BICOS_E_ARG, "rectify: null source stack");
+    if (!j.dst) return fail(BICOS_E_ARG, "rectify: null output stack");
+    if (!j.map_x || !j.map_y) return fail(BICOS_E_ARG, "rectify: null map");
+    if (j.dst == j.src) return fail(BICOS_E_ARG, "rectify: the output must not be the source");
+    // 32-bit offsets within a plane, 32-bit linear index of the dense valid map
+    const unsigned long long lim = 0xFFFFFFFFull;
+    if ((unsigned long long)(j.src_rows - 1) * j.src_row_pitch + (unsigned long long)j.src_cols > lim ||
+        (unsigned long long)(j.rows - 1) * j.dst_row_pitch + (unsigned long long)j.cols > lim ||
+        (unsigned long long)j.rows * (j.map_pitch ? j.map_pitch / sizeof(float) : (size_t)j.cols) > lim ||
+        (unsigned long long)j.rows * (unsigned long long)j.cols > (unsigned long long)INT32_MAX)
+        return fail(BICOS_E_ARG, "rectify: a plane spans more than 2^32 - 1 elements");
+    return BICOS_OK;
+}
+
+int rectify_device(const RectifyJob& j, hipStream_t st) {
+    bicos_hip::RectifyArgs a{};
+    a.src = j.src;
+    a.dst = j.dst;
+    a.map_x = j.map_x;
+    a.map_y = j.map_y;
+    a.valid = j.valid;
+    a.n = j.n;
+    a.src_rows = j.src_rows;
+    a.src_cols = j.src_cols;
+    a.rows = j.rows;
+    a.cols = j.cols;
+    a.src_row_pitch = (uint32_t)j.src_row_pitch;
+    a.dst_row_pitch = (uint32_t)j.dst_row_pitch;
+    a.src_plane_pitch = j.src_plane_pitch;
+    a.dst_plane_pitch = j.dst_plane_pitch;
+    a.map_pitch = (uint32_t)(j.map_pitch ? j.map_pitch / sizeof(float) : (size_t)j.cols);
+    a.border = (uint32_t)j.border;
+    // a lane's four pixels start at a column that is a multiple of four
+    const size_t vec_bytes = (size_t)bicos_hip::RECTIFY_PER_LANE * j.depth;
+    a.dst_vector = (uintptr_t)j.dst % vec_bytes == 0 &&
+                   j.dst_row_pitch % bicos_hip::RECTIFY_PER_LANE == 0 &&
+                   j.dst_plane_pitch % bicos_hip::RECTIFY_PER_LANE == 0;
+    a.valid_vector = (uintptr_t)j.valid % 4 == 0 && j.cols % 4 == 0;
+    return check_hip(bicos_hip::launch_rectify(a, j.depth, st), "rectify launch");
+}
+
+int check_rectify_maps(const RectifyMapsJob& j, bicos_hip::RectifyCamera* cam) {
+    if (j.nd != 0 && j.nd != 4 && j.nd != 5 && j.nd != 8)
+        return fail(BICOS_E_ARG, "rectify_maps: nd must be 0, 4, 5 or 8");
+    if (j.p_cols != 3 && j.p_cols != 4)
+        return fail(BICOS_E_ARG, "rectify_maps: p_cols must be 3 or 4");
+    if (j.rows < 1 || j.cols < 1)
+        return fail(BICOS_E_ARG, "rectify_maps: the output size must be positive");
+    if ((int64_t)j.rows * j.cols > INT32_MAX)
+        return fail(BICOS_E_ARG, "rectify_maps: rows * cols exceeds int32");
+    if (!j.K || !j.P || (j.nd > 0 && !j.D))
+        return fail(BICOS_E_ARG, "rectify_maps: null K, D or P");
+    if (!j.map_x || !j.map_y) return fail(BICOS_E_ARG, "rectify_maps: null map");
+    bool finite = true;
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(j.K[i]);
+    for (int i = 0; i < j.nd; ++i) finite = finite && std::isfinite(j.D[i]);
+    for (int i = 0; j.R && i < 9; ++i) finite = finite && std::isfinite(j.R[i]);
+    for (int i = 0; i < 3 * j.p_cols; ++i) finite = finite && std::isfinite(j.P[i]);
+    if (!finite) return fail(BICOS_E_ARG, "rectify_maps: a calibration value is not finite");
+    static const double identity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    const double* R = j.R ? j.R : identity;
+    double m[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const double* p = j.P + r * j.p_cols;
+            m[r][c] = ((p[0] * R[c] + p[1] * R[3 + c]) + p[2] * R[6 + c]);
+        }
+    const double det = (m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) -
+                        m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0])) +
+                       m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    if (det == 0.0 || !std::isfinite(det))
+        return fail(BICOS_E_ARG, "rectify_maps: P[:, :3] * R is singular");
+    bicos_hip::RectifyCamera c{};
+    c.iM[0] = (m[1][1] * m[2][2] - m[1][2] * m[2][1]) / det;
+    c.iM[1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det;
+    c.iM[2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det;
+    c.iM[3] = (m[1][2] * m[2][0] - m[1][0] * m[2][2]) / det;
+    c.iM[4] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det;
+    c.iM[5] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det;
+    c.iM[6] = (m[1][0] * m[2][1] - m[1][1] * m[2][0]) / det;
+    c.iM[7] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det;
+    c.iM[8] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det;
+    c.fx = j.K[0];
+    c.cx = j.K[2];
+    c.fy = j.K[4];
+    c.cy = j.K[5];
+    const auto d = [&](int i) { return i < j.nd ? j.D[i] : 0.0; };
+    c.k1 = d(0);
+    c.k2 = d(1);
+    c.p1 = d(2);
+    c.p2 = d(3);
+    c.k3 = d(4);
+    c.k4 = d(5);
+    c.k5 = d(6);
+    c.k6 = d(7);
+    *cam = c;
+    return BICOS_OK;
+}
+
+int rectify_maps_device(const RectifyMapsJob& j, const bicos_hip::RectifyCamera& cam,
+                        hipStream_t st) {
+    return check_hip(bicos_hip::launch_rectify_maps(cam, j.rows, j.cols, j.map_x, j.map_y, st),
+                     "rectify_maps launch");
+}
+
 // ------------------------------------------------------- process-wide engines
 
 namespace {

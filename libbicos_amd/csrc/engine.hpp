@@ -6,9 +6,10 @@
 //
 //   engine.cpp  errors, the workspace lease, engine resources, the plans, the search driver
 //               and match_device; reproject_device (disparity map -> 3-D points);
-//               speckle_device (the speckle filter of a disparity map)
+//               speckle_device (the speckle filter of a disparity map); rectify_device and
+//               rectify_maps_device (raw stacks -> rectified stacks)
 //   host.cpp    the banded host-buffer pipeline (HostPool, match_host); reproject_host;
-//               speckle_host
+//               speckle_host; rectify_host, rectify_maps_host
 //   entries.cpp the bicos_* extern "C" entries (bicos_c.h) but the multi-GPU ones
 //   multi.cpp   bicos_match_host_multi, bicos_match_bands_device
 //   cxxapi.cpp  namespace BICOS (HipImage, match, reproject, filter_speckles)
@@ -27,6 +28,7 @@
 
 #include "../../include/bicos_c.h"
 #include "kernels.hpp"
+#include "rectify.hpp"
 
 namespace bicos_impl {
 // Small persistent pool for the host-side copies of the host-buffer pipeline: run(k, f)
@@ -313,6 +315,50 @@ int speckle_device(bicos_engine* e, const SpeckleJob& j, hipStream_t st);
 // Host buffers: the map uploaded into the engine's staging, the same launches on the engine's
 // own stream, the map, the counts and the labels downloaded. Synchronous.
 int speckle_host(bicos_engine* e, const SpeckleJob& j);
+
+// One remap of a stack (bicos_c.h "rectification"): the arguments of bicos_rectify_device, the
+// pointers all in device memory, the stack pitches in elements, map_pitch in bytes (0 = dense).
+struct RectifyJob {
+    const void* src;
+    int n, src_rows, src_cols;
+    size_t src_row_pitch, src_plane_pitch;
+    int depth;
+    const float* map_x;
+    const float* map_y;
+    size_t map_pitch;
+    int rows, cols;
+    void* dst;
+    size_t dst_row_pitch, dst_plane_pitch;
+    int border;
+    uint8_t* valid;
+};
+// BICOS_E_ARG (with a message) for what the entries refuse; no HIP call.
+int check_rectify(const RectifyJob& j);
+// The one launch on `st` (validated arguments); no workspace, no engine.
+int rectify_device(const RectifyJob& j, hipStream_t st);
+// Host buffers: n plane pointers in and out with their steps in bytes (0 = dense), the maps and
+// valid in host memory; staged through the engine, the same launch on its own stream. Synchronous.
+int rectify_host(bicos_engine* e, const void* const* src, size_t src_step, void* const* dst,
+                 size_t dst_step, const RectifyJob& j);
+
+// The maps of one camera (bicos_c.h "rectification"): the calibration as the entries take it.
+struct RectifyMapsJob {
+    const double* K;
+    const double* D;
+    int nd;
+    const double* R;
+    const double* P;
+    int p_cols, rows, cols;
+    float* map_x;
+    float* map_y;
+};
+// BICOS_E_ARG (with a message) for what the entries refuse, else the camera with the inverse of
+// P[:, :3] * R as the kernel takes it (plain double arithmetic on the host); no HIP call.
+int check_rectify_maps(const RectifyMapsJob& j, bicos_hip::RectifyCamera* cam);
+int rectify_maps_device(const RectifyMapsJob& j, const bicos_hip::RectifyCamera& cam,
+                        hipStream_t st);
+// Host maps: computed in the engine's staging on its own stream and downloaded. Synchronous.
+int rectify_maps_host(bicos_engine* e, const RectifyMapsJob& j, const bicos_hip::RectifyCamera& cam);
 
 // Process-wide engine for `device` (created on first use).
 bicos_engine* default_engine(int device);

@@ -406,6 +406,85 @@ int bicos_speckle_tile(int* rows, int* cols) {
     return BICOS_OK;
 }
 
+int bicos_rectify_maps_device(const double K[9], const double* D, int nd, const double* R,
+                              const double* P, int p_cols, int rows, int cols, float* map_x,
+                              float* map_y, void* stream) {
+    const RectifyMapsJob job{K, D, nd, R, P, p_cols, rows, cols, map_x, map_y};
+    bicos_hip::RectifyCamera cam;
+    if (int rc0 = check_rectify_maps(job, &cam)) return rc0;
+    return guarded([&]() -> int { return rectify_maps_device(job, cam, (hipStream_t)stream); });
+}
+
+int bicos_rectify_maps_host(const double K[9], const double* D, int nd, const double* R,
+                            const double* P, int p_cols, int rows, int cols, float* map_x,
+                            float* map_y) {
+    const RectifyMapsJob job{K, D, nd, R, P, p_cols, rows, cols, map_x, map_y};
+    bicos_hip::RectifyCamera cam;
+    if (int rc0 = check_rectify_maps(job, &cam)) return rc0;
+    return guarded([&]() -> int {
+        int dev = 0;
+        int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
+        if (rc) return rc;
+        bicos_engine* e = default_engine(dev);
+        if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        std::lock_guard<std::mutex> g(e->lock);
+        return rectify_maps_host(e, job, cam);
+    });
+}
+
+int bicos_rectify_device(bicos_engine* e, const void* src, int n, int src_rows, int src_cols,
+                         size_t src_row_pitch, size_t src_plane_pitch, int depth,
+                         const float* map_x, const float* map_y, size_t map_pitch, int rows,
+                         int cols, void* dst, size_t dst_row_pitch, size_t dst_plane_pitch,
+                         int border, uint8_t* valid, void* stream) {
+    (void)e;  // no workspace: one launch on the caller's stream
+    const RectifyJob job{src, n, src_rows, src_cols, src_row_pitch, src_plane_pitch, depth,
+                         map_x, map_y, map_pitch, rows, cols, dst, dst_row_pitch,
+                         dst_plane_pitch, border, valid};
+    if (int rc0 = check_rectify(job)) return rc0;
+    return guarded([&]() -> int { return rectify_device(job, (hipStream_t)stream); });
+}
+
+int bicos_rectify_host(bicos_engine* e, const void* const* src, int n, int src_rows, int src_cols,
+                       size_t src_step, int depth, const float* map_x, const float* map_y,
+                       size_t map_pitch, int rows, int cols, void* const* dst, size_t dst_step,
+                       int border, uint8_t* valid) {
+    if (n < 1) return fail(BICOS_E_ARG, "rectify: need at least one image");
+    if (depth != 1 && depth != 2)
+        return fail(BICOS_E_ARG, "rectify: depth must be 1 (u8) or 2 (u16)");
+    if (!src || !dst) return fail(BICOS_E_ARG, "rectify: null image list");
+    if (src_step % (size_t)depth || dst_step % (size_t)depth)
+        return fail(BICOS_E_ARG, "rectify: a step is not a multiple of the depth");
+    const size_t sstep = src_step ? src_step : (size_t)(src_cols > 0 ? src_cols : 0) * depth;
+    const size_t dstep = dst_step ? dst_step : (size_t)(cols > 0 ? cols : 0) * depth;
+    for (int t = 0; t < n; ++t) {
+        // every image through the device entry's checks, as a one-plane stack of its step
+        const RectifyJob one{src[t], 1, src_rows, src_cols, sstep / depth, sstep / depth, depth,
+                             map_x, map_y, map_pitch, rows, cols, dst[t], dstep / depth,
+                             dstep / depth, border, valid};
+        if (int rc0 = check_rectify(one)) return rc0;
+    }
+    const RectifyJob job{src[0], n, src_rows, src_cols, 0, 0, depth, map_x, map_y, map_pitch,
+                         rows, cols, dst[0], 0, 0, border, valid};
+    return guarded([&]() -> int {
+        if (!e) {
+            int dev = 0;
+            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
+            if (rc) return rc;
+            e = default_engine(dev);
+            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        }
+        std::lock_guard<std::mutex> g(e->lock);
+        return rectify_host(e, src, sstep, dst, dstep, job);
+    });
+}
+
+int bicos_rectify_tile(int* rows, int* cols) {
+    if (rows) *rows = bicos_hip::RECTIFY_TILE_ROWS;
+    if (cols) *cols = bicos_hip::RECTIFY_TILE_COLS;
+    return BICOS_OK;
+}
+
 const char* bicos_build_info(void) {
     return "libbicos_amd: gfx950 HIP kernels (transform, mx search: FP4 MFMA Hamming products "
            "with argmin keys in the accumulator [default], LDS-broadcast popcount/argmin VALU "

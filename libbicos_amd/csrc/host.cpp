@@ -447,4 +447,84 @@ int speckle_host(bicos_engine* e, const SpeckleJob& j) {
     return rc ? rc : rc2;
 }
 
+// --------------------------------------------------------------- rectification
+
+int rectify_host(bicos_engine* e, const void* const* src, size_t src_step, void* const* dst,
+                 size_t dst_step, const RectifyJob& j) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    hipStream_t st = e->own_stream;
+    const size_t d = (size_t)j.depth;
+    const size_t src_row = (size_t)j.src_cols * d, dst_row = (size_t)j.cols * d;
+    const size_t map_row = (size_t)j.cols * sizeof(float);
+    const size_t src_plane = src_row * j.src_rows, dst_plane = dst_row * j.rows;
+    RectifyJob dj = j;  // the same job on dense staged device buffers
+    dj.src_row_pitch = (size_t)j.src_cols;
+    dj.src_plane_pitch = (size_t)j.src_cols * j.src_rows;
+    dj.dst_row_pitch = (size_t)j.cols;
+    dj.dst_plane_pitch = (size_t)j.cols * j.rows;
+    dj.map_pitch = 0;
+    Lease stage(e, e->stage, e->stage_bytes, st);
+    char *s = nullptr, *o = nullptr;
+    auto carve = [&] {
+        s = stage.take(src_plane * j.n);
+        o = stage.take(dst_plane * j.n);
+        dj.map_x = stage.take<float>((size_t)j.rows * j.cols);
+        dj.map_y = stage.take<float>((size_t)j.rows * j.cols);
+        dj.valid = j.valid ? stage.take<uint8_t>((size_t)j.rows * j.cols) : nullptr;
+    };
+    carve();
+    int rc = stage.acquire();
+    if (rc) return rc;
+    carve();
+    dj.src = s;
+    dj.dst = o;
+    for (int t = 0; t < j.n && !rc; ++t)
+        rc = check_hip(hipMemcpy2DAsync(s + t * src_plane, src_row, src[t], src_step, src_row,
+                                        (size_t)j.src_rows, hipMemcpyHostToDevice, st),
+                       "stack upload");
+    const size_t mp = j.map_pitch ? j.map_pitch : map_row;
+    if (!rc)
+        rc = check_hip(hipMemcpy2DAsync((void*)dj.map_x, map_row, j.map_x, mp, map_row,
+                                        (size_t)j.rows, hipMemcpyHostToDevice, st), "map upload");
+    if (!rc)
+        rc = check_hip(hipMemcpy2DAsync((void*)dj.map_y, map_row, j.map_y, mp, map_row,
+                                        (size_t)j.rows, hipMemcpyHostToDevice, st), "map upload");
+    if (!rc) rc = rectify_device(dj, st);
+    for (int t = 0; t < j.n && !rc; ++t)
+        rc = check_hip(hipMemcpy2DAsync(dst[t], dst_step, o + t * dst_plane, dst_row, dst_row,
+                                        (size_t)j.rows, hipMemcpyDeviceToHost, st),
+                       "stack download");
+    if (!rc && j.valid)
+        rc = check_hip(hipMemcpyAsync(j.valid, dj.valid, (size_t)j.rows * j.cols,
+                                      hipMemcpyDeviceToHost, st), "valid download");
+    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    return rc ? rc : rc2;
+}
+
+int rectify_maps_host(bicos_engine* e, const RectifyMapsJob& j,
+                      const bicos_hip::RectifyCamera& cam) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    hipStream_t st = e->own_stream;
+    const size_t pixels = (size_t)j.rows * j.cols;
+    RectifyMapsJob dj = j;
+    Lease stage(e, e->stage, e->stage_bytes, st);
+    auto carve = [&] {
+        dj.map_x = stage.take<float>(pixels);
+        dj.map_y = stage.take<float>(pixels);
+    };
+    carve();
+    int rc = stage.acquire();
+    if (rc) return rc;
+    carve();
+    rc = rectify_maps_device(dj, cam, st);
+    if (!rc)
+        rc = check_hip(hipMemcpyAsync(j.map_x, dj.map_x, pixels * sizeof(float),
+                                      hipMemcpyDeviceToHost, st), "map download");
+    if (!rc)
+        rc = check_hip(hipMemcpyAsync(j.map_y, dj.map_y, pixels * sizeof(float),
+                                      hipMemcpyDeviceToHost, st), "map download");
+    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    return rc ? rc : rc2;
+}
+
 }  // namespace bicos_impl

@@ -378,6 +378,73 @@ class Engine:
         _lib.check(rc, "bicos_speckle_device")
         return out if lab is None else (out, lab)
 
+    # ----------------------------------------------------------- rectification
+    def rectify_maps(self, K, D, R, P, size, stream=None):
+        """bicos_rectify_maps_device: the float32 lookup maps (map_x, map_y), each [rows, cols]
+        on this engine's device, of one camera for `size` = (rows, cols) output pixels -- the
+        model of cv::initUndistortRectifyMap (include/bicos_c.h "rectification"). K: 3x3
+        intrinsics, D: None or 4, 5 or 8 distortion coefficients, R: None (identity) or the 3x3
+        rectifying rotation, P: the 3x3 or 3x4 new projection matrix. Asynchronous on `stream`
+        (default: torch's current stream)."""
+        k, d, nd, r, p, p_cols, rows, cols = _lib.rectify_camera(K, D, R, P, size)
+        map_x = torch.empty((rows, cols), dtype=torch.float32, device=self.device)
+        map_y = torch.empty((rows, cols), dtype=torch.float32, device=self.device)
+        rc = self._L.bicos_rectify_maps_device(k, d, nd, r, p, p_cols, rows, cols,
+                                               map_x.data_ptr(), map_y.data_ptr(),
+                                               _stream(self.device, stream))
+        _lib.check(rc, "bicos_rectify_maps_device")
+        return map_x, map_y
+
+    def rectify(self, stack: torch.Tensor, map_x: torch.Tensor, map_y: torch.Tensor, *,
+                border: int = 0, out: Optional[torch.Tensor] = None, valid=False, stream=None):
+        """bicos_rectify_device: the planar stack [n, src_rows, src_cols] (uint8, or 16 bits in
+        an int16 / uint16 tensor) remapped bilinearly through the float32 maps [rows, cols] of
+        absolute source coordinates to a stack [n, rows, cols] of the same dtype
+        (include/bicos_c.h "rectification"); pixels whose coordinates lie outside the source get
+        `border`. Plane and row strides of `stack`, `out` and the maps may be anything (the
+        last dimension contiguous), as for match(); the result can go straight into match().
+
+        Returns the stack -- `out` if given -- or, with `valid`, the pair (stack, valid): uint8
+        [rows, cols], 1 where every tap that contributed lies in the source. `valid` may be
+        True or a contiguous uint8 tensor to fill.
+
+        The call NEVER synchronises: one launch on `stream` (default: torch's current stream)."""
+        n, src_rows, src_cols, rp, pp = _check_stack(stack)
+        dev = stack.device
+        for name, m in (("map_x", map_x), ("map_y", map_y)):
+            if m.device != dev or m.dtype != torch.float32 or m.dim() != 2 or \
+                    (m.shape[1] > 1 and m.stride(1) != 1):
+                raise ValueError("%s must be a float32 [rows, cols] tensor on %s with contiguous "
+                                 "rows" % (name, dev))
+        if tuple(map_y.shape) != tuple(map_x.shape) or \
+                (map_x.shape[0] > 1 and map_y.stride(0) != map_x.stride(0)):
+            raise ValueError("map_y must match map_x in shape and row stride")
+        rows, cols = map_x.shape
+        if n < 1 or rows < 1 or cols < 1 or src_rows < 1 or src_cols < 1:
+            raise ValueError("rectify needs a non-empty stack and non-empty maps")
+        if out is None:
+            out = torch.empty((n, rows, cols), dtype=stack.dtype, device=dev)
+        if out.device != dev or out.dtype != stack.dtype or tuple(out.shape) != (n, rows, cols) \
+                or out.stride(2) != 1:
+            raise ValueError("out must be a %s [%d, %d, %d] tensor on %s with contiguous rows"
+                             % (stack.dtype, n, rows, cols, dev))
+        val = None
+        if valid is True:
+            val = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+        elif valid is not False and valid is not None:
+            val = valid
+            _check_out(val, "valid", (rows, cols), (torch.uint8,), dev)
+        map_pitch = 4 * (map_x.stride(0) if rows > 1 else cols)
+        rc = self._L.bicos_rectify_device(
+            self._h, stack.data_ptr(), n, src_rows, src_cols,
+            # (the stride of a dimension of size one means nothing)
+            rp if src_rows > 1 else src_cols, pp if n > 1 else src_cols, _depth(stack),
+            map_x.data_ptr(), map_y.data_ptr(), map_pitch, rows, cols, out.data_ptr(),
+            out.stride(1) if rows > 1 else cols, out.stride(0) if n > 1 else cols,
+            int(border), val.data_ptr() if val is not None else None, _stream(dev, stream))
+        _lib.check(rc, "bicos_rectify_device")
+        return out if val is None else (out, val)
+
     # ----------------------------------------------------------------- stages
     def transform(self, stack: torch.Tensor, mode: int = 0, words: Optional[int] = None,
                   out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:

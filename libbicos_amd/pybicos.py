@@ -292,6 +292,60 @@ def filter_speckles(disparity, max_size, max_diff=1.0, sentinel=True):
                      removed_components=counts[3])
 
 
+def rectify_maps(K, D, R, P, size):
+    """An extension (the reference starts at rectified imagery): the float32 lookup maps
+    (map_x, map_y), each [rows, cols] for size = (rows, cols), of one camera from its
+    calibration -- K 3x3, D None or 4, 5 or 8 coefficients, R None or 3x3, P 3x3 or 3x4, what
+    cv2.stereoRectify returns -- in the model of cv2.initUndistortRectifyMap
+    (bicos_rectify_maps_host, include/bicos_c.h "rectification": on the GPU, in double)."""
+    k, d, nd, r, p, p_cols, rows, cols = _lib.rectify_camera(K, D, R, P, size)
+    map_x = np.empty((rows, cols), np.float32)
+    map_y = np.empty((rows, cols), np.float32)
+    L = _lib.lib()
+    rc = L.bicos_rectify_maps_host(k, d, nd, r, p, p_cols, rows, cols, map_x.ctypes.data,
+                                   map_y.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("BICOS rectification maps failed: " +
+                           L.bicos_last_error().decode(errors="replace"))
+    return map_x, map_y
+
+
+def rectify(stack, map_x, map_y, border=0):
+    """An extension: the images of `stack` -- a list of 2-D uint8 or uint16 arrays of one size,
+    or one [n, rows, cols] array -- remapped bilinearly through the float32 maps of absolute
+    source coordinates (rectify_maps) to the maps' size; pixels that fall outside the source
+    get `border` (bicos_rectify_host, include/bicos_c.h "rectification": on the GPU, all images
+    through one computation of the taps). Returns (rectified, valid): an [n, rows, cols] array of
+    the input dtype, ready for match(), and a uint8 [rows, cols] array that is 1 where every
+    contributing tap lies in the source."""
+    imgs = [np.ascontiguousarray(im) for im in stack]
+    if not imgs:
+        raise ValueError("Empty image stack")
+    f = imgs[0]
+    if f.ndim != 2 or f.dtype not in (np.uint8, np.uint16):
+        raise ValueError("images must be 2-D uint8 or uint16 arrays")
+    if any(im.shape != f.shape or im.dtype != f.dtype for im in imgs):
+        raise ValueError("all images must share size and type")
+    mx = np.ascontiguousarray(map_x, dtype=np.float32)
+    my = np.ascontiguousarray(map_y, dtype=np.float32)
+    if mx.ndim != 2 or mx.shape != my.shape or mx.size == 0:
+        raise ValueError("map_x and map_y must be non-empty 2-D arrays of one shape")
+    n = len(imgs)
+    rows, cols = mx.shape
+    out = np.empty((n, rows, cols), f.dtype)
+    valid = np.empty((rows, cols), np.uint8)
+    src = (ctypes.c_void_p * n)(*[im.ctypes.data for im in imgs])
+    dst = (ctypes.c_void_p * n)(*[out[t].ctypes.data for t in range(n)])
+    L = _lib.lib()
+    rc = L.bicos_rectify_host(None, src, n, f.shape[0], f.shape[1], 0, f.dtype.itemsize,
+                              mx.ctypes.data, my.ctypes.data, 0, rows, cols, dst, 0, int(border),
+                              valid.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("BICOS rectification failed: " +
+                           L.bicos_last_error().decode(errors="replace"))
+    return out, valid
+
+
 def invalid_disparity(dtype):
     """reference pybicos/__init__.py:246-252."""
     L = _lib.lib()
