@@ -57,6 +57,7 @@ struct SearchArgs {
     int chunk;              // set by launch_search
     int tiles_per_row;      // set by launch_search
     int split;              // set by launch_search: waves per col0 group scanning col1 tiles
+                            // (launch_pk_variant, search_pkp_kernel: the probe depth at a row's start)
     int tail_col0;          // set by launch_search_mx: first col0 of the tail workgroups
     int tail_T;             // set by launch_search_mx: their tiles per wave (0: no tail)
     // Compacted col0 (launch_search_mx only; nullptr: every col0 of the row). Row r matches

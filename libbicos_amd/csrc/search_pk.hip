@@ -38,8 +38,10 @@ constexpr uint32_t LUT_PB = 0x11199199u;  // left: bit 0 -> -0.5 (0x9), 1 -> +0.
 constexpr int PK_SCALE_HI = 127 + 16;     // E8M0 2^16 for the K-half-0 (col0 P) lanes
 constexpr uint32_t PK_PAD = 0x7BFF7BFFu;  // the largest finite f16 in both fields
 // search_pkp_kernel's reach test: thr = R + 33 per field, so that the saturated thr - lb is 0
-// exactly where ham_lo lies above the running minimum
+// exactly where ham_lo lies above the running minimum (a probe of words 0 and 1); R + 49 where
+// the probe is word 0 alone
 constexpr uint32_t PKP_THR = 0x00210021u;
+constexpr uint32_t PKP_THR1 = 0x00310031u;
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 typedef short i16x2 __attribute__((ext_vector_type(2)));
@@ -541,8 +543,9 @@ void search_pk_kernel(typename SearchKArgs<AG>::type ka) {
 }
 
 // The pruned 128-bit search: WORDS = 4, one pair of wide tiles per wave, lazy drops, every
-// col0 of the row (no tail, no list), main launches only; words 2 and 3 only where they can
-// matter (block_pr). ST: the right row streamed (raw_col); EOR: a shorter end of row
+// col0 of the row (no tail, no list), main launches only; a block is probed with word 0, or
+// with words 0 and 1, and the other words are multiplied only where they can matter
+// (block_pr). ST: the right row streamed (raw_col); EOR: a shorter end of row
 // (pair_update, and the end of the kernel). Prologue, lazy step and, without EOR, the end of
 // row are search_pk_kernel<4, 2, false, false, AG, true>'s.
 template <bool AG, bool ST, bool EOR>
@@ -618,13 +621,18 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     pk_bfrags<WORDS, T>(bf, row0, c0_wave, lane, cols, [](int i) { return i; });
     const int sb = h ? 127 : PK_SCALE_HI;
     v16f cb = pk_cb<WORDS>();
+    // (C kept in VGPRs: left alone the compiler re-copies it from SGPRs every block. Made opaque
+    // once, here: done in every block, each of the three block loops carries a copy of its own)
+    asm volatile("" : "+v"(cb));
 
     // lanes 0-31: tile 0, lanes 32-63: tile 1 -- running minimum, tie marker, block base of
-    // the last drop; the reach test's threshold R + 33 per field; the fallback's state
-    // (wave-uniform)
+    // the last drop; the reach test's threshold R + thr_off per field (49 at probe depth 1, 33
+    // at depth 2); the fallback's state (wave-uniform): the probe depth in descriptor words,
+    // from the launch (a.split: 1 or 2), 1 -> 2 -> 0 (the unpruned loop), never back up
     uint32_t R = PK_PAD, M = 0xFFFFFFFFu, C = 0u;
-    uint32_t thr = PK_PAD + PKP_THR;
-    bool prune_on = true;
+    int depth = a.split == 1 ? 1 : 2;
+    uint32_t thr_off = depth == 1 ? PKP_THR1 : PKP_THR;
+    uint32_t thr = PK_PAD + thr_off;
     int wblocks = 0, wreach = 0;
 
     // the lazy pair step from the two trees' results x (tile 0) / y (tile 1) in this lane half
@@ -658,7 +666,7 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         } else {
             lazy_drop(M, R, C, comb, diff, B);
         }
-        thr = R + PKP_THR;
+        thr = R + thr_off;
     };
 
     const bool idle = c0_wave >= cols;  // wave-uniform; still joins the barriers
@@ -711,8 +719,6 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         // a block in full, at col1 B, the step's block bi: the partial last block (pad) and the
         // fallback's loop
         auto block = [&](uint32_t ad, int B, int bi, bool pad) {
-            // (C kept in VGPRs: left alone the compiler re-copies it from SGPRs every block)
-            asm volatile("" : "+v"(cb));
             v4i af[WORDS];
 #pragma unroll
             for (int w = 0; w < WORDS; ++w) af[w] = frag(ad, w);
@@ -742,44 +748,68 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         // of 16) send it to the unpruned loop for the rest of the row. (Lazy drops stay under
         // pruning: with the drop branch in the reaching blocks instead of the rescans the fused
         // cfg2 launch took 313.8 instead of 276.2 us.)
+        // Probe depth 1 (D = 1): one scaled MFMA multiplies exactly one descriptor word, so the
+        // block can be tested after word 0 alone. After that MFMA both fields of every
+        // accumulator hold 0x4B00 + 48 + ham_0 (C carries + 64, word 0 adds ham_0 - 16), and
+        // the final field is 0x4B00 + ham with ham >= ham_lo >= ham_0. The packed tree of these
+        // keys, combined over the lane halves, is tested per field against thr = R + 0x00310031
+        // as unsigned 16-bit integers by the same saturating subtraction, thr - key != 0
+        // (neither field of thr wraps: R <= 0x7BFF, and 0x7BFF + 0x31 < 2^16): reach is ham_0
+        // <= running minimum, "<=" because a tie must never be pruned. A tile none of whose 64
+        // col0 reaches skips its MFMAs of words 1, 2 and 3 and its second tree, and enters the
+        // pair step, if the other tile takes one, with its word-0 keys. That is safe under lazy
+        // drops for the same reason: a tile-block pruned at depth 1 has ham >= ham_0 > R for
+        // every col0 and every column of the block, and R only falls, so the block is neither
+        // a drop nor a tie now or later; its word-0 keys, 0x4B00 + 48 + ham_0, lie above R in
+        // every field too, so all they can give M is a positive value, which never decides
+        // anything. A tile that reaches takes words 1-3 at once and the full tree. The window
+        // rule is the same at both depths: at depth 1 a wave 14 of whose 16 wide-tile-blocks
+        // reach goes on at depth 2 (thr = R + 33) for the rest of the row, and from depth 2 to
+        // the unpruned loop; it never goes back up. Noisy rows so pay one window more than
+        // they did.
         // af0 holds the block's word-0 fragment on entry and the next block's on return, read
         // once the probe products are issued; the other words' fragments are read here, at the
         // top of the block, and ad then steps by d bytes to the next block.
-        auto block_pr = [&](int B, uint32_t& ad, v4i& af0, int d) {
-            asm volatile("" : "+v"(cb));
-            const v4i af1 = frag(ad, 1);
-            // (words 2 and 3 read here too: read only in the blocks that reach, the fused
-            // cfg2 launch took 275.9 instead of 273.5 us)
-            const v4i af2 = frag(ad, 2);
-            const v4i af3 = frag(ad, 3);
+        auto block_pr = [&](auto depth_tag, int B, uint32_t& ad, v4i& af0, int d) {
+            constexpr int D = decltype(depth_tag)::value;  // the probe's words
+            // (the words behind the probe read here too: words 2 and 3 read only in the blocks
+            // that reach, the fused cfg2 launch took 275.9 instead of 273.5 us at depth 2)
+            v4i af[WORDS];
+            af[0] = af0;
+#pragma unroll
+            for (int w = 1; w < WORDS; ++w) af[w] = frag(ad, w);
             // (one v_add_u32 with the scalar step: kept a value of its own, or the compiler
             // rebuilds the address of every word from the scalar block offset)
             ad += (uint32_t)d;
             asm volatile("" : "+v"(ad));
-            v16f dx = mfma_pk(af0, bf[0][0], cb, sb);
-            v16f dy = mfma_pk(af0, bf[1][0], cb, sb);
-            dx = mfma_pk(af1, bf[0][1], dx, sb);
-            dy = mfma_pk(af1, bf[1][1], dy, sb);
+            v16f dx = mfma_pk(af[0], bf[0][0], cb, sb);
+            v16f dy = mfma_pk(af[0], bf[1][0], cb, sb);
+#pragma unroll
+            for (int w = 1; w < D; ++w) {
+                dx = mfma_pk(af[w], bf[0][w], dx, sb);
+                dy = mfma_pk(af[w], bf[1][w], dy, sb);
+            }
             // (both tiles' probe products go out before the first key is read)
             __builtin_amdgcn_sched_barrier(0);
             af0 = frag(ad, 0);
             uint32_t x = pk_tree(dx), y = pk_tree(dy);
             const auto sw = __builtin_amdgcn_permlane32_swap(x, y, false, false);
-            // ham_lo <= running minimum in either field, as u16 ("<=": a tie reaches): thr
-            // is R + 33, so the saturated thr - lb is 0 exactly where lb > R + 32
+            // the probe's distance <= running minimum in either field, as u16 ("<=": a tie
+            // reaches): thr is R + 49 / R + 33, so the saturated thr - lb is 0 exactly where lb
+            // > R + 48 / R + 32
             const uint64_t bal = __builtin_amdgcn_ballot_w64(pksubsat(thr, pkminu(sw[0], sw[1])) != 0u);
             if (bal) {
                 uint32_t lo = (uint32_t)bal, hi = (uint32_t)(bal >> 32);
                 asm volatile("" : "+s"(lo), "+s"(hi));
                 if (lo) {
-                    dx = mfma_pk(af2, bf[0][2], dx, sb);
-                    dx = mfma_pk(af3, bf[0][3], dx, sb);
+#pragma unroll
+                    for (int w = D; w < WORDS; ++w) dx = mfma_pk(af[w], bf[0][w], dx, sb);
                     x = pk_tree(dx);
                     ++wreach;
                 }
                 if (hi) {
-                    dy = mfma_pk(af2, bf[1][2], dy, sb);
-                    dy = mfma_pk(af3, bf[1][3], dy, sb);
+#pragma unroll
+                    for (int w = D; w < WORDS; ++w) dy = mfma_pk(af[w], bf[1][w], dy, sb);
                     y = pk_tree(dy);
                     ++wreach;
                 }
@@ -802,25 +832,39 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         // a window sends the wave to the unpruned loop below for the rest of the row. Shaped
         // as search_mx_kernel's: an inner run of blocks up to the window's end that only steps
         // the (wrapping) block offset, the next block's word-0 fragment read unconditionally
-        // (behind the last block: the wrapped offset, a block nobody uses)
+        // (behind the last block: the wrapped offset, a block nobody uses). The run is at the
+        // wave's probe depth; a window that falls at depth 1 goes on here at depth 2
         int i0 = 0;
-        if (prune_on && nfull > 0) {
+        if (depth && nfull > 0) {
             v4i af0 = frag(ad, 0);
             while (i0 < nfull) {
                 int n = min(nfull - i0, PRUNE_WINDOW - wblocks);
                 i0 += n;
                 wblocks += n;
-                for (; n > 0; --n) {
-                    const int d = so > 0 ? -512 : wrap;
-                    block_pr(Bs + (so >> 4), ad, af0, d);
-                    so += d;
+                if (depth == 1) {
+                    for (; n > 0; --n) {
+                        const int d = so > 0 ? -512 : wrap;
+                        block_pr(std::integral_constant<int, 1>{}, Bs + (so >> 4), ad, af0, d);
+                        so += d;
+                    }
+                } else {
+                    for (; n > 0; --n) {
+                        const int d = so > 0 ? -512 : wrap;
+                        block_pr(std::integral_constant<int, 2>{}, Bs + (so >> 4), ad, af0, d);
+                        so += d;
+                    }
                 }
                 if (wblocks == PRUNE_WINDOW) {
                     const bool fall = 8 * wreach >= 7 * PRUNE_WINDOW * T;
                     wblocks = wreach = 0;
                     if (fall) {
-                        prune_on = false;
-                        break;
+                        if (depth == 2) {
+                            depth = 0;
+                            break;
+                        }
+                        depth = 2;
+                        thr_off = PKP_THR;
+                        thr = R + thr_off;
                     }
                 }
             }
@@ -971,6 +1015,15 @@ bool pkp_eor() {
     }();
     return on;
 }
+// search_pkp_kernel's probe depth at the start of a row, in descriptor words (block_pr): 1, or
+// with BICOS_PKP_PROBE=2 the two-word probe from the first block on (read once)
+int pkp_probe() {
+    static const int depth = [] {
+        const char* v = std::getenv("BICOS_PKP_PROBE");
+        return v && !std::strcmp(v, "2") ? 2 : 1;
+    }();
+    return depth;
+}
 
 }  // namespace
 
@@ -985,11 +1038,15 @@ hipError_t launch_pk_variant(const SearchLaunch& l, const SearchArgs& a, const A
         if (!v.prune || !v.lazy || v.words != 4 || v.T != 2 || v.tail || v.list) return hipErrorInvalidValue;
         // (the streamed instantiations are built for one chunk: two columns per thread)
         if (v.stream && (a.chunk != PKP_ST_CHUNK || l.block * 2 != PKP_ST_CHUNK)) return hipErrorInvalidValue;
+        // (the start depth travels in `split`, which only the VALU search's launch reads: a field
+        // of its own would move the agree's arguments in every fused kernel)
+        SearchArgs ap = a;
+        ap.split = pkp_probe();
         // clang-format off
         return pick<bool, false, true>(v.agree, [&](auto agree) {
         return pick<bool, false, true>(v.stream, [&](auto stream) {
         return pick<bool, false, true>(pkp_eor(), [&](auto eor) {
-            return launch_planned<agree.value>(search_pkp_kernel<agree.value, stream.value, eor.value>, l, a, ag, st);
+            return launch_planned<agree.value>(search_pkp_kernel<agree.value, stream.value, eor.value>, l, ap, ag, st);
         }); }); });
         // clang-format on
     }

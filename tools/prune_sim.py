@@ -11,8 +11,15 @@ skips the block; the simulation checks that the minima and the last minima then 
 the full scan's. With --fallback the wave's window rule is simulated too (PRUNE_WINDOW blocks,
 >= 7/8 of the pair-blocks reaching sends the wave to the unpruned loop for the rest of the row).
 
+--probe-words D simulates the packed kernel instead (search_pk.hip search_pkp_kernel): units
+are its wide tiles (64 col0, two per wave), the probe is the first D 32-bit descriptor words
+from --lo-bits on, and a wave starts at depth D and follows the chain 1 -> 2 -> unpruned under
+the same window rule (a wave never goes back up). It prints the reach rate per depth, the
+waves that left each depth, and the scaled MFMAs and trees per wave-block that follow (probe
+2 D, + (4 - D) per reaching tile; trees 2, + 1 per reaching tile; unpruned 8 and 2).
+
   python tools/prune_sim.py [--rows 0 500 767 1535] [--W 2048] [--flip 0 0.02 0.05 0.1]
-                            [--random] [--lo-bits 0] [--fallback]
+                            [--random] [--lo-bits 0] [--fallback] [--probe-words 1] [--window1 8]
 """
 import argparse
 import os
@@ -82,6 +89,64 @@ def simulate(C, Clo, cols, unit_tiles, fallback, waves=8, T=4, chunk=1024):
     return units, reach, second, nwaves, fell
 
 
+def simulate_chain(C, Cw, cols, depth0, window1=PRUNE_WINDOW, waves=8, chunk=1024):
+    """The packed kernel's chain. Cw[d]: costs over the first d words (d = 1, 2). -> int64[11]:
+    wave-blocks, wide-tile-blocks, tile-blocks tested and reaching at depth 1, at depth 2,
+    MFMAs, trees, waves that left depth 1, waves that left depth 2, pruned wave-blocks with a
+    reaching tile"""
+    out = np.zeros(11, np.int64)
+    per_wg = waves * 128
+    full_min = C.min(axis=1)
+    for wg in range((cols + per_wg - 1) // per_wg):
+        for w in range(waves):
+            c0_wave = wg * per_wg + w * 128
+            if c0_wave >= cols:
+                continue
+            blocks = order_current(c0_wave, (wg + 1) * per_wg - 1, cols, chunk)
+            spans = [(lo, min(cols, lo + 64)) for lo in (c0_wave, c0_wave + 64) if lo < cols]
+            run = {s: np.full(s[1] - s[0], 1 << 30) for s in spans}
+            last = {s: np.full(s[1] - s[0], -1) for s in spans}
+            depth, wb, wr = depth0, 0, 0
+            for B in blocks:
+                e = min(cols, B + 32)
+                d = depth if e - B == 32 else 0  # the partial last block never prunes
+                out[0] += 1
+                any_reach = False
+                out[6] += 8 if d == 0 else 2 * d   # both tiles' slots run (an idle tile too)
+                out[7] += 2
+                for s in spans:
+                    out[1] += 1
+                    c = C[s[0]:s[1], B:e]
+                    bm = c.min(axis=1)
+                    r = d == 0 or bool((Cw[d][s[0]:s[1], B:e].min(axis=1) <= run[s]).any())
+                    if d:
+                        out[2 * d] += 1
+                        out[2 * d + 1] += r
+                        wr += r
+                        any_reach |= r
+                        out[6] += (4 - d) * r
+                        out[7] += r
+                    if r:
+                        arg = B + c.shape[1] - 1 - np.argmin(c[:, ::-1], axis=1)
+                        take = (bm < run[s]) | ((bm == run[s]) & (arg > last[s]))
+                        last[s] = np.where(take, arg, last[s])
+                        run[s] = np.minimum(run[s], bm)
+                if d:
+                    out[10] += any_reach
+                    wb += 1
+                    win = window1 if depth == 1 else PRUNE_WINDOW
+                    if wb == win:
+                        if 8 * wr >= 7 * win * 2:
+                            out[7 + depth] += 1
+                            depth = 2 if depth == 1 else 0
+                        wb = wr = 0
+            for s in spans:  # pruning changed nothing
+                assert (run[s] == full_min[s[0]:s[1]]).all()
+                want = cols - 1 - np.argmin(C[s[0]:s[1], ::-1], axis=1)
+                assert (last[s] == want).all()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, nargs="+", default=[0, 500, 767, 1535])
@@ -91,11 +156,15 @@ def main():
     ap.add_argument("--random", action="store_true")
     ap.add_argument("--lo-bits", type=int, default=0, help="first bit of the 64-bit partial subset")
     ap.add_argument("--fallback", action="store_true")
+    ap.add_argument("--probe-words", type=int, default=0, choices=[0, 1, 2],
+                    help="the packed kernel's chain from this probe depth (0: the one-product kernel)")
+    ap.add_argument("--window1", type=int, default=PRUNE_WINDOW, help="the chain's window at depth 1, in blocks")
     args = ap.parse_args()
     H = 1536
     for flip in ([0.0] if args.random else args.flip):
         tot = {1: np.zeros(5, np.int64), 2: np.zeros(5, np.int64)}
         med = []
+        chain = np.zeros(11, np.int64)
         for r in args.rows:
             if args.random:
                 L = random_stack(args.n, 1, args.W, seed=int(r) + 1)
@@ -108,11 +177,23 @@ def main():
             nb = b0.shape[-1]
             sel = (np.arange(64) + args.lo_bits) % nb
             C = costs(pack(b0), pack(b1))
+            if args.probe_words:
+                Cw = {d: costs(pack(b0[:, sel[:32 * d]]), pack(b1[:, sel[:32 * d]])) for d in (1, 2)}
+                chain = chain + simulate_chain(C, Cw, args.W, args.probe_words, args.window1)
+                continue
             Clo = costs(pack(b0[:, sel]), pack(b1[:, sel]))
             med.append(float(np.median(C.min(axis=1))))
             for ut in (1, 2):
                 tot[ut] += np.array(simulate(C, Clo, args.W, ut, args.fallback))
         name = "random" if args.random else "flip %.2f" % flip
+        if args.probe_words:
+            wb, tb, t1, r1, t2, r2, mf, tr, f1, f2, wr = chain
+            print("%-10s start depth %d: depth 1 reach %.3f of %d tile-blocks, depth 2 reach %.3f of %d, "
+                  "%.3f of pruned wave-blocks hold a reaching tile; per wave-block %.3f scaled MFMAs, "
+                  "%.3f trees; waves leaving depth 1: %d, depth 2: %d" % (
+                      name, args.probe_words, r1 / max(1, t1), t1, r2 / max(1, t2), t2,
+                      wr / max(1, (t1 + t2) // 2), mf / wb, tr / wb, f1, f2))
+            continue
         for ut, label in ((1, "tile"), (2, "pair")):
             u, rch, sec, nw, fell = tot[ut]
             # (partial reach counts the blocks tested while pruning: after a wave falls back its
