@@ -491,6 +491,59 @@ int bicos_rectify_host(bicos_engine* e, const void* const* src, int n, int src_r
 /* The tile (rows, cols) of output pixels one workgroup remaps (tests). Returns BICOS_OK. */
 int bicos_rectify_tile(int* rows, int* cols);
 
+/* ---------------------------------------------------------- median filter */
+/* The 3x3 or 5x5 median of a dense rows x cols disparity map (BICOS_CV_16S or BICOS_CV_32F), on
+ * the GPU, that knows the map's invalid values and can fill small holes. The reference has no
+ * such step. Parameters: ksize in {3, 5}, fill_min, flags.
+ *     valid pixel  as in the speckle filter: an int16 that is not -32768; a float that is not
+ *                  NaN and, with BICOS_MEDIAN_F32_SENTINEL, not -32768.0f either. Infinities
+ *                  are valid.
+ *     window of p  the ksize x ksize pixels centred on p that lie inside the image. There is no
+ *                  border replication: a clipped window is simply smaller. V(p) is the multiset
+ *                  of the valid values in the window, m = |V(p)|.
+ *     order        int16 values as integers; floats by the integer key
+ *                      k = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000)
+ *                  compared unsigned: numeric order with -0.0 before +0.0, a total order on
+ *                  every valid float. So the result is one definite element of V, whose bits
+ *                  are copied.
+ *     median(p)    the element of rank floor((m - 1) / 2), 0-based, of V sorted in that order:
+ *                  the lower median, and the median for odd m.
+ *     output       p valid on input: out(p) = median(p) (m >= 1: p is in its own window).
+ *                  p invalid on input, fill_min > 0 and m >= fill_min: out(p) = median(p); the
+ *                  hole is filled.
+ *                  Otherwise p is copied bit for bit. The filter never creates an invalid pixel
+ *                  and never changes one that it does not fill.
+ *     fill_min     0: no filling; else 1 .. ksize*ksize. ksize*ksize/2 + 1 fills only holes
+ *                  that valid pixels surround.
+ * Outputs:
+ *     out     same type and shape as the map. On the device entry it must not overlap the map
+ *             (the filter reads neighbours): any overlap is an argument error. On the host
+ *             entry out may be the input buffer.
+ *     counts  optional, uint32[4]: {unchanged, changed, filled, invalid} = valid on input and
+ *             the output bits equal the input bits; valid on input and they differ; invalid on
+ *             input and valid on output; invalid on input and copied. They sum to rows*cols.
+ * The results are exact and deterministic: integers and copied bits.
+ * rows*cols must fit int32. rows == 0 or cols == 0 is legal (counts all zero, nothing launched).
+ * Argument errors (a type other than 16S / 32F, a ksize other than 3 or 5, a fill_min outside
+ * 0 .. ksize*ksize, unknown flag bits, a negative size, too many pixels, a NULL map or out on a
+ * non-empty map, an overlap of map and out on the device entry) are BICOS_E_ARG before any HIP
+ * call.
+ * Where every pixel of a window is valid and inside the image, the result is that pixel of
+ * cv::medianBlur(map, ksize) -- a statement from reading that function's definition (the
+ * median of the ksize x ksize neighbourhood; for 16-bit and float images it offers exactly
+ * the apertures 3 and 5), not from a test against it. At the border cv::medianBlur replicates
+ * pixels where this filter clips the window. */
+#define BICOS_MEDIAN_F32_SENTINEL 1
+/* device: asynchronous on `stream`. Needs no workspace: e may be NULL. */
+int bicos_median_device(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                        int ksize, int fill_min, int flags, void* out, uint32_t* counts, void* stream);
+/* host buffers, synchronous, e NULL = default engine: uploads the map, runs the same launch,
+ * downloads the map and the counts. */
+int bicos_median_host(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                      int ksize, int fill_min, int flags, void* out, uint32_t counts[4]);
+/* The output tile (rows, cols) of one workgroup (tests). Returns BICOS_OK. */
+int bicos_median_tile(int* rows, int* cols);
+
 /* Build identification (arch, flags) for reports. */
 const char* bicos_build_info(void);
 

@@ -65,6 +65,7 @@ EXPORTS = (
     "bicos_speckle_device", "bicos_speckle_host", "bicos_speckle_tile",
     "bicos_rectify_maps_device", "bicos_rectify_maps_host", "bicos_rectify_device",
     "bicos_rectify_host", "bicos_rectify_tile",
+    "bicos_median_device", "bicos_median_host", "bicos_median_tile",
 )
 
 # bicos_match_plan bits (include/bicos_c.h)
@@ -82,6 +83,9 @@ REPROJECT_F32_SENTINEL = 2
 
 # bicos_speckle_* flag (include/bicos_c.h)
 SPECKLE_F32_SENTINEL = 1
+
+# bicos_median_* flag (include/bicos_c.h)
+MEDIAN_F32_SENTINEL = 1
 
 
 def build(verbose: bool = False, jobs: int = 4) -> str:
@@ -203,6 +207,12 @@ def lib() -> ctypes.CDLL:
     L.bicos_rectify_host.restype = I
     L.bicos_rectify_tile.argtypes = [PI, PI]
     L.bicos_rectify_tile.restype = I
+    L.bicos_median_device.argtypes = [P, P, I, I, I, I, I, I, P, P, P]
+    L.bicos_median_device.restype = I
+    L.bicos_median_host.argtypes = [P, P, I, I, I, I, I, I, P, P]
+    L.bicos_median_host.restype = I
+    L.bicos_median_tile.argtypes = [PI, PI]
+    L.bicos_median_tile.restype = I
     L.bicos_build_info.restype = ctypes.c_char_p
     L.bicos_build_info.argtypes = []
     _lib = L
@@ -259,6 +269,27 @@ def speckle_tile():
     """(rows, cols) of the tile one workgroup labels (bicos_speckle_tile)."""
     r, c = ctypes.c_int(0), ctypes.c_int(0)
     lib().bicos_speckle_tile(ctypes.byref(r), ctypes.byref(c))
+    return r.value, c.value
+
+
+def median_params(ksize, fill_min):
+    """(int ksize, int fill_min) as the bicos_median_* entries take them (ValueError for what
+    they would refuse: a ksize other than 3 or 5, a fill_min outside 0 .. ksize * ksize)."""
+    try:
+        k, f = int(ksize), int(fill_min)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("ksize and fill_min must be integers, got %r, %r" % (ksize, fill_min))
+    if k != ksize or k not in (3, 5):
+        raise ValueError("ksize must be 3 or 5, got %r" % (ksize,))
+    if f != fill_min or f < 0 or f > k * k:
+        raise ValueError("fill_min must be an integer in [0, %d], got %r" % (k * k, fill_min))
+    return k, f
+
+
+def median_tile():
+    """(rows, cols) of the output tile of one workgroup (bicos_median_tile)."""
+    r, c = ctypes.c_int(0), ctypes.c_int(0)
+    lib().bicos_median_tile(ctypes.byref(r), ctypes.byref(c))
     return r.value, c.value
 
 

@@ -55,6 +55,12 @@ const char* USAGE =
     "                          saved and reprojected (default: off)\n"
     "      --speckle-diff F    largest disparity difference of two neighbours in one region\n"
     "                          (1; only with --speckle-size)\n"
+    "      --median K          median filter: K x K (3 or 5) median over the valid disparities\n"
+    "                          of each pixel's window, after --speckle-size and before the\n"
+    "                          disparity is saved and reprojected (default: off)\n"
+    "      --median-fill M     also fill an invalid pixel whose window holds at least M valid\n"
+    "                          disparities (K*K/2 + 1: only surrounded holes; 0: none; only\n"
+    "                          with --median)\n"
     "      --rectify FILE      the inputs are raw frames: OpenCV FileStorage (YAML/XML) with\n"
     "                          the matrices M1 D1 R1 P1 M2 D2 R2 P2 of cv::stereoRectify;\n"
     "                          both stacks are rectified to their own size before the match.\n"
@@ -82,7 +88,7 @@ Args parse(int argc, char** argv) {
         {"stacksize", true}, {"qmatrix", true}, {"lr-maxdiff", true}, {"help", false},
         {"allow-negative-z", false}, {"double", false}, {"limited", false},
         {"corrmap", false}, {"no-dupes", false}, {"speckle-size", true}, {"speckle-diff", true},
-        {"rectify", true}};
+        {"rectify", true}, {"median", true}, {"median-fill", true}};
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i];
@@ -266,6 +272,24 @@ int run(int argc, char** argv) {
                   << " regions" << std::endl;
     } else if (args.has("speckle-diff")) {
         std::cerr << "'speckle-diff' has no effect without 'speckle-size'.\n";
+    }
+
+    if (args.has("median")) {
+        // on the GPU, after the speckle filter (islands are gone before anything can be filled
+        // from them), with the flags of that call and of the reprojection below
+        const unsigned ksize = as_uint(args, "median");
+        const unsigned fill_min = args.has("median-fill") ? as_uint(args, "median-fill") : 0u;
+        if (ksize != 3 && ksize != 5) throw std::invalid_argument("--median: K must be 3 or 5");
+        if (fill_min > ksize * ksize)
+            throw std::invalid_argument("--median-fill: M must lie in 0 .. K * K");
+        uint32_t counts[4] = {0, 0, 0, 0};  // unchanged, changed, filled, invalid
+        if (bicos_median_host(nullptr, disp.data(), disp.type(), disp.rows(), disp.cols(),
+                              (int)ksize, (int)fill_min, 0, disp.data(), counts) != BICOS_OK)
+            throw std::runtime_error(std::string("median filter failed: ") + bicos_last_error());
+        std::cout << "Median filter:\tchanged " << counts[1] << " pixels, filled " << counts[2]
+                  << std::endl;
+    } else if (args.has("median-fill")) {
+        std::cerr << "'median-fill' has no effect without 'median'.\n";
     }
 
     save_image(disp, outfile, bicos_cli::Colormap::Turbo);

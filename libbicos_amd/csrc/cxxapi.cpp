@@ -5,6 +5,7 @@
 //   BICOS::reproject  (bicos/reproject.hpp; no reference counterpart in its library)
 //   BICOS::filter_speckles  (bicos/speckle.hpp; no reference counterpart)
 //   BICOS::rectify_maps, BICOS::rectify  (bicos/rectify.hpp; no reference counterpart)
+//   BICOS::median_filter  (bicos/median.hpp; no reference counterpart)
 #include "engine.hpp"
 
 #include <algorithm>
@@ -19,6 +20,7 @@
 #include "../../include/bicos/reproject.hpp"
 #include "../../include/bicos/speckle.hpp"
 #include "../../include/bicos/rectify.hpp"
+#include "../../include/bicos/median.hpp"
 
 using bicos_impl::check_hip;
 
@@ -358,6 +360,58 @@ SpeckleStats filter_speckles(const Image& disparity, Image& out, int max_size, f
                                          hipMemcpyDeviceToHost), "labels download"));
     }
     return SpeckleStats{counts[0], counts[1], counts[2], counts[3]};
+}
+
+// ------------------------------------------------------------ BICOS::median_filter
+// over the C entries (entries.cpp), which validate and launch
+
+namespace {
+
+void check_median_map(const Image& disparity) {
+    if (disparity.type() != S16 && disparity.type() != F32)
+        throw Exception("median_filter: the disparity map must be S16 or F32");
+    if (disparity.step() != (size_t)disparity.cols() * disparity.elemSize() && disparity.rows() > 1)
+        throw Exception("median_filter: the disparity map must be dense");
+}
+
+}  // namespace
+
+void median_filter(const Image& disparity, Image& out, int ksize, int fill_min, int flags,
+                   uint32_t* counts, hipStream_t stream) {
+    check_median_map(disparity);
+    if (disparity.memory() != Memory::Device)
+        throw Exception("median_filter: device buffers need a device map");
+    if (&out == &disparity)
+        throw Exception("median_filter: a device map cannot be filtered in place");
+    const int rows = disparity.rows(), cols = disparity.cols(), type = disparity.type();
+    out.create(rows, cols, type, Memory::Device);
+    throw_rc(bicos_median_device(current_engine(), disparity.data(), type, rows, cols, ksize,
+                                 fill_min, flags, out.data(), counts, stream));
+}
+
+MedianStats median_filter(const Image& disparity, Image& out, int ksize, int fill_min, int flags) {
+    check_median_map(disparity);
+    const void* map = disparity.data();  // (a host out may be the same header)
+    const int rows = disparity.rows(), cols = disparity.cols(), type = disparity.type();
+    const Memory mem = disparity.memory();
+    uint32_t counts[4] = {0, 0, 0, 0};
+    if (mem == Memory::Host) {
+        out.create(rows, cols, type, mem);
+        throw_rc(bicos_median_host(nullptr, map, type, rows, cols, ksize, fill_min, flags,
+                                   out.data(), counts));
+    } else {
+        if (&out == &disparity)
+            throw Exception("median_filter: a device map cannot be filtered in place");
+        out.create(rows, cols, type, mem);
+        void* raw = nullptr;
+        throw_rc(check_hip(hipMalloc(&raw, sizeof counts), "hipMalloc(counts)"));
+        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
+        throw_rc(bicos_median_device(current_engine(), map, type, rows, cols, ksize, fill_min,
+                                     flags, out.data(), (uint32_t*)raw, nullptr));
+        throw_rc(check_hip(hipMemcpy(counts, raw, sizeof counts, hipMemcpyDeviceToHost),
+                           "counts download"));
+    }
+    return MedianStats{counts[0], counts[1], counts[2], counts[3]};
 }
 
 // ------------------------------------------------- BICOS::rectify_maps, BICOS::rectify

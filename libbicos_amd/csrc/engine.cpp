@@ -7,6 +7,7 @@
 #include "engine.hpp"
 #include "reproject.hpp"
 #include "speckle.hpp"
+#include "median.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -656,6 +657,47 @@ int speckle_device(bicos_engine* e, const SpeckleJob& j, hipStream_t st) {
     carve();
     return check_hip(bicos_hip::launch_speckle(a, j.disp_type == BICOS_CV_32F, st),
                      "speckle launches");
+}
+
+// ------------------------------------------------------------- median filter
+
+int check_median(const MedianJob& j, bool device) {
+    if (j.disp_type != BICOS_CV_16S && j.disp_type != BICOS_CV_32F)
+        return fail(BICOS_E_ARG, "median: the disparity map must be CV_16S or CV_32F");
+    if (j.ksize != 3 && j.ksize != 5) return fail(BICOS_E_ARG, "median: ksize must be 3 or 5");
+    if (j.fill_min < 0 || j.fill_min > j.ksize * j.ksize)
+        return fail(BICOS_E_ARG, "median: fill_min must lie in 0 .. ksize * ksize");
+    if (j.flags & ~BICOS_MEDIAN_F32_SENTINEL)
+        return fail(BICOS_E_ARG, "median: unknown flag bits");
+    if (j.rows < 0 || j.cols < 0) return fail(BICOS_E_ARG, "median: negative image size");
+    if ((int64_t)j.rows * j.cols > INT32_MAX)
+        return fail(BICOS_E_ARG, "median: rows * cols exceeds int32");
+    if (j.rows > 0 && j.cols > 0) {
+        if (!j.disp) return fail(BICOS_E_ARG, "median: null disparity map");
+        if (!j.out) return fail(BICOS_E_ARG, "median: null out");
+        const uintptr_t a = (uintptr_t)j.disp, b = (uintptr_t)j.out;
+        const uintptr_t bytes = (uintptr_t)j.rows * j.cols * (j.disp_type == BICOS_CV_32F ? 4 : 2);
+        if (device && a < b + bytes && b < a + bytes)
+            return fail(BICOS_E_ARG, "median: out overlaps the map (the filter reads neighbours)");
+    }
+    return BICOS_OK;
+}
+
+int median_device(const MedianJob& j, hipStream_t st) {
+    if ((size_t)j.rows * j.cols == 0)  // nothing to launch: the counts are all zero
+        return j.counts ? check_hip(hipMemsetAsync(j.counts, 0, 4 * sizeof(uint32_t), st),
+                                    "hipMemsetAsync(counts)")
+                        : (int)BICOS_OK;
+    bicos_hip::MedianArgs a{};
+    a.disp = j.disp;
+    a.out = j.out;
+    a.rows = j.rows;
+    a.cols = j.cols;
+    a.fill_min = j.fill_min;
+    a.flags = j.flags;
+    a.counts = j.counts;
+    return check_hip(bicos_hip::launch_median(a, j.disp_type == BICOS_CV_32F, j.ksize, st),
+                     "median launch");
 }
 
 // ------------------------------------------------------------- rectification

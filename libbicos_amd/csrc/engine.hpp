@@ -7,12 +7,13 @@
 //   engine.cpp  errors, the workspace lease, engine resources, the plans, the search driver
 //               and match_device; reproject_device (disparity map -> 3-D points);
 //               speckle_device (the speckle filter of a disparity map); rectify_device and
-//               rectify_maps_device (raw stacks -> rectified stacks)
+//               rectify_maps_device (raw stacks -> rectified stacks); median_device (the
+//               median filter of a disparity map)
 //   host.cpp    the banded host-buffer pipeline (HostPool, match_host); reproject_host;
-//               speckle_host; rectify_host, rectify_maps_host
+//               speckle_host; rectify_host, rectify_maps_host; median_host
 //   entries.cpp the bicos_* extern "C" entries (bicos_c.h) but the multi-GPU ones
 //   multi.cpp   bicos_match_host_multi, bicos_match_bands_device
-//   cxxapi.cpp  namespace BICOS (HipImage, match, reproject, filter_speckles)
+//   cxxapi.cpp  namespace BICOS (HipImage, match, reproject, filter_speckles, median_filter)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -315,6 +316,24 @@ int speckle_device(bicos_engine* e, const SpeckleJob& j, hipStream_t st);
 // Host buffers: the map uploaded into the engine's staging, the same launches on the engine's
 // own stream, the map, the counts and the labels downloaded. Synchronous.
 int speckle_host(bicos_engine* e, const SpeckleJob& j);
+
+// One median filter (bicos_c.h "median filter"): the arguments of bicos_median_device /
+// bicos_median_host, the pointers all in device or all in host memory.
+struct MedianJob {
+    const void* disp;
+    int disp_type, rows, cols;
+    int ksize, fill_min, flags;
+    void* out;
+    uint32_t* counts;
+};
+// BICOS_E_ARG (with a message) for what the entries refuse; no HIP call. device: any overlap
+// of map and out is an error (the host entry stages both, so its out may be the map).
+int check_median(const MedianJob& j, bool device);
+// The launch on `st` (validated arguments). It needs nothing of an engine.
+int median_device(const MedianJob& j, hipStream_t st);
+// Host buffers: the map uploaded into the engine's staging, the same launch on the engine's
+// own stream, the map and the counts downloaded. Synchronous.
+int median_host(bicos_engine* e, const MedianJob& j);
 
 // One remap of a stack (bicos_c.h "rectification"): the arguments of bicos_rectify_device, the
 // pointers all in device memory, the stack pitches in elements, map_pitch in bytes (0 = dense).

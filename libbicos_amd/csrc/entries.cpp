@@ -3,6 +3,7 @@
 #include "engine.hpp"
 #include "reproject.hpp"
 #include "speckle.hpp"
+#include "median.hpp"
 
 #include <cmath>
 #include <vector>
@@ -482,6 +483,38 @@ int bicos_rectify_host(bicos_engine* e, const void* const* src, int n, int src_r
 int bicos_rectify_tile(int* rows, int* cols) {
     if (rows) *rows = bicos_hip::RECTIFY_TILE_ROWS;
     if (cols) *cols = bicos_hip::RECTIFY_TILE_COLS;
+    return BICOS_OK;
+}
+
+int bicos_median_device(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                        int ksize, int fill_min, int flags, void* out, uint32_t* counts,
+                        void* stream) {
+    const MedianJob job{disparity, disp_type, rows, cols, ksize, fill_min, flags, out, counts};
+    if (int rc0 = check_median(job, true)) return rc0;
+    (void)e;  // no workspace: nothing of the engine is used, so it may be NULL and is not locked
+    return guarded([&]() -> int { return median_device(job, (hipStream_t)stream); });
+}
+
+int bicos_median_host(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                      int ksize, int fill_min, int flags, void* out, uint32_t counts[4]) {
+    const MedianJob job{disparity, disp_type, rows, cols, ksize, fill_min, flags, out, counts};
+    if (int rc0 = check_median(job, false)) return rc0;
+    return guarded([&]() -> int {
+        if (!e) {
+            int dev = 0;
+            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
+            if (rc) return rc;
+            e = default_engine(dev);
+            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        }
+        std::lock_guard<std::mutex> g(e->lock);
+        return median_host(e, job);
+    });
+}
+
+int bicos_median_tile(int* rows, int* cols) {
+    if (rows) *rows = bicos_hip::MEDIAN_TILE_ROWS;
+    if (cols) *cols = bicos_hip::MEDIAN_TILE_COLS;
     return BICOS_OK;
 }
 

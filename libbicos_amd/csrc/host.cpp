@@ -527,4 +527,42 @@ int rectify_maps_host(bicos_engine* e, const RectifyMapsJob& j,
     return rc ? rc : rc2;
 }
 
+int median_host(bicos_engine* e, const MedianJob& j) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    if (int rc0 = check_median(j, false)) return rc0;
+    const size_t pixels = (size_t)j.rows * j.cols;
+    if (pixels == 0) {
+        if (j.counts) std::fill(j.counts, j.counts + 4, 0u);
+        return BICOS_OK;
+    }
+    hipStream_t st = e->own_stream;
+    const size_t esz = j.disp_type == BICOS_CV_32F ? 4 : 2;
+    // the same job on staged device buffers: two of them, because the launch reads
+    // neighbours (which is why the caller's out may be its map)
+    MedianJob d = j;
+    Lease stage(e, e->stage, e->stage_bytes, st);
+    void* map = nullptr;
+    auto carve = [&] {
+        map = stage.take(pixels * esz);
+        d.disp = map;
+        d.out = stage.take(pixels * esz);
+        d.counts = j.counts ? stage.take<uint32_t>(4) : nullptr;
+    };
+    carve();
+    int rc = stage.acquire();
+    if (rc) return rc;
+    carve();
+    rc = check_hip(hipMemcpyAsync(map, j.disp, pixels * esz, hipMemcpyHostToDevice, st),
+                   "disparity upload");
+    if (!rc) rc = median_device(d, st);
+    if (!rc)
+        rc = check_hip(hipMemcpyAsync(j.out, d.out, pixels * esz, hipMemcpyDeviceToHost, st),
+                       "filtered map download");
+    if (!rc && j.counts)
+        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 4 * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, st), "counts download");
+    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    return rc ? rc : rc2;
+}
+
 }  // namespace bicos_impl

@@ -378,6 +378,59 @@ class Engine:
         _lib.check(rc, "bicos_speckle_device")
         return out if lab is None else (out, lab)
 
+    # ----------------------------------------------------------- median filter
+    def median_filter(self, disp: torch.Tensor, ksize: int = 3, fill_min: int = 0, *,
+                      sentinel: bool = True, out: Optional[torch.Tensor] = None,
+                      counts: Optional[torch.Tensor] = None, stream=None):
+        """bicos_median_device: the ksize x ksize (3 or 5) median filter of an int16 or float32
+        map [rows, cols] that knows its invalid values; include/bicos_c.h, "median filter".
+        A valid pixel becomes the lower median of the valid values of its window, which is
+        clipped at the border; an invalid pixel (int16 -32768; float NaN, and -32768.0 with
+        `sentinel`) becomes it too where fill_min > 0 and the window holds at least fill_min
+        valid values, and keeps its bits otherwise. Exact: every output is the bits of one
+        input pixel.
+
+        Returns the filtered map: `out` if given, else a new tensor. `out` must not share
+        storage with `disp` (the filter reads neighbours). `counts`, an int32 [4] tensor on
+        the map's device, receives {unchanged, changed, filled, invalid} (uint32 bits).
+
+        The call NEVER synchronises: everything is enqueued on `stream` (default: torch's
+        current stream). Reading `counts` (`counts.tolist()`) is where the caller does."""
+        if not disp.is_cuda:
+            raise ValueError("device API needs CUDA/HIP tensors")
+        if disp.dim() != 2:
+            raise ValueError("disparity map must be [rows, cols]")
+        if disp.dtype not in (torch.int16, torch.float32):
+            raise ValueError("disparity map must be int16 or float32, got %s" % disp.dtype)
+        if not disp.is_contiguous():
+            raise ValueError("disparity map must be contiguous (dense rows)")
+        rows, cols = disp.shape
+        if rows * cols >= 2 ** 31:
+            raise ValueError("disparity map has more than 2^31 - 1 pixels")
+        k, fill = _lib.median_params(ksize, fill_min)
+        dev = disp.device
+        if out is None:
+            out = torch.empty_like(disp)
+        _check_out(out, "out", (rows, cols), (disp.dtype,), dev)
+        if counts is not None:
+            _check_out(counts, "counts", (4,), (torch.int32,), dev)
+        if rows * cols == 0:  # (an empty tensor has no pointer to hand over)
+            if counts is not None:
+                s = stream if stream is not None else torch.cuda.current_stream(dev)
+                with torch.cuda.stream(s):
+                    counts.zero_()
+            return out
+        if out.untyped_storage().data_ptr() == disp.untyped_storage().data_ptr():
+            raise ValueError("out must not share storage with the disparity map: the filter "
+                             "reads neighbours")
+        typ = _lib.CV_32F if disp.dtype == torch.float32 else _lib.CV_16S
+        rc = self._L.bicos_median_device(
+            self._h, disp.data_ptr(), typ, rows, cols, k, fill,
+            _lib.MEDIAN_F32_SENTINEL if sentinel else 0, out.data_ptr(),
+            counts.data_ptr() if counts is not None else None, _stream(dev, stream))
+        _lib.check(rc, "bicos_median_device")
+        return out
+
     # ----------------------------------------------------------- rectification
     def rectify_maps(self, K, D, R, P, size, stream=None):
         """bicos_rectify_maps_device: the float32 lookup maps (map_x, map_y), each [rows, cols]

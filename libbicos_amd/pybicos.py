@@ -346,6 +346,34 @@ def rectify(stack, map_x, map_y, border=0):
     return out, valid
 
 
+def median_filter(disparity, ksize=3, fill_min=0, sentinel=True):
+    """An extension (the reference has no such step; cv2.medianBlur is the CPU counterpart,
+    which knows nothing of invalid pixels): the ksize x ksize (3 or 5) median filter of a
+    disparity map of match() -- int16 or float32, [rows, cols] -- over the valid values of each
+    pixel's window, clipped at the border (bicos_median_host, include/bicos_c.h "median
+    filter": on the GPU, exact). Invalid pixels (int16 -32768, float NaN, and with `sentinel`
+    the float -32768.0 of a match without subpixel step) never enter a median; one whose
+    window holds at least fill_min > 0 valid values is filled with their median, every other
+    one keeps its bits. Returns (filtered, stats) with stats = dict(unchanged, changed, filled,
+    invalid); the input is left as it is."""
+    d = np.ascontiguousarray(disparity)
+    if d.ndim != 2:
+        raise ValueError("disparity map must be 2-D")
+    if d.dtype != np.int16 and d.dtype != np.float32:
+        raise ValueError(f"Unsupported disparity dtype: {d.dtype}")
+    k, fill = _lib.median_params(ksize, fill_min)
+    rows, cols = d.shape
+    out = np.empty_like(d)
+    counts = (ctypes.c_uint32 * 4)()
+    L = _lib.lib()
+    rc = L.bicos_median_host(None, d.ctypes.data, _get_cv_type(d.dtype), rows, cols, k, fill,
+                             _lib.MEDIAN_F32_SENTINEL if sentinel else 0, out.ctypes.data, counts)
+    if rc != 0:
+        raise RuntimeError("BICOS median filter failed: " +
+                           L.bicos_last_error().decode(errors="replace"))
+    return out, dict(unchanged=counts[0], changed=counts[1], filled=counts[2], invalid=counts[3])
+
+
 def invalid_disparity(dtype):
     """reference pybicos/__init__.py:246-252."""
     L = _lib.lib()
