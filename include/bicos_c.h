@@ -130,7 +130,15 @@ int bicos_output_type(const BicosConfig* cfg, int has_nxcorr);
 /*
  * Full match on device-resident planar stacks.
  *   stack0/stack1 : n planes each; element (t, y, x) at
- *                   base[t*plane_pitch + y*row_pitch + x], u8 (depth 1) or u16 (depth 2)
+ *                   base[t*plane_pitch + y*row_pitch + x], u8 (depth 1) or u16 (depth 2).
+ *                   Pitches are in ELEMENTS and may be anything >= a row / the rows of a plane;
+ *                   the base needs only the element's own alignment (any byte for u8, 2 bytes
+ *                   for u16): a region of interest cut out of a pitched frame is passed as it
+ *                   lies. Bytes between rows, between planes and around the view are never
+ *                   taken for pixels and never written. Alignment only selects kernels
+ *                   (bicos_match_plan, bicos_agree_kernel), never results: every stage is
+ *                   tested at every base residue and pitch residue mod 4
+ *                   (tests/test_stack_views_gpu.py).
  *   has_nxcorr    : 0 disables the NXC stage (Config::nxcorr_threshold = nullopt, only
  *                   reachable from C++ in the reference); disparity is then int16
  *   disparity     : device, rows*cols dense, int16 or float32 per bicos_output_type
@@ -233,7 +241,13 @@ int bicos_match_bands_device(const int* devices, int ndev, const void* const* st
                              void* corrmap);
 
 /* Stage entry points (tests, benchmarks, custom pipelines). Same conventions.
- * desc buffers: rows x desc_pitch uint32 with desc_pitch = bicos_desc_pitch(cols, words). */
+ * desc buffers: rows x desc_pitch uint32 with desc_pitch = bicos_desc_pitch(cols, words), dense.
+ * Descriptors that are READ (the search entries, bicos_search_agree_device) need 4-byte
+ * alignment only (they are uint32_t*); 16 bytes, which the engine's own buffers have, only
+ * lets a few copies use wider loads. Results are the same at every word offset, and desc0 and
+ * desc1 may differ in it (tests/test_desc_views_gpu.py). bicos_transform_device WRITES whole
+ * 16-byte vectors: its desc must be 16-byte aligned. Output maps are dense and need their
+ * element's alignment only (tested 2, 4 and 8 bytes past a 16-byte boundary). */
 size_t bicos_desc_pitch(int cols, int words);
 int bicos_transform_device(const void* stack, int n, int rows, int cols, size_t row_pitch,
                            size_t plane_pitch, int depth, int mode, int words, uint32_t* desc,
@@ -301,6 +315,14 @@ int bicos_match_plan(bicos_engine* e, const void* stack0, const void* stack1, in
  * (0 where that launch is not planned); else n is ignored. For tests; no HIP call, e may be
  * NULL. */
 int bicos_search_packed(bicos_engine* e, int rows, int cols, int words, int bits, int n, int fused);
+/* Which kernel the agree stage (bicos_agree_device, bicos_agree_stage_device without a step, the
+ * agree launch of a match) runs for these stacks: 2 = the left tile staged through LDS with
+ * dword loads (stack0's base and both pitches, in bytes, multiples of 4; stack1's base is
+ * free), 1 = every sample by byte / short loads into registers (any other view), 0 = the
+ * generic kernel (n > 65, stage entries only). Results are identical. The pointers are only
+ * inspected for their alignment. For tests; no HIP call. */
+int bicos_agree_kernel(const void* stack0, const void* stack1, int n, size_t row_pitch,
+                       size_t plane_pitch, int depth);
 
 /* bicos_match_device from its search on: desc0 / desc1 are the two stacks' descriptors as
  * bicos_transform_device writes them (rows x bicos_desc_pitch(cols, words) uint32, words =

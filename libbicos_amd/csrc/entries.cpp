@@ -251,6 +251,18 @@ int bicos_search_packed(bicos_engine* e, int rows, int cols, int words, int bits
     return search_runs_packed(e, rows, cols, words, bits, n, fused != 0) ? 1 : 0;
 }
 
+int bicos_agree_kernel(const void* stack0, const void* stack1, int n, size_t row_pitch,
+                       size_t plane_pitch, int depth) {
+    if (int rc0 = check_stack_shape(n, depth, 0, 0)) return rc0;
+    bicos_hip::AgreeArgs aa{};
+    aa.stack0 = stack0;
+    aa.stack1 = stack1;
+    aa.n = n;
+    aa.row_pitch = row_pitch;
+    aa.plane_pitch = plane_pitch;
+    return bicos_hip::agree_kernel_kind(aa, depth);
+}
+
 int bicos_search_agree_device(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1,
                               const void* stack0, const void* stack1, int n, int rows, int cols,
                               size_t row_pitch, size_t plane_pitch, int depth,

@@ -759,13 +759,20 @@ hipError_t launch_search_w(const SearchArgs& a, bool nodupes, const SearchGeomet
 }
 
 
+// Whether the agree reads the left tile through LDS (agree_lds_kernel): its dword loads need
+// stack0's base and both pitches 4-byte aligned. stack1's base is free -- its samples are
+// gathered by byte / short loads in either kernel. launch_agree_m's one dispatch condition,
+// and what agree_kernel_kind reports (tests/test_stack_views_gpu.py pins it at every base).
+bool agree_dwords_aligned(const AgreeArgs& a, size_t sz) {
+    return ((uintptr_t)a.stack0 % 4 == 0) && (a.row_pitch * sz) % 4 == 0 &&
+           (a.plane_pitch * sz) % 4 == 0;
+}
+
 template <typename TIn, typename TPrec, int MAXN>
 hipError_t launch_agree_m(const AgreeArgs& a, hipStream_t st) {
     dim3 grid((a.cols + 255) / 256, a.rows);
     // left tile through LDS when the dword loads are aligned
-    const size_t sz = sizeof(TIn);
-    const bool aligned = ((uintptr_t)a.stack0 % 4 == 0) && (a.row_pitch * sz) % 4 == 0 &&
-                         (a.plane_pitch * sz) % 4 == 0;
+    const bool aligned = agree_dwords_aligned(a, sizeof(TIn));
     if (a.fwd) {  // Consistency's check in the agree: the LDS kernel only (engine.cpp plan)
         if (!aligned || !a.rev) return hipErrorInvalidValue;
         hipLaunchKernelGGL((agree_lds_kernel<TIn, TPrec, MAXN, false, true>), grid, dim3(256), 0, st, a);
@@ -877,6 +884,11 @@ hipError_t launch_consistency(const ConsistencyArgs& a, hipStream_t st) {
     dim3 grid((a.cols + 255) / 256, a.rows);
     hipLaunchKernelGGL(consistency_kernel, grid, dim3(256), 0, st, a);
     return hipGetLastError();
+}
+
+int agree_kernel_kind(const AgreeArgs& a, int depth) {
+    if (a.n > 65) return 0;  // (launch_agree_t: the generic kernel)
+    return agree_dwords_aligned(a, depth == 1 ? 1 : 2) ? 2 : 1;
 }
 
 hipError_t launch_agree(const AgreeArgs& a, int depth, bool dbl, hipStream_t st) {

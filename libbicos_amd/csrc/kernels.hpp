@@ -200,6 +200,9 @@ hipError_t launch_search_range(SearchArgs a, int dmin, int dmax, int words, bool
                                int bits, int cus, hipStream_t st, int tiles = 0,
                                int waves_wg = 0);
 hipError_t launch_agree(const AgreeArgs& a, int depth, bool dbl, hipStream_t st);
+// The kernel launch_agree picks for a's stacks (stack0's base, n and the pitches; no HIP call):
+// 2 = agree_lds_kernel, 1 = agree_reg_kernel, 0 = the generic agree_kernel (n > 65)
+int agree_kernel_kind(const AgreeArgs& a, int depth);
 hipError_t launch_subpixel(const AgreeArgs& a, int depth, bool dbl, hipStream_t st);
 // n > 40 (subpixel_wide.hip); launch_subpixel dispatches to it
 hipError_t launch_subpixel_wide(const AgreeArgs& a, int depth, bool dbl, hipStream_t st);

@@ -198,6 +198,16 @@ class Engine:
         fused search + agree launch of n-image stacks) runs the pruned packed-key kernel."""
         return bool(self._L.bicos_search_packed(self._h, rows, cols, words, bits, n, int(fused)))
 
+    def agree_kernel(self, stack0: torch.Tensor, stack1: torch.Tensor) -> int:
+        """bicos_agree_kernel: which kernel agree() (without a step) runs for these views --
+        2 the LDS-staged one, 1 the register one, 0 the generic one (n > 65)."""
+        n, rows, cols, rp, pp = _check_stack(stack0)
+        rc = self._L.bicos_agree_kernel(stack0.data_ptr(), stack1.data_ptr(), n, rp, pp,
+                                        _depth(stack0))
+        if rc < 0:
+            _lib.check(rc, "bicos_agree_kernel")
+        return rc
+
     def search_agree(self, desc0: torch.Tensor, desc1: torch.Tensor, stack0: torch.Tensor,
                      stack1: torch.Tensor, cfg: Optional[MatchConfig] = None,
                      out: Optional[torch.Tensor] = None, corrmap: Optional[torch.Tensor] = None,
@@ -550,16 +560,23 @@ class Engine:
 
     def agree(self, raw: torch.Tensor, stack0: torch.Tensor, stack1: torch.Tensor,
               threshold: float, minvar_scaled: Optional[float] = None,
-              step: Optional[float] = None, stream=None, precision: int = 0
+              step: Optional[float] = None, stream=None, precision: int = 0,
+              out: Optional[torch.Tensor] = None, corrmap: Optional[torch.Tensor] = None
               ) -> Tuple[torch.Tensor, torch.Tensor]:
         """NXC agree (step None) or subpixel refine of an int16 search result -> (float32
-        disparity, corrmap float32 / float64 with precision=1)."""
+        disparity, corrmap float32 / float64 with precision=1), into `out` / `corrmap` where
+        given (dense)."""
         if step is not None and not step > 0:
             raise ValueError("subpixel step must be positive")
         n, rows, cols, rp, pp = _check_stack(stack0)
-        out = torch.empty((rows, cols), dtype=torch.float32, device=stack0.device)
-        corr = torch.empty((rows, cols), dtype=torch.float64 if precision else torch.float32,
-                           device=stack0.device)
+        corr_dtype = torch.float64 if precision else torch.float32
+        if out is None:
+            out = torch.empty((rows, cols), dtype=torch.float32, device=stack0.device)
+        _check_out(out, "out", (rows, cols), (torch.float32,), stack0.device)
+        corr = corrmap
+        if corr is None:
+            corr = torch.empty((rows, cols), dtype=corr_dtype, device=stack0.device)
+        _check_out(corr, "corrmap", (rows, cols), (corr_dtype,), stack0.device)
         hm = int(minvar_scaled is not None)
         mv = float(minvar_scaled or 0.0)
         st = _stream(stack0.device, stream)

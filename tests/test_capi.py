@@ -54,6 +54,27 @@ def test_invalid_disparity_values(blib):
     assert blib.BICOS_InvalidDisparityInt16() == -32768
 
 
+def test_agree_kernel_query(blib):
+    """bicos_agree_kernel (no HIP call): the LDS-staged agree (2) needs stack0's base and both
+    pitches, in bytes, multiples of 4 -- stack1's base is free; the register kernel (1) takes
+    every other view; n > 65 the generic one (0)."""
+    q = blib.bicos_agree_kernel
+    A = 1 << 20                                   # (only the addresses' alignment is looked at)
+    for depth in (1, 2):
+        for b0 in range(0, 8, depth):
+            for b1 in range(0, 8, depth):
+                for rp in range(300, 300 + 4):
+                    for pp in (rp * 6, rp * 6 + 1, rp * 6 + 2, rp * 6 + 7):
+                        lds = b0 % 4 == 0 and (rp * depth) % 4 == 0 and (pp * depth) % 4 == 0
+                        assert q(A + b0, A + 4096 + b1, 33, rp, pp, depth) == (2 if lds else 1), \
+                            (depth, b0, b1, rp, pp)
+    assert q(A, A, 65, 304, 304 * 6, 1) == 2 and q(A, A, 66, 304, 304 * 6, 1) == 0
+    assert q(A + 1, A, 70, 304, 304 * 6, 1) == 0
+    from libbicos_amd import _lib
+    assert q(A, A, 1, 304, 304 * 6, 1) == _lib.BICOS_E_ARG      # n < 2
+    assert q(A, A, 8, 304, 304 * 6, 3) == _lib.BICOS_E_ARG      # depth
+
+
 def test_descriptor_words(blib):
     assert blib.bicos_descriptor_words(8, 0) == 1
     assert blib.bicos_descriptor_words(17, 0) == 2
