@@ -1,6 +1,7 @@
 // host.cpp -- the banded host-buffer pipeline: bicos_impl::match_host and its thread pool
 // (the reference's cv::Mat path, src/impl/cpu.cpp:100-159).
 #include "engine.hpp"
+#include "host_plan.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -113,7 +114,8 @@ struct HostMatch {
     hipStream_t cs, ks;  // compute, copy
     const bool dl_bands = download_by_band();
     const int up_streams = upload_streams();
-    // the band plan (plan_bands)
+    // the band plan (plan_bands; the arithmetic is host_plan.hpp's)
+    host_plan::BandPlan bands;
     size_t row_bytes = 0, band_bytes = 0, dsz = 0, csz = 0, disp_bytes = 0, corr_bytes = 0;
     int band_rows = 0, B = 0, K = 0;
     // the stage: band-major stacks | disparity | corrmap (carve)
@@ -131,13 +133,11 @@ struct HostMatch {
         std::fprintf(stderr, "[bicos host] %8.1f us  %s %d\n", us, what, b);
     }
 
-    // Row bands (every stage is row-local): upload of band b+1 overlaps the
-    // match of band b; ~8 bands keep the pipeline tail short without starving the search.
     void plan_bands() {
-        const int want = rows >= 1024 ? 8 : rows >= 256 ? 4 : rows >= 64 ? 2 : 1;
-        band_rows = (rows + want - 1) / want;
-        B = (rows + band_rows - 1) / band_rows;
-        K = B > 1 ? 3 : 1;  // pinned slots in flight
+        bands = host_plan::plan_bands(rows);
+        band_rows = bands.band_rows;
+        B = bands.B;
+        K = bands.K;  // pinned slots in flight
         row_bytes = (size_t)cols * depth;
         band_bytes = 2 * (size_t)n * band_rows * row_bytes;
         dsz = has_nxcorr ? 4 : 2;
@@ -145,7 +145,14 @@ struct HostMatch {
         disp_bytes = (size_t)rows * cols * dsz;
         corr_bytes = corr ? (size_t)rows * cols * csz : 0;
     }
-    int band_height(int b) const { return std::min(band_rows, rows - b * band_rows); }
+    int band_height(int b) const { return bands.height(b); }
+    // band b's bytes in its slot and on the device, and whether its upload has a second part
+    // (on copy_stream2, with events2[b] recorded behind it)
+    size_t band_upload(int b) const { return 2 * (size_t)n * band_height(b) * row_bytes; }
+    bool upload_is_split(int b) const {
+        const size_t up = band_upload(b);
+        return host_plan::upload_first(up, up_streams) < up;
+    }
 
     void carve(Lease& stage) {
         dev = stage.take((size_t)B * band_bytes);
@@ -196,7 +203,7 @@ struct HostMatch {
         int rc = BICOS_OK;
         if (b >= K) {
             rc = check_hip(hipEventSynchronize(e->events[b - K]), "hipEventSynchronize");
-            if (!rc && up_streams == 2)
+            if (!rc && upload_is_split(b - K))
                 rc = check_hip(hipEventSynchronize(e->events2[b - K]), "hipEventSynchronize");
             if (rc) return rc;
         }
@@ -225,12 +232,16 @@ struct HostMatch {
             (void)hipEventCreate(&t1);
             (void)hipEventRecord(t0, ks);
         }
-        const size_t up = 2 * (size_t)n * plane;
-        const size_t first = up_streams == 2 ? (up / 2 + 4095) / 4096 * 4096 : up;
-        rc = check_hip(hipMemcpyAsync(band, slot, first, hipMemcpyHostToDevice, ks), "stack upload");
-        if (!rc && first < up) {
-            rc = check_hip(hipMemcpyAsync(band + first, slot + first, up - first,
-                                          hipMemcpyHostToDevice, e->copy_stream2), "stack upload");
+        // one copy, or two on two streams: never past the band's own bytes (a band of under
+        // 4096 bytes once had a first part of 4096, host_plan.hpp upload_first)
+        host_plan::Span part[2];
+        const int copies = host_plan::upload_parts(band_upload(b), up_streams, part);
+        rc = check_hip(hipMemcpyAsync(band + part[0].offset, slot + part[0].offset, part[0].length,
+                                      hipMemcpyHostToDevice, ks), "stack upload");
+        if (!rc && copies == 2) {
+            rc = check_hip(hipMemcpyAsync(band + part[1].offset, slot + part[1].offset,
+                                          part[1].length, hipMemcpyHostToDevice, e->copy_stream2),
+                           "stack upload");
             if (!rc) rc = check_hip(hipEventRecord(e->events2[b], e->copy_stream2), "hipEventRecord");
             if (!rc) rc = check_hip(hipStreamWaitEvent(cs, e->events2[b], 0), "hipStreamWaitEvent");
         }
@@ -252,14 +263,15 @@ struct HostMatch {
     int download_band(int b) {
         const int r0 = b * band_rows, br = band_height(b);
         hipStream_t ds = e->dl_stream;
-        const size_t od = (size_t)r0 * cols * dsz, oc = (size_t)r0 * cols * csz;
+        const host_plan::Span d = host_plan::map_rows(r0, br, cols, dsz);
+        const host_plan::Span c = host_plan::map_rows(r0, br, cols, csz);
         int rc = check_hip(hipEventRecord(e->dl_events[2 * b], cs), "hipEventRecord");
         if (!rc) rc = check_hip(hipStreamWaitEvent(ds, e->dl_events[2 * b], 0), "hipStreamWaitEvent");
         if (!rc)
-            rc = check_hip(hipMemcpyAsync(hout_d + od, dev_disp + od, (size_t)br * cols * dsz,
+            rc = check_hip(hipMemcpyAsync(hout_d + d.offset, dev_disp + d.offset, d.length,
                                           hipMemcpyDeviceToHost, ds), "download");
         if (!rc && corr)
-            rc = check_hip(hipMemcpyAsync(hout_c + oc, dev_corr + oc, (size_t)br * cols * csz,
+            rc = check_hip(hipMemcpyAsync(hout_c + c.offset, dev_corr + c.offset, c.length,
                                           hipMemcpyDeviceToHost, ds), "download");
         if (!rc) rc = check_hip(hipEventRecord(e->dl_events[2 * b + 1], ds), "hipEventRecord");
         return rc;
@@ -271,18 +283,15 @@ struct HostMatch {
         int rc = check_hip(hipEventSynchronize(e->dl_events[2 * b + 1]), "hipEventSynchronize");
         if (rc) return rc;
         const int r0 = b * band_rows, br = band_height(b);
-        const int parts = 8;
+        const int parts = host_plan::DELIVER_PARTS;
         const std::function<void(int)> out = [&](int i) {
             const bool c = i >= parts;
             if (c && !corr) return;
-            const size_t esz = c ? csz : dsz;
-            const size_t bytes = (size_t)br * cols * esz;
-            const size_t chunk = (bytes / parts + 63) / 64 * 64;
-            const size_t o = (size_t)(i % parts) * chunk;
-            if (o >= bytes) return;
-            const size_t base = (size_t)r0 * cols * esz + o;
-            std::memcpy((char*)(c ? corr : disp) + base, (c ? hout_c : hout_d) + base,
-                        std::min(chunk, bytes - o));
+            const host_plan::Span band = host_plan::map_rows(r0, br, cols, c ? csz : dsz);
+            const host_plan::Span part = host_plan::deliver_part(band.length, parts, i % parts);
+            if (!part.length) return;
+            const size_t base = band.offset + part.offset;
+            std::memcpy((char*)(c ? corr : disp) + base, (c ? hout_c : hout_d) + base, part.length);
         };
         e->pool->run(2 * parts, out);
         return BICOS_OK;

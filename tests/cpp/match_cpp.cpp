@@ -3,6 +3,7 @@
 // every input branch of BICOS::match, and writes the maps for the Python test to compare
 // with the CPU oracle:
 //   host        host Images with padded rows (banded pinned upload path)
+//   host_mixed  host Images with dense and padded rows mixed in one stack (one step per image)
 //   dev_planar  device Images that are views into ONE planar buffer per stack (zero-copy)
 //   dev_staged  device Images in separate pitched allocations (2-D staging copies)
 //   mats        an OpenCV-shaped matrix type through bicos/opencv.hpp's match_mats
@@ -98,7 +99,8 @@ int main(int argc, char** argv) {
 
     // optional MATCH_CPP_ORDER=b1,b2,... runs only those branches, in that order (debugging)
     const char* order_env = std::getenv("MATCH_CPP_ORDER");
-    const std::string order = order_env ? order_env : "host,dev_planar,dev_staged,mats,seam";
+    const std::string order =
+        order_env ? order_env : "host,host_mixed,dev_planar,dev_staged,mats,seam";
     hipStream_t st;
     hip_ok(hipStreamCreate(&st), "hipStreamCreate");
     auto run_host = [&]() {
@@ -115,6 +117,27 @@ int main(int argc, char** argv) {
         Image d, c;
         match(s0, s1, d, cfg, &c);
         report("host", d, c);
+    };
+    // 1b. host images that alternate between dense and padded rows within one stack (the
+    //     left stack dense at even t and padded by 13 elements at odd t, the right one padded
+    //     by 7 at even t and dense at odd t): BICOS::match passes one step per image, so one
+    //     band's gather takes both arms of its dense-row test
+    auto run_host_mixed = [&]() {
+        std::vector<std::vector<unsigned char>> keep;
+        std::vector<Image> s0, s1;
+        for (int s = 0; s < 2; ++s)
+            for (int t = 0; t < n; ++t) {
+                const bool dense = (t + s) % 2 == 0;
+                const size_t step = dense ? rowb : rowb + (s ? 7 : 13) * depth;
+                keep.emplace_back(step * rows, (unsigned char)0xEE);
+                for (int r = 0; r < rows; ++r)
+                    std::memcpy(keep.back().data() + r * step, src(s, t) + r * rowb, rowb);
+                (s ? s1 : s0).emplace_back(rows, cols, type, keep.back().data(), dense ? 0 : step,
+                                           Memory::Host);
+            }
+        Image d, c;
+        match(s0, s1, d, cfg, &c);
+        report("host_mixed", d, c);
     };
     // 2. device, one planar buffer per stack (pitch cols + 64 elements, planes 3 rows apart
     //    more than needed): the zero-copy branch
@@ -192,6 +215,7 @@ int main(int argc, char** argv) {
         if (e == std::string::npos) e = order.size();
         const std::string b = order.substr(pos, e - pos);
         if (b == "host") run_host();
+        else if (b == "host_mixed") run_host_mixed();
         else if (b == "dev_planar") run_planar();
         else if (b == "dev_staged") run_staged();
         else if (b == "mats") run_mats();

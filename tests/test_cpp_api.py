@@ -1,6 +1,7 @@
 """The C++ API (include/bicos/match.hpp, hip.hpp, opencv.hpp) as a reference C++ caller
 uses it (reference include/match.hpp:31-41, src/lib.cpp:31-49): tests/cpp/match_cpp runs
-BICOS::match through every input branch -- host images with padded rows, device images
+BICOS::match through every input branch -- host images with padded rows, host images with
+dense and padded rows mixed in one stack (one step per image), device images
 that form one planar buffer (zero-copy), device images in separate pitched allocations
 (2-D staging), an OpenCV-shaped matrix type through bicos/opencv.hpp, and the
 impl::hip::match backend seam -- and each branch's maps must equal the CPU oracle's bit
@@ -16,7 +17,7 @@ from libbicos_amd.synthetic import stereo_stack
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "tests", "cpp", "match_cpp")
-BRANCHES = ("host", "dev_planar", "dev_staged", "mats", "seam")
+BRANCHES = ("host", "host_mixed", "dev_planar", "dev_staged", "mats", "seam")
 
 
 def test_cpp_driver_is_built():
@@ -67,7 +68,7 @@ def test_cpp_match_branches_bit_exact(case, oracle, tmp_path):
     rd, rc = oracle.match(L, R, oracle.OracleConfig(**cfg))
     for b in BRANCHES:
         assert b in lines, r.stdout
-        mem = "host" if b in ("host", "mats", "seam") else "device"
+        mem = "host" if b in ("host", "host_mixed", "mats", "seam") else "device"
         assert lines[b].endswith("mem=" + mem), lines[b]
         d = np.fromfile(tmp_path / ("out.%s.disp" % b), dtype=rd.dtype).reshape(H, W)
         assert np.array_equal(d.view(np.uint8), rd.view(np.uint8)), b
