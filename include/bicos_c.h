@@ -323,6 +323,15 @@ int bicos_search_packed(bicos_engine* e, int rows, int cols, int words, int bits
  * inspected for their alignment. For tests; no HIP call. */
 int bicos_agree_kernel(const void* stack0, const void* stack1, int n, size_t row_pitch,
                        size_t plane_pitch, int depth);
+/* Which kernel the transform (bicos_transform_device with stack1 NULL, the transform launch of
+ * a match over both stacks) runs for these stacks: 1 = two pixels per 32-bit register from
+ * dword loads (u8 stacks, LIMITED, n one of 9 12 17 24 33 40 48 65 with words =
+ * bicos_descriptor_words(n, 0), every base and both pitches multiples of 4 bytes, the stacks
+ * within 256 MiB together, and the environment's BICOS_TRANSFORM_PK, read once, not 0),
+ * 0 = one pixel per lane from byte / short loads (anything else). Results are identical. The
+ * pointers are only inspected for their alignment. For tests; no HIP call. */
+int bicos_transform_kernel(const void* stack0, const void* stack1, int n, int rows, int cols,
+                           size_t row_pitch, size_t plane_pitch, int depth, int mode, int words);
 
 /* bicos_match_device from its search on: desc0 / desc1 are the two stacks' descriptors as
  * bicos_transform_device writes them (rows x bicos_desc_pitch(cols, words) uint32, words =

@@ -60,6 +60,7 @@ EXPORTS = (
     "bicos_desc_pitch", "bicos_transform_device", "bicos_search_device",
     "bicos_agree_device", "bicos_subpixel_device", "bicos_agree_stage_device", "bicos_build_info",
     "bicos_match_plan", "bicos_search_agree_device", "bicos_search_packed", "bicos_agree_kernel",
+    "bicos_transform_kernel",
     "bicos_match_device_range", "bicos_match_host_range", "bicos_search_device_range",
     "bicos_reproject_device", "bicos_reproject_host", "bicos_reproject_segment",
     "bicos_speckle_device", "bicos_speckle_host", "bicos_speckle_tile",
@@ -175,6 +176,8 @@ def lib() -> ctypes.CDLL:
     L.bicos_search_packed.restype = I
     L.bicos_agree_kernel.argtypes = [P, P, I, Z, Z, I]
     L.bicos_agree_kernel.restype = I
+    L.bicos_transform_kernel.argtypes = [P, P, I, I, I, Z, Z, I, I, I]
+    L.bicos_transform_kernel.restype = I
     L.bicos_search_agree_device.argtypes = [P, P, P, P, P, I, I, I, Z, Z, I,
                                             ctypes.POINTER(BicosConfig), I, P, P, P]
     L.bicos_search_agree_device.restype = I

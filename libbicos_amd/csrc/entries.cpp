@@ -263,6 +263,24 @@ int bicos_agree_kernel(const void* stack0, const void* stack1, int n, size_t row
     return bicos_hip::agree_kernel_kind(aa, depth);
 }
 
+int bicos_transform_kernel(const void* stack0, const void* stack1, int n, int rows, int cols,
+                           size_t row_pitch, size_t plane_pitch, int depth, int mode, int words) {
+    if (int rc0 = check_stack_shape(n, depth, 0, 0)) return rc0;
+    if (int rc0 = check_words(words)) return rc0;
+    uint32_t span = 0;
+    if (int rc0 = stack_span(n, rows, cols, row_pitch, plane_pitch, depth, &span)) return rc0;
+    bicos_hip::TransformArgs ta{};
+    ta.stack0 = stack0;
+    ta.stack1 = stack1;
+    ta.n = n;
+    ta.rows = rows;
+    ta.cols = cols;
+    ta.row_pitch = row_pitch;
+    ta.plane_pitch = plane_pitch;
+    ta.stack_bytes = span;
+    return bicos_hip::transform_kernel_kind(ta, depth, mode ? 1 : 0, words);
+}
+
 int bicos_search_agree_device(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1,
                               const void* stack0, const void* stack1, int n, int rows, int cols,
                               size_t row_pitch, size_t plane_pitch, int depth,

@@ -20,6 +20,7 @@
 #include "nxc.hpp"
 #include "stack.hpp"
 #include "transform.hpp"
+#include "transform_pk.hpp"
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -197,6 +198,105 @@ __global__ __launch_bounds__(256) void transform_limited_kernel(TransformArgs a)
         *(uint2*)out = make_uint2(w[0], w[1 % WORDS]);
     } else {
         out[0] = w[0];
+    }
+}
+
+// LIMITED transform of u8 stacks, two pixels per 32-bit register (transform_pk.hpp). A lane
+// takes the 4 adjacent columns of one dword load per plane -- pixels (0, 2) and (1, 3) as two
+// registers of 16-bit fields -- and writes their descriptors, 16 WORDS contiguous bytes,
+// through LDS where those are more than one store. A workgroup covers 1024 columns of one
+// row of one stack. Needs the stack's base and both pitches 4-byte aligned
+// (transform_pk_eligible); N is the stack size, WORDS its narrowest descriptor. Columns past
+// a.cols in the row's last dword are computed and not stored; the buffer resource is rounded
+// up to whole dwords so that dword is in range (the aligned dword that holds the stack's last
+// byte lies within the last byte's page), and loads past it return 0.
+template <int WORDS, int N>
+__global__ __launch_bounds__(256) void transform_limited_pk_kernel(TransformArgs a) {
+    constexpr int PX = 4;  // columns per lane
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t col = (blockIdx.x * 256 + threadIdx.x) * PX;
+    const uint32_t wave_col = col - lane * PX;  // the wave's first column
+    const uint32_t cols = (uint32_t)a.cols;
+    const int row = blockIdx.y;
+    const int which = blockIdx.z;
+    // whole waves leave: the lanes past the row's end still carry words for the stores below
+    // (their loads are bounded by the buffer resource, their results are not stored)
+    if (wave_col >= cols) return;
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<void*>(which ? a.stack1 : a.stack0), (short)0, (int)((a.stack_bytes + 3u) & ~3u),
+        0x00020000);
+    const uint32_t pp = (uint32_t)a.plane_pitch;
+    const uint32_t rowoff = (uint32_t)row * (uint32_t)a.row_pitch;
+
+    // The N dwords stay as loaded: a pair's samples are split out of them for its sum, and
+    // again, one per step, for its bits (the empty asm keeps the compiler from holding on to
+    // the first split: 2 N more registers). N + 16 accumulators + a step's window: 55 VGPRs
+    // at N = 33.
+    uint32_t d[N];
+#pragma unroll
+    for (int t = 0; t < N; ++t)
+        d[t] = __builtin_amdgcn_raw_buffer_load_b32(r, col, rowoff + (uint32_t)t * pp, 0);
+    const auto even = [&](int t) { return tpk::even_pixels(d[t]); };
+    const auto odd = [&](int t) { return tpk::odd_pixels(d[t]); };
+    const uint32_t thr_e = tpk::pair_threshold(tpk::pair_sum<N>(even), N, a.magic);
+    const uint32_t thr_o = tpk::pair_threshold(tpk::pair_sum<N>(odd), N, a.magic);
+#pragma unroll
+    for (int t = 0; t < N; ++t) asm volatile("" : "+v"(d[t]));
+    uint32_t acc_e[tpk::accumulators(N)], acc_o[tpk::accumulators(N)];
+    tpk::pair_bits<N>(even, thr_e, acc_e);
+    tpk::pair_bits<N>(odd, thr_o, acc_o);
+    uint32_t w0[WORDS], w1[WORDS], w2[WORDS], w3[WORDS];
+    tpk::pair_words<WORDS>(acc_e, w0, w2);
+    tpk::pair_words<WORDS>(acc_o, w1, w3);
+    uint32_t w[PX * WORDS];  // pixel col + i at [i * WORDS, i * WORDS + WORDS)
+#pragma unroll
+    for (int k = 0; k < WORDS; ++k) {
+        w[k] = w0[k];
+        w[WORDS + k] = w1[k];
+        w[2 * WORDS + k] = w2[k];
+        w[3 * WORDS + k] = w3[k];
+    }
+
+    uint32_t* __restrict__ orow = (which ? a.desc1 : a.desc0) + (size_t)row * a.desc_pitch;
+    constexpr int LW = PX * WORDS;  // words per lane
+    if constexpr (LW == 4) {
+        // a lane's words are one store, and consecutive lanes write consecutive bytes
+        uint32_t* __restrict__ out = orow + col;
+        if (col + PX <= cols) {
+            *(uint4*)out = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < PX - 1; ++i)
+                if (col + i < cols) out[i] = w[i];
+        }
+    } else {
+        // A lane's 4 LW bytes are several 16-byte stores; issued as they stand, each store
+        // instruction scatters 64 pieces of 16 bytes over 64 LW words (measured: 78 us for the
+        // cfg2 frame's launch against 57). The wave passes its words through its own part of
+        // LDS instead (in order within a wave: no barrier), and every store instruction writes
+        // 1 KiB of consecutive bytes. The stores are non-temporal: the descriptors are next
+        // read by another kernel, after 100 MB of them have gone by (cfg2: 53.9 us against 56.6).
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+        __shared__ __attribute__((aligned(16))) uint32_t stage[256 * LW];
+        uint32_t* sw = stage + (threadIdx.x - lane) * LW;
+#pragma unroll
+        for (int k = 0; k < LW; k += 4)
+            *(uint4*)(sw + lane * LW + k) = make_uint4(w[k], w[k + 1], w[k + 2], w[k + 3]);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint32_t wave_cols = cols - wave_col < 64u * PX ? cols - wave_col : 64u * PX;
+        const uint32_t valid = wave_cols * WORDS;  // words of this wave's columns inside the row
+        uint32_t* __restrict__ out = orow + (size_t)wave_col * WORDS;
+#pragma unroll
+        for (int k = 0; k < LW / 4; ++k) {
+            const uint32_t q = (k * 64 + lane) * 4;
+            if (q + 4 <= valid)
+                __builtin_nontemporal_store(*(const u32x4*)(sw + q), (u32x4*)(out + q));
+            else if (WORDS == 2 && q + 2 <= valid)
+                __builtin_nontemporal_store(*(const u32x2*)(sw + q), (u32x2*)(out + q));
+        }
     }
 }
 
@@ -679,8 +779,45 @@ __global__ __launch_bounds__(256) void agree_lds_kernel(AgreeArgs a) {
 
 // ------------------------------------------------------------------- dispatch
 
+// BICOS_TRANSFORM_PK=0 (read once): never the packed transform, for A/B runs
+bool transform_pk_enabled() {
+    static const bool on = [] {
+        const char* v = std::getenv("BICOS_TRANSFORM_PK");
+        return !(v && v[0] == '0' && v[1] == 0);
+    }();
+    return on;
+}
+
+// The packed transform's gain is its non-temporal descriptor stores, which leave the stacks in
+// the 256 MiB last-level cache for the agree that reads them next: cfg2 (2 x 33 planes of
+// 2048 x 1536, 198 MiB) 53.6-53.8 us against 56.8-57.2, and the search + agree launch after it
+// 246.8 against 249.7. Stacks that do not fit gain nothing there, and the packed kernel alone
+// is no faster than the one-pixel kernel (cfg2 without the hint 56.6-58.6 us; 3840 x 2160
+// 152.8 us against 149.8, 3208 x 2200 144.7 against 140.2): those keep the one-pixel kernel.
+// (profiles/transform_pk_r16.jsonl)
+constexpr uint64_t PK_CACHED_STACK_BYTES = 256ull << 20;
+
+// Whether the LIMITED transform runs transform_limited_pk_kernel: u8 stacks of a size it is
+// built for at that size's narrowest descriptor, whose dword loads are aligned -- the base of
+// each stack, the row pitch and the plane pitch all multiples of 4 bytes -- and which fit the
+// last-level cache together. launch_tl's one dispatch condition, and what
+// transform_kernel_kind reports.
+bool transform_pk_eligible(const TransformArgs& a, int depth, int mode, int words) {
+    return transform_pk_enabled() && depth == 1 && mode == 0 && tpk::built(a.n) &&
+           words == tpk::limited_words(a.n) && (uintptr_t)a.stack0 % 4 == 0 &&
+           (uintptr_t)a.stack1 % 4 == 0 && a.row_pitch % 4 == 0 && a.plane_pitch % 4 == 0 &&
+           (uint64_t)a.stack_bytes * (a.stack1 ? 2 : 1) <= PK_CACHED_STACK_BYTES;
+}
+
 template <typename TIn, int WORDS, int MAXN>
 hipError_t launch_tl(const TransformArgs& a, dim3 grid, hipStream_t st) {
+    if constexpr (sizeof(TIn) == 1 && tpk::built(MAXN) && WORDS == tpk::limited_words(MAXN)) {
+        if (transform_pk_eligible(a, 1, 0, WORDS)) {  // (then a.n == MAXN: the exact bucket)
+            const dim3 grid4((a.cols + 1023) / 1024, grid.y, grid.z);
+            hipLaunchKernelGGL((transform_limited_pk_kernel<WORDS, MAXN>), grid4, dim3(256), 0, st, a);
+            return hipGetLastError();
+        }
+    }
     if (a.n == MAXN)
         hipLaunchKernelGGL((transform_limited_kernel<TIn, WORDS, MAXN, true>), grid, dim3(256), 0, st, a);
     else
@@ -884,6 +1021,10 @@ hipError_t launch_consistency(const ConsistencyArgs& a, hipStream_t st) {
     dim3 grid((a.cols + 255) / 256, a.rows);
     hipLaunchKernelGGL(consistency_kernel, grid, dim3(256), 0, st, a);
     return hipGetLastError();
+}
+
+int transform_kernel_kind(const TransformArgs& a, int depth, int mode, int words) {
+    return transform_pk_eligible(a, depth, mode, words) ? 1 : 0;
 }
 
 int agree_kernel_kind(const AgreeArgs& a, int depth) {

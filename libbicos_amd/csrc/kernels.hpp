@@ -112,6 +112,12 @@ struct ConsistencyArgs {
 
 
 hipError_t launch_transform(TransformArgs a, int depth, int mode, int words, hipStream_t st);
+// The kernel launch_transform picks for a's stacks (n, the bases -- stack1 may be null --, the
+// pitches and stack_bytes; no HIP call): 1 = transform_limited_pk_kernel (two pixels per
+// register from dword loads: u8, LIMITED, n one of 9 12 17 24 33 40 48 65 at its narrowest
+// descriptor, bases and pitches 4-byte aligned, the stacks within 256 MiB together,
+// BICOS_TRANSFORM_PK not 0), 0 = a one-pixel kernel
+int transform_kernel_kind(const TransformArgs& a, int depth, int mode, int words);
 SearchGeometry search_geometry(int rows, int cols, int words, int max_lds_bytes, int variant = 16,
                                int R = 0, int waves = 0, int split = 0, int cus = 256,
                                int extra_col_bytes = 0);

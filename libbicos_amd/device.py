@@ -208,6 +208,21 @@ class Engine:
             _lib.check(rc, "bicos_agree_kernel")
         return rc
 
+    def transform_kernel(self, stack0: torch.Tensor, stack1: Optional[torch.Tensor] = None,
+                         mode: int = 0, words: Optional[int] = None) -> int:
+        """bicos_transform_kernel: which kernel transform() (stack1 None) or match()'s
+        transform launch over both stacks runs for these views -- 1 two pixels per register
+        from dword loads (aligned u8 LIMITED stacks of a built size within 256 MiB together),
+        0 one pixel per lane."""
+        n, rows, cols, rp, pp = _check_stack(stack0)
+        words = words or descriptor_words(n, mode)
+        rc = self._L.bicos_transform_kernel(
+            stack0.data_ptr(), stack1.data_ptr() if stack1 is not None else None, n, rows, cols,
+            rp, pp, _depth(stack0), mode, words)
+        if rc < 0:
+            _lib.check(rc, "bicos_transform_kernel")
+        return rc
+
     def search_agree(self, desc0: torch.Tensor, desc1: torch.Tensor, stack0: torch.Tensor,
                      stack1: torch.Tensor, cfg: Optional[MatchConfig] = None,
                      out: Optional[torch.Tensor] = None, corrmap: Optional[torch.Tensor] = None,
