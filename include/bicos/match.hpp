@@ -27,4 +27,12 @@ namespace BICOS {
 void match(const std::vector<HipImage>& stack0, const std::vector<HipImage>& stack1, HipImage& disparity,
            Config cfg = Config{}, HipImage* corrmap = nullptr, hipStream_t stream = nullptr);
 
+// The guided match (an extension; include/bicos_c.h "disparity guide"): `guide`, an S16 image
+// of rows x 2 cols in the memory of the stacks, holds one disparity window {lo, hi} per left
+// pixel (bicos/guide.hpp builds one from a prior map); cfg.disparity_range supplies the global
+// window beside it (none: no global bound -- but Consistency's reverse search has no other).
+void match(const std::vector<HipImage>& stack0, const std::vector<HipImage>& stack1,
+           const HipImage& guide, HipImage& disparity, Config cfg = Config{},
+           HipImage* corrmap = nullptr, hipStream_t stream = nullptr);
+
 }  // namespace BICOS

@@ -575,6 +575,84 @@ int bicos_median_host(bicos_engine* e, const void* disparity, int disp_type, int
 /* The output tile (rows, cols) of one workgroup (tests). Returns BICOS_OK. */
 int bicos_median_tile(int* rows, int* cols);
 
+/* --------------------------------------------------------- disparity guide */
+/* The search restricted to one disparity window PER LEFT PIXEL, from a prior: the previous
+ * frame's map of a continuous scan, the match of a downsampled stack, a CAD pose, a
+ * neighbouring view (no reference counterpart).
+ *   guide       int16 pairs, guide[row * guide_pitch + col] = {lo, hi}: one dword per pixel, lo
+ *               in its low half. guide_pitch is counted in PIXELS (dwords) and is >= cols; the
+ *               base is 4-byte aligned. Device memory for the *_device entries, host memory
+ *               for bicos_match_host_guided.
+ *   window      every guided call also takes the global window min_disparity <= max_disparity
+ *               with the meaning and clamping of the *_range calls ("disparity range" above);
+ *               (INT_MIN, INT_MAX) is allowed and means no global bound.
+ *   candidates  of the left pixel (row, col0): C(row, col0) = { col1 : 0 <= col1 < cols and
+ *               max(min_disparity, lo) <= col0 - col1 <= min(max_disparity, hi) }
+ *   search      the reference's bicos_search over C in ascending col1: the first minimum wins;
+ *               NoDuplicates rejects a minimum that occurs more than once WITHIN C; a pixel
+ *               with an empty C is invalid. lo > hi is legal and gives an empty C ("do not
+ *               search here"); so does a window wholly outside the image.
+ *   consistency the right view has no prior, so its pixels have no guide: the reverse search
+ *               is exactly that of the *_range call with the same global window,
+ *               [-max_disparity, -min_disparity] with the descriptor sets swapped, run by the
+ *               same kernel. The max_lr_diff check and the output formula are unchanged. A
+ *               TIGHT GLOBAL WINDOW is therefore what keeps the reverse search fast: pass the
+ *               bounding window of the guide, not (INT_MIN, INT_MAX), where one is known. A
+ *               transposed per-pixel mask for the reverse search is left for a later change.
+ * Identities, byte for byte: a guide whose every pixel is (min_disparity, max_disparity) gives
+ * the *_range call's maps; a guide and a global window that both cover [-(cols-1), cols-1]
+ * give the unrestricted call's maps.
+ * Restrictions, those of the *_range calls: the guided search runs on the matrix cores only
+ * (search_guided.hip) with separate consistency / agree launches; bicos_match_plan reports
+ * nothing new; the multi-GPU entries (bicos_match_host_multi, bicos_match_bands_device) take
+ * no guide.
+ * A NULL guide, guide_pitch < cols, a base that is not 4-byte aligned and min_disparity >
+ * max_disparity are BICOS_E_ARG before any HIP call; bicos_last_error names the cause. */
+int bicos_search_device_guided(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1,
+                               int rows, int cols, int words, int flags, int max_lr_diff,
+                               int min_disparity, int max_disparity, const int16_t* guide,
+                               size_t guide_pitch, int16_t* out, void* stream);
+int bicos_match_device_guided(bicos_engine* e, const void* stack0, const void* stack1, int n,
+                              int rows, int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                              const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                              int max_disparity, const int16_t* guide, size_t guide_pitch,
+                              void* disparity, void* corrmap, void* stream);
+/* host buffers (the guide too; uploaded whole before the first band), synchronous */
+int bicos_match_host_guided(bicos_engine* e, const void* const* stack0, const void* const* stack1,
+                            int n, int rows, int cols, size_t step, int depth,
+                            const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                            int max_disparity, const int16_t* guide, size_t guide_pitch,
+                            void* disparity, void* corrmap);
+
+/* The guide builder: a rows x cols guide from a prior disparity map of its own size prows x
+ * pcols (dense). prior_type BICOS_CV_16S (invalid: -32768) or BICOS_CV_32F (invalid: NaN, and
+ * -32768.0f with BICOS_GUIDE_F32_SENTINEL). scale 1..8 (output pixels per prior pixel, and the
+ * factor of its disparities), radius 0..32767, spread 0..7, and the fallback pair, any two
+ * int16 values (lo > hi: "do not search here"). For the output pixel (r, c):
+ *   pr = min(r / scale, prows - 1), pc = min(c / scale, pcols - 1)
+ *   N  = the valid prior values in the (2 spread + 1)^2 window around (pr, pc), clipped to the
+ *        prior map
+ *   N empty:  {lo, hi} = {fallback_lo, fallback_hi}
+ *   else:     lo = scale * floor(min N) - radius
+ *             hi = scale * ceil(max N) + (scale - 1) + radius
+ * floor and ceil are taken in float and clamped to +-32767 before the conversion to int; lo
+ * and hi are computed in int32 and clamped to [-32767, 32767]: integer-exact throughout.
+ * counts, if not NULL: uint32[2] {from_prior, fallback}, which add up to rows * cols.
+ * guide_pitch in pixels, 0 = cols. One launch, no workspace. Out-of-range parameters, a null
+ * or misaligned guide and a null or empty prior for a non-empty guide are BICOS_E_ARG before
+ * any HIP call. */
+#define BICOS_GUIDE_F32_SENTINEL 1
+/* device: asynchronous on `stream`. Needs no workspace: e may be NULL. */
+int bicos_guide_device(bicos_engine* e, const void* prior, int prior_type, int prows, int pcols,
+                       int rows, int cols, int scale, int radius, int spread, int fallback_lo,
+                       int fallback_hi, int flags, int16_t* guide, size_t guide_pitch,
+                       uint32_t* counts, void* stream);
+/* host buffers, synchronous, e NULL = default engine */
+int bicos_guide_host(bicos_engine* e, const void* prior, int prior_type, int prows, int pcols,
+                     int rows, int cols, int scale, int radius, int spread, int fallback_lo,
+                     int fallback_hi, int flags, int16_t* guide, size_t guide_pitch,
+                     uint32_t counts[2]);
+
 /* Build identification (arch, flags) for reports. */
 const char* bicos_build_info(void);
 

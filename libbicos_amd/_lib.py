@@ -67,6 +67,8 @@ EXPORTS = (
     "bicos_rectify_maps_device", "bicos_rectify_maps_host", "bicos_rectify_device",
     "bicos_rectify_host", "bicos_rectify_tile",
     "bicos_median_device", "bicos_median_host", "bicos_median_tile",
+    "bicos_search_device_guided", "bicos_match_device_guided", "bicos_match_host_guided",
+    "bicos_guide_device", "bicos_guide_host",
 )
 
 # bicos_match_plan bits (include/bicos_c.h)
@@ -87,6 +89,11 @@ SPECKLE_F32_SENTINEL = 1
 
 # bicos_median_* flag (include/bicos_c.h)
 MEDIAN_F32_SENTINEL = 1
+
+# bicos_guide_* flag (include/bicos_c.h)
+GUIDE_F32_SENTINEL = 1
+
+INT_MIN, INT_MAX = -2 ** 31, 2 ** 31 - 1
 
 
 def build(verbose: bool = False, jobs: int = 4) -> str:
@@ -218,6 +225,18 @@ def lib() -> ctypes.CDLL:
     L.bicos_median_host.restype = I
     L.bicos_median_tile.argtypes = [PI, PI]
     L.bicos_median_tile.restype = I
+    L.bicos_search_device_guided.argtypes = [P, P, P, I, I, I, I, I, I, I, P, Z, P, P]
+    L.bicos_search_device_guided.restype = I
+    L.bicos_match_device_guided.argtypes = [P, P, P, I, I, I, Z, Z, I,
+                                            ctypes.POINTER(BicosConfig), I, I, I, P, Z, P, P, P]
+    L.bicos_match_device_guided.restype = I
+    L.bicos_match_host_guided.argtypes = [P, PP, PP, I, I, I, Z, I, ctypes.POINTER(BicosConfig), I,
+                                          I, I, P, Z, P, P]
+    L.bicos_match_host_guided.restype = I
+    L.bicos_guide_device.argtypes = [P, P, I, I, I, I, I, I, I, I, I, I, I, P, Z, P, P]
+    L.bicos_guide_device.restype = I
+    L.bicos_guide_host.argtypes = [P, P, I, I, I, I, I, I, I, I, I, I, I, P, Z, P]
+    L.bicos_guide_host.restype = I
     L.bicos_build_info.restype = ctypes.c_char_p
     L.bicos_build_info.argtypes = []
     _lib = L
@@ -242,6 +261,61 @@ def check_disparity_range(rng):
     if not (-2 ** 31 <= lo and hi < 2 ** 31):
         raise ValueError("disparity_range bounds must fit a C int")
     return lo, hi
+
+
+def check_guide_shape(shape, rows, cols):
+    """A guide's shape must be (rows, cols, 2) (ValueError otherwise): one int16 pair (lo, hi)
+    per left pixel (include/bicos_c.h "disparity guide")."""
+    if tuple(shape) != (rows, cols, 2):
+        raise ValueError("guide must have shape (%d, %d, 2): one (lo, hi) pair per pixel, got %s"
+                         % (rows, cols, tuple(shape)))
+
+
+def guide_window(rng):
+    """The global window of a guided call: check_disparity_range's pair, or no global bound
+    (INT_MIN, INT_MAX) for None."""
+    rng = check_disparity_range(rng)
+    return (INT_MIN, INT_MAX) if rng is None else rng
+
+
+def guide_params(radius, spread=0, scale=1, fallback=None):
+    """(radius, spread, scale, fallback_lo, fallback_hi) as the bicos_guide_* entries take them
+    (ValueError for what they would refuse): radius 0..32767, spread 0..7, scale 1..8, fallback
+    None (every disparity, (-32767, 32767)) or a pair of int16 values -- lo > hi is legal and
+    means "do not search here"."""
+    def integer(v, name, lo, hi):
+        if isinstance(v, bool) or not hasattr(v, "__index__"):
+            raise ValueError("%s must be an integer, got %r" % (name, v))
+        v = int(v)
+        if not lo <= v <= hi:
+            raise ValueError("%s must lie in [%d, %d], got %d" % (name, lo, hi, v))
+        return v
+
+    r = integer(radius, "radius", 0, 32767)
+    sp = integer(spread, "spread", 0, 7)
+    sc = integer(scale, "scale", 1, 8)
+    if fallback is None:
+        fallback = (-32767, 32767)
+    try:
+        flo, fhi = fallback
+    except (TypeError, ValueError):
+        raise ValueError("fallback must be None or a pair (lo, hi)") from None
+    return r, sp, sc, integer(flo, "fallback lo", -32768, 32767), \
+        integer(fhi, "fallback hi", -32768, 32767)
+
+
+def guide_shape(shape, prior_shape, scale):
+    """(rows, cols) of the guide to build: `shape`, or the prior's size times scale."""
+    if shape is None:
+        return int(prior_shape[0]) * scale, int(prior_shape[1]) * scale
+    try:
+        rows, cols = shape
+        rows, cols = int(rows), int(cols)
+    except (TypeError, ValueError):
+        raise ValueError("shape must be None or a pair (rows, cols)") from None
+    if rows < 0 or cols < 0 or rows * cols >= 2 ** 31:
+        raise ValueError("shape must be non-negative with fewer than 2^31 pixels, got %r" % (shape,))
+    return rows, cols
 
 
 def reproject_q(Q):

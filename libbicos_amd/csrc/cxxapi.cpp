@@ -6,6 +6,7 @@
 //   BICOS::filter_speckles  (bicos/speckle.hpp; no reference counterpart)
 //   BICOS::rectify_maps, BICOS::rectify  (bicos/rectify.hpp; no reference counterpart)
 //   BICOS::median_filter  (bicos/median.hpp; no reference counterpart)
+//   BICOS::guide_from_disparity, the guided BICOS::match  (bicos/guide.hpp; likewise)
 #include "engine.hpp"
 
 #include <algorithm>
@@ -21,6 +22,7 @@
 #include "../../include/bicos/speckle.hpp"
 #include "../../include/bicos/rectify.hpp"
 #include "../../include/bicos/median.hpp"
+#include "../../include/bicos/guide.hpp"
 
 using bicos_impl::check_hip;
 
@@ -88,9 +90,25 @@ void match(const std::vector<Image>& stack0, const std::vector<Image>& stack1, I
     impl::hip::match(stack0, stack1, disparity, cfg, corrmap, stream);
 }
 
+static void match_stacks(const std::vector<Image>& stack0, const std::vector<Image>& stack1,
+                         const Image* guide, Image& disparity, Config cfg, Image* corrmap,
+                         hipStream_t stream);
+
 // the backend seam (bicos/hip.hpp; reference include/cpu.hpp:27-33, include/cuda.hpp:27-34)
 void impl::hip::match(const std::vector<Image>& stack0, const std::vector<Image>& stack1,
                       Image& disparity, Config cfg, Image* corrmap, hipStream_t stream) {
+    match_stacks(stack0, stack1, nullptr, disparity, cfg, corrmap, stream);
+}
+
+// the guided match (bicos/match.hpp): cfg.disparity_range is the global window beside the guide
+void match(const std::vector<Image>& stack0, const std::vector<Image>& stack1, const Image& guide,
+           Image& disparity, Config cfg, Image* corrmap, hipStream_t stream) {
+    match_stacks(stack0, stack1, &guide, disparity, cfg, corrmap, stream);
+}
+
+static void match_stacks(const std::vector<Image>& stack0, const std::vector<Image>& stack1,
+                         const Image* guide, Image& disparity, Config cfg, Image* corrmap,
+                         hipStream_t stream) {
     const size_t n = stack0.size();
     if (n < 2) throw Exception("need at least two images");
     if (stack1.size() != n) throw Exception("stacks differ in length");
@@ -125,7 +143,20 @@ void impl::hip::match(const std::vector<Image>& stack0, const std::vector<Image>
         range = {cfg.disparity_range->min, cfg.disparity_range->max};
         throw_rc(bicos_impl::check_range(range.min, range.max));
     }
-    const bicos_impl::DispRange* rg = cfg.disparity_range ? &range : nullptr;
+    if (guide) {
+        // pairs {lo, hi} side by side: S16, rows x 2 cols, rows a whole number of dwords apart
+        if (guide->type() != S16 || guide->rows() != rows || guide->cols() != 2 * cols)
+            throw Exception("guide: need an S16 image of rows x 2 cols");
+        if (guide->memory() != mem) throw Exception("guide: must be in the memory of the stacks");
+        if (guide->step() % 4) throw Exception("guide: the row step must be a multiple of 4 bytes");
+        if (!cfg.disparity_range) range = {INT32_MIN, INT32_MAX};
+        range.guide = (const int16_t*)guide->data();
+        range.guide_pitch = guide->step() / 4;
+        if (rows > 0 && cols > 0)
+            throw_rc(bicos_impl::check_guide(range.guide, range.guide_pitch, cols, range.min,
+                                             range.max));
+    }
+    const bicos_impl::DispRange* rg = cfg.disparity_range || guide ? &range : nullptr;
     if (cfg.min_variance && *cfg.min_variance < 0) c.min_variance = -1.f;
 
     int dev = 0;
@@ -412,6 +443,58 @@ MedianStats median_filter(const Image& disparity, Image& out, int ksize, int fil
                            "counts download"));
     }
     return MedianStats{counts[0], counts[1], counts[2], counts[3]};
+}
+
+// ------------------------------------------------------ BICOS::guide_from_disparity
+// over the C entries (entries.cpp), which validate and launch
+
+namespace {
+
+void check_prior_map(const Image& prior) {
+    if (prior.type() != S16 && prior.type() != F32)
+        throw Exception("guide_from_disparity: the prior map must be S16 or F32");
+    if (prior.step() != (size_t)prior.cols() * prior.elemSize() && prior.rows() > 1)
+        throw Exception("guide_from_disparity: the prior map must be dense");
+    if ((int64_t)prior.cols() * 2 > INT32_MAX) throw Exception("guide_from_disparity: map too wide");
+}
+
+}  // namespace
+
+void guide_from_disparity(const Image& prior, Image& guide, int rows, int cols,
+                          const GuideParams& p, uint32_t* counts, hipStream_t stream) {
+    check_prior_map(prior);
+    if (prior.memory() != Memory::Device)
+        throw Exception("guide_from_disparity: device buffers need a device map");
+    if (rows < 0 || cols < 0 || cols > INT32_MAX / 2)
+        throw Exception("guide_from_disparity: bad guide size");
+    guide.create(rows, 2 * cols, S16, Memory::Device);
+    throw_rc(bicos_guide_device(nullptr, prior.data(), prior.type(), prior.rows(), prior.cols(),
+                                rows, cols, p.scale, p.radius, p.spread, p.fallback_lo,
+                                p.fallback_hi, p.flags, (int16_t*)guide.data(), guide.step() / 4,
+                                counts, stream));
+}
+
+GuideStats guide_from_disparity(const Image& prior, Image& guide, int rows, int cols,
+                                const GuideParams& p) {
+    check_prior_map(prior);
+    if (rows < 0 || cols < 0 || cols > INT32_MAX / 2)
+        throw Exception("guide_from_disparity: bad guide size");
+    uint32_t counts[2] = {0, 0};
+    if (prior.memory() == Memory::Host) {
+        guide.create(rows, 2 * cols, S16, Memory::Host);
+        throw_rc(bicos_guide_host(nullptr, prior.data(), prior.type(), prior.rows(), prior.cols(),
+                                  rows, cols, p.scale, p.radius, p.spread, p.fallback_lo,
+                                  p.fallback_hi, p.flags, (int16_t*)guide.data(),
+                                  guide.step() / 4, counts));
+    } else {
+        void* raw = nullptr;
+        throw_rc(check_hip(hipMalloc(&raw, sizeof counts), "hipMalloc(counts)"));
+        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
+        guide_from_disparity(prior, guide, rows, cols, p, (uint32_t*)raw, nullptr);
+        throw_rc(check_hip(hipMemcpy(counts, raw, sizeof counts, hipMemcpyDeviceToHost),
+                           "counts download"));
+    }
+    return GuideStats{counts[0], counts[1]};
 }
 
 // ------------------------------------------------- BICOS::rectify_maps, BICOS::rectify

@@ -8,6 +8,7 @@
 #include "reproject.hpp"
 #include "speckle.hpp"
 #include "median.hpp"
+#include "guide.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -275,6 +276,20 @@ int check_range(int min_disparity, int max_disparity) {
     return fail(BICOS_E_ARG, os.str());
 }
 
+int check_guide(const void* guide, size_t guide_pitch, int cols, int min_disparity,
+                int max_disparity) {
+    if (int rc0 = check_range(min_disparity, max_disparity)) return rc0;
+    if (!guide) return fail(BICOS_E_ARG, "disparity guide: null guide");
+    if (cols > 0 && guide_pitch < (size_t)cols) {
+        std::ostringstream os;
+        os << "disparity guide: guide_pitch " << guide_pitch << " is smaller than cols " << cols;
+        return fail(BICOS_E_ARG, os.str());
+    }
+    if ((uintptr_t)guide & 3u)
+        return fail(BICOS_E_ARG, "disparity guide: the guide's base is not 4-byte aligned");
+    return BICOS_OK;
+}
+
 static int required_bits(int n, int mode) { return mode ? n * n - 2 * n + 3 : 4 * n - 7; }
 
 // Consistency's reverse search (reference bicos.hpp:94-106, bicos.cuh:110-135): rev[col1] is
@@ -422,6 +437,13 @@ int run_search(const bicos_engine* e, const SearchPlan& p, const SearchBuffers& 
     const int hi = j.range ? std::min(std::max(j.range->max, -cols), cols) : 0;
     const bool tuned = e && e->tune_variant >= 64;
     auto search = [&](const bicos_hip::SearchArgs& sa, bool reverse, const char* what) {
+        // the guide holds windows of the LEFT pixels: the forward search alone reads it
+        if (j.range && j.range->guide && !reverse)
+            return check_hip(bicos_hip::launch_search_guided(
+                                 sa, lo, hi, j.range->guide, j.range->guide_pitch, words,
+                                 j.nodupes, j.used_bits, e ? e->cus : 256, st,
+                                 tuned ? e->tune_R : 0, tuned ? e->tune_waves : 0),
+                             what);
         if (j.range)
             return check_hip(bicos_hip::launch_search_range(
                                  sa, reverse ? -hi : lo, reverse ? -lo : hi, words, j.nodupes,
@@ -468,6 +490,9 @@ int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int row
                  const DispRange* range) {
     if (range)
         if (int rc0 = check_range(range->min, range->max)) return rc0;
+    if (range && range->guide)
+        if (int rc0 = check_guide(range->guide, range->guide_pitch, cols, range->min, range->max))
+            return rc0;
     if (!e) return fail(BICOS_E_ARG, "null engine");
     if (int rc0 = check_stack_shape(n, depth, rows, cols)) return rc0;
     if (cols > 32767)
@@ -698,6 +723,58 @@ int median_device(const MedianJob& j, hipStream_t st) {
     a.counts = j.counts;
     return check_hip(bicos_hip::launch_median(a, j.disp_type == BICOS_CV_32F, j.ksize, st),
                      "median launch");
+}
+
+// ------------------------------------------------------------ disparity guide
+
+int check_guide_job(const GuideJob& j) {
+    if (j.prior_type != BICOS_CV_16S && j.prior_type != BICOS_CV_32F)
+        return fail(BICOS_E_ARG, "guide: the prior map must be CV_16S or CV_32F");
+    if (j.scale < 1 || j.scale > 8) return fail(BICOS_E_ARG, "guide: scale must lie in 1 .. 8");
+    if (j.radius < 0 || j.radius > 32767)
+        return fail(BICOS_E_ARG, "guide: radius must lie in 0 .. 32767");
+    if (j.spread < 0 || j.spread > 7) return fail(BICOS_E_ARG, "guide: spread must lie in 0 .. 7");
+    if (j.fallback_lo < -32768 || j.fallback_lo > 32767 || j.fallback_hi < -32768 ||
+        j.fallback_hi > 32767)
+        return fail(BICOS_E_ARG, "guide: the fallback pair must fit int16");
+    if (j.flags & ~BICOS_GUIDE_F32_SENTINEL) return fail(BICOS_E_ARG, "guide: unknown flag bits");
+    if (j.rows < 0 || j.cols < 0 || j.prows < 0 || j.pcols < 0)
+        return fail(BICOS_E_ARG, "guide: negative image size");
+    if ((int64_t)j.rows * j.cols > INT32_MAX || (int64_t)j.prows * j.pcols > INT32_MAX)
+        return fail(BICOS_E_ARG, "guide: rows * cols exceeds int32");
+    if (j.guide_pitch && j.guide_pitch < (size_t)j.cols)
+        return fail(BICOS_E_ARG, "guide: guide_pitch is smaller than cols");
+    if (j.rows > 0 && j.cols > 0) {
+        if (j.prows == 0 || j.pcols == 0) return fail(BICOS_E_ARG, "guide: empty prior map");
+        if (!j.prior) return fail(BICOS_E_ARG, "guide: null prior map");
+        if (!j.guide) return fail(BICOS_E_ARG, "guide: null guide");
+        if ((uintptr_t)j.guide & 3u)
+            return fail(BICOS_E_ARG, "guide: the guide's base is not 4-byte aligned");
+    }
+    return BICOS_OK;
+}
+
+int guide_device(const GuideJob& j, hipStream_t st) {
+    if ((size_t)j.rows * j.cols == 0)  // nothing to launch: the counts are zero
+        return j.counts ? check_hip(hipMemsetAsync(j.counts, 0, 2 * sizeof(uint32_t), st),
+                                    "hipMemsetAsync(counts)")
+                        : (int)BICOS_OK;
+    bicos_hip::GuideArgs a{};
+    a.prior = j.prior;
+    a.prows = j.prows;
+    a.pcols = j.pcols;
+    a.guide = j.guide;
+    a.guide_pitch = j.guide_pitch ? j.guide_pitch : (size_t)j.cols;
+    a.rows = j.rows;
+    a.cols = j.cols;
+    a.scale = j.scale;
+    a.radius = j.radius;
+    a.spread = j.spread;
+    a.fallback_lo = j.fallback_lo;
+    a.fallback_hi = j.fallback_hi;
+    a.sentinel = (j.flags & BICOS_GUIDE_F32_SENTINEL) != 0;
+    a.counts = j.counts;
+    return check_hip(bicos_hip::launch_guide(a, j.prior_type == BICOS_CV_32F, st), "guide launch");
 }
 
 // ------------------------------------------------------------- rectification

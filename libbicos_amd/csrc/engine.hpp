@@ -8,12 +8,14 @@
 //               and match_device; reproject_device (disparity map -> 3-D points);
 //               speckle_device (the speckle filter of a disparity map); rectify_device and
 //               rectify_maps_device (raw stacks -> rectified stacks); median_device (the
-//               median filter of a disparity map)
+//               median filter of a disparity map); guide_device (a prior disparity map ->
+//               per-pixel search windows)
 //   host.cpp    the banded host-buffer pipeline (HostPool, match_host); reproject_host;
-//               speckle_host; rectify_host, rectify_maps_host; median_host
+//               speckle_host; rectify_host, rectify_maps_host; median_host; guide_host
 //   entries.cpp the bicos_* extern "C" entries (bicos_c.h) but the multi-GPU ones
 //   multi.cpp   bicos_match_host_multi, bicos_match_bands_device
-//   cxxapi.cpp  namespace BICOS (HipImage, match, reproject, filter_speckles, median_filter)
+//   cxxapi.cpp  namespace BICOS (HipImage, match, reproject, filter_speckles, median_filter,
+//               guide_from_disparity)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -178,8 +180,13 @@ void free_resources(bicos_engine* e);  // streams, events, pinned buffers; not w
 int descriptor_words(int n, int mode);
 
 // An inclusive disparity window min <= col0 - col1 <= max (bicos_c.h, the *_range entries)
+// guide != nullptr (the *_guided entries): besides, one window per left pixel for the forward
+// search, guide[row * guide_pitch + col] = {lo, hi} in device memory (4-byte aligned,
+// guide_pitch in pixels)
 struct DispRange {
     int min, max;
+    const int16_t* guide = nullptr;
+    size_t guide_pitch = 0;
 };
 
 // What the search stage runs (the search's BICOS_PLAN_* bits: MATRIX_CORES, PACKED_KEYS,
@@ -268,9 +275,31 @@ int match_host(bicos_engine* e, const void* const* p0, const size_t* steps0,
                const void* const* p1, const size_t* steps1, int n, int rows, int cols,
                int depth, const BicosConfig& cfg, bool has_nxcorr, float threshold, void* disp,
                void* corr, const DispRange* range = nullptr);
+// (range->guide, if any, is in HOST memory here: uploaded whole before the first band)
 
 // BICOS_E_ARG (with a message) for a window whose min exceeds its max; no HIP call
 int check_range(int min_disparity, int max_disparity);
+// ... and for what the *_guided entries refuse besides: a null guide, a pitch below cols, a
+// base that is not 4-byte aligned
+int check_guide(const void* guide, size_t guide_pitch, int cols, int min_disparity,
+                int max_disparity);
+
+// One guide build (bicos_c.h "disparity guide"): the arguments of bicos_guide_device /
+// bicos_guide_host, the pointers all in device or all in host memory.
+struct GuideJob {
+    const void* prior;
+    int prior_type, prows, pcols;
+    int rows, cols;
+    int scale, radius, spread;
+    int fallback_lo, fallback_hi;
+    int flags;
+    int16_t* guide;
+    size_t guide_pitch;  // pixels; 0 = cols
+    uint32_t* counts;
+};
+int check_guide_job(const GuideJob& j);  // BICOS_E_ARG (with a message); no HIP call
+int guide_device(const GuideJob& j, hipStream_t st);
+int guide_host(bicos_engine* e, const GuideJob& j);
 
 // One reprojection (bicos_c.h "reprojection"): the arguments of bicos_reproject_device /
 // bicos_reproject_host, the pointers all in device or all in host memory.

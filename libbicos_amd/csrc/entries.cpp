@@ -4,6 +4,7 @@
 #include "reproject.hpp"
 #include "speckle.hpp"
 #include "median.hpp"
+#include "guide.hpp"
 
 #include <cmath>
 #include <vector>
@@ -338,6 +339,69 @@ int bicos_search_device_range(bicos_engine* e, const uint32_t* desc0, const uint
     const DispRange range{min_disparity, max_disparity};
     return search_entry(e, desc0, desc1, rows, cols, words, flags, max_lr_diff, &range, out,
                         stream);
+}
+
+int bicos_search_device_guided(bicos_engine* e, const uint32_t* desc0, const uint32_t* desc1,
+                               int rows, int cols, int words, int flags, int max_lr_diff,
+                               int min_disparity, int max_disparity, const int16_t* guide,
+                               size_t guide_pitch, int16_t* out, void* stream) {
+    if (int rc0 = check_guide(guide, guide_pitch, cols, min_disparity, max_disparity)) return rc0;
+    const DispRange range{min_disparity, max_disparity, guide, guide_pitch};
+    return search_entry(e, desc0, desc1, rows, cols, words, flags, max_lr_diff, &range, out,
+                        stream);
+}
+
+int bicos_match_device_guided(bicos_engine* e, const void* stack0, const void* stack1, int n,
+                              int rows, int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                              const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                              int max_disparity, const int16_t* guide, size_t guide_pitch,
+                              void* disparity, void* corrmap, void* stream) {
+    if (int rc0 = check_guide(guide, guide_pitch, cols, min_disparity, max_disparity)) return rc0;
+    const DispRange range{min_disparity, max_disparity, guide, guide_pitch};
+    return match_device_entry(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth, cfg,
+                              has_nxcorr, disparity, corrmap, stream, false, &range);
+}
+
+int bicos_match_host_guided(bicos_engine* e, const void* const* stack0, const void* const* stack1,
+                            int n, int rows, int cols, size_t step, int depth,
+                            const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                            int max_disparity, const int16_t* guide, size_t guide_pitch,
+                            void* disparity, void* corrmap) {
+    if (int rc0 = check_guide(guide, guide_pitch, cols, min_disparity, max_disparity)) return rc0;
+    const DispRange range{min_disparity, max_disparity, guide, guide_pitch};
+    return match_host_entry(e, stack0, stack1, n, rows, cols, step, depth, cfg, has_nxcorr,
+                            disparity, corrmap, &range);
+}
+
+int bicos_guide_device(bicos_engine* e, const void* prior, int prior_type, int prows, int pcols,
+                       int rows, int cols, int scale, int radius, int spread, int fallback_lo,
+                       int fallback_hi, int flags, int16_t* guide, size_t guide_pitch,
+                       uint32_t* counts, void* stream) {
+    const GuideJob job{prior, prior_type, prows, pcols, rows, cols, scale, radius, spread,
+                       fallback_lo, fallback_hi, flags, guide, guide_pitch, counts};
+    if (int rc0 = check_guide_job(job)) return rc0;
+    (void)e;  // no workspace: nothing of the engine is used, so it may be NULL and is not locked
+    return guarded([&]() -> int { return guide_device(job, (hipStream_t)stream); });
+}
+
+int bicos_guide_host(bicos_engine* e, const void* prior, int prior_type, int prows, int pcols,
+                     int rows, int cols, int scale, int radius, int spread, int fallback_lo,
+                     int fallback_hi, int flags, int16_t* guide, size_t guide_pitch,
+                     uint32_t counts[2]) {
+    const GuideJob job{prior, prior_type, prows, pcols, rows, cols, scale, radius, spread,
+                       fallback_lo, fallback_hi, flags, guide, guide_pitch, counts};
+    if (int rc0 = check_guide_job(job)) return rc0;
+    return guarded([&]() -> int {
+        if (!e) {
+            int dev = 0;
+            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
+            if (rc) return rc;
+            e = default_engine(dev);
+            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        }
+        std::lock_guard<std::mutex> g(e->lock);
+        return guide_host(e, job);
+    });
 }
 
 int bicos_agree_stage_device(const int16_t* raw, const void* stack0, const void* stack1, int n,

@@ -121,6 +121,7 @@ struct HostMatch {
     // the stage: band-major stacks | disparity | corrmap (carve)
     char *dev = nullptr, *dev_disp = nullptr, *dev_corr = nullptr;
     char *hout_d = nullptr, *hout_c = nullptr;  // pinned maps (dl_bands)
+    int16_t* dev_guide = nullptr;  // the whole guide, dense (range->guide set)
 
     // BICOS_HOST_TRACE=1: per-phase host timestamps on stderr (tools/host_bench.py)
     const bool trace = host_trace();
@@ -158,6 +159,16 @@ struct HostMatch {
         dev = stage.take((size_t)B * band_bytes);
         dev_disp = stage.take(disp_bytes);
         dev_corr = corr ? stage.take(corr_bytes) : nullptr;
+        dev_guide = range && range->guide ? stage.take<int16_t>(2 * (size_t)rows * cols) : nullptr;
+    }
+
+    // the guide, whole, on the copy stream ahead of the first band's stacks (4 bytes per
+    // pixel against the stacks' 2 n: not worth a banded overlap)
+    int upload_guide() {
+        if (!dev_guide) return BICOS_OK;
+        return check_hip(hipMemcpy2DAsync(dev_guide, (size_t)cols * 4, range->guide,
+                                          range->guide_pitch * 4, (size_t)cols * 4, (size_t)rows,
+                                          hipMemcpyHostToDevice, ks), "guide upload");
     }
 
     // pinned slots, events, streams and the pool, each on first use / grown only
@@ -252,11 +263,17 @@ struct HostMatch {
         if (!rc) rc = check_hip(hipEventRecord(e->events[b], ks), "hipEventRecord");
         if (!rc) rc = check_hip(hipStreamWaitEvent(cs, e->events[b], 0), "hipStreamWaitEvent");
         if (rc) return rc;
+        // the band's window: the call's, with the band's rows of the uploaded guide
+        DispRange band_range = range ? *range : DispRange{0, 0};
+        if (dev_guide) {
+            band_range.guide = dev_guide + 2 * (size_t)r0 * cols;
+            band_range.guide_pitch = (size_t)cols;
+        }
         return match_device(e, band, band + (size_t)n * plane, n, br, cols, (size_t)cols,
                             (size_t)br * cols, depth, cfg, has_nxcorr, threshold,
                             dev_disp + (size_t)r0 * cols * dsz,
                             dev_corr ? dev_corr + (size_t)r0 * cols * csz : nullptr, cs, false,
-                            nullptr, nullptr, range);
+                            nullptr, nullptr, range ? &band_range : nullptr);
     }
 
     // band b's rows of the maps into pinned memory, as soon as they are matched (dl_bands)
@@ -335,12 +352,17 @@ int match_host(bicos_engine* e, const void* const* p0, const size_t* steps0,
                void* corr, const DispRange* range) {
     if (range)
         if (int rc0 = check_range(range->min, range->max)) return rc0;
+    if (range && range->guide)
+        if (int rc0 = check_guide(range->guide, range->guide_pitch, cols, range->min, range->max))
+            return rc0;
     if (!e) return fail(BICOS_E_ARG, "null engine");
     if (int rc0 = check_stack_shape(n, depth, rows, cols)) return rc0;
-    if (rows == 0 || cols == 0)  // validates the configuration, no work
+    if (rows == 0 || cols == 0) {  // validates the configuration, no work
+        const DispRange window = range ? DispRange{range->min, range->max} : DispRange{0, 0};
         return match_device(e, nullptr, nullptr, n, rows, cols, (size_t)cols,
                             (size_t)rows * cols, depth, cfg, has_nxcorr, threshold, disp, corr,
-                            e->own_stream, false, nullptr, nullptr, range);
+                            e->own_stream, false, nullptr, nullptr, range ? &window : nullptr);
+    }
     if (!p0 || !p1 || !disp) return fail(BICOS_E_ARG, "null buffer");
     for (int t = 0; t < n; ++t) {
         if (!p0[t] || !p1[t]) return fail(BICOS_E_ARG, "null image");
@@ -357,6 +379,7 @@ int match_host(bicos_engine* e, const void* const* p0, const size_t* steps0,
     if (!rc) rc = m.ensure_resources();
     if (rc) return rc;
     m.carve(stage);
+    rc = m.upload_guide();
     for (int b = 0; b < m.B && !rc; ++b) {
         rc = m.upload_and_match(b);
         if (!rc && m.dl_bands) rc = m.download_band(b);
@@ -569,6 +592,43 @@ int median_host(bicos_engine* e, const MedianJob& j) {
                        "filtered map download");
     if (!rc && j.counts)
         rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 4 * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, st), "counts download");
+    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    return rc ? rc : rc2;
+}
+
+int guide_host(bicos_engine* e, const GuideJob& j) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    if (int rc0 = check_guide_job(j)) return rc0;
+    const size_t pixels = (size_t)j.rows * j.cols;
+    if (pixels == 0) {
+        if (j.counts) std::fill(j.counts, j.counts + 2, 0u);
+        return BICOS_OK;
+    }
+    hipStream_t st = e->own_stream;
+    const size_t prior_bytes = (size_t)j.prows * j.pcols * (j.prior_type == BICOS_CV_32F ? 4 : 2);
+    const size_t pitch = j.guide_pitch ? j.guide_pitch : (size_t)j.cols;
+    GuideJob d = j;  // the same job on staged device buffers, the guide dense
+    d.guide_pitch = (size_t)j.cols;
+    Lease stage(e, e->stage, e->stage_bytes, st);
+    auto carve = [&] {
+        d.prior = stage.take(prior_bytes);
+        d.guide = stage.take<int16_t>(2 * pixels);
+        d.counts = j.counts ? stage.take<uint32_t>(2) : nullptr;
+    };
+    carve();
+    int rc = stage.acquire();
+    if (rc) return rc;
+    carve();
+    rc = check_hip(hipMemcpyAsync((void*)d.prior, j.prior, prior_bytes, hipMemcpyHostToDevice, st),
+                   "prior upload");
+    if (!rc) rc = guide_device(d, st);
+    if (!rc)
+        rc = check_hip(hipMemcpy2DAsync(j.guide, pitch * 4, d.guide, (size_t)j.cols * 4,
+                                        (size_t)j.cols * 4, (size_t)j.rows, hipMemcpyDeviceToHost,
+                                        st), "guide download");
+    if (!rc && j.counts)
+        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 2 * sizeof(uint32_t),
                                       hipMemcpyDeviceToHost, st), "counts download");
     const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
     return rc ? rc : rc2;

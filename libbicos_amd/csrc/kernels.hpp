@@ -92,6 +92,16 @@ struct SearchRangeArgs {
     int dmin, dmax;
 };
 
+// launch_search_guided: the windowed search with one window per left pixel besides the global
+// one. guide[row * guide_pitch + col0] = {lo, hi} (int16 pairs, one dword per pixel, 4-byte
+// aligned; guide_pitch in pixels)
+struct SearchGuidedArgs {
+    SearchArgs s;
+    int dmin, dmax;
+    const int16_t* guide;
+    size_t guide_pitch;
+};
+
 struct SearchGeometry {
     int chunk;              // col1 columns per LDS fill
     int waves;              // waves per workgroup
@@ -205,6 +215,13 @@ hipError_t launch_search_lr(SearchArgs a, int words, int bits, int max_lr_diff, 
 hipError_t launch_search_range(SearchArgs a, int dmin, int dmax, int words, bool nodupes,
                                int bits, int cus, hipStream_t st, int tiles = 0,
                                int waves_wg = 0);
+// Guided matrix-core search (search_guided.hip): launch_search_range with the candidates of
+// col0 further restricted to max(dmin, lo) <= col0 - col1 <= min(dmax, hi), {lo, hi} = the
+// pixel's pair of `guide` (SearchGuidedArgs; lo > hi: no candidate). Same outputs, tiles,
+// waves and K-step rules.
+hipError_t launch_search_guided(SearchArgs a, int dmin, int dmax, const int16_t* guide,
+                                size_t guide_pitch, int words, bool nodupes, int bits, int cus,
+                                hipStream_t st, int tiles = 0, int waves_wg = 0);
 hipError_t launch_agree(const AgreeArgs& a, int depth, bool dbl, hipStream_t st);
 // The kernel launch_agree picks for a's stacks (stack0's base, n and the pitches; no HIP call):
 // 2 = agree_lds_kernel, 1 = agree_reg_kernel, 0 = the generic agree_kernel (n > 65)

@@ -83,6 +83,28 @@ def _check_out(t: torch.Tensor, name: str, shape, dtypes, device: torch.device) 
         raise ValueError("%s must be contiguous (dense rows)" % name)
 
 
+def _guide_args(guide: torch.Tensor, rows: int, cols: int, device: torch.device):
+    """(pointer, pitch in pixels) of a guide tensor: int16 [rows, cols, 2] on `device`, the
+    pairs contiguous, rows a whole number of pairs apart (a view with a row stride is fine)."""
+    if not isinstance(guide, torch.Tensor) or guide.dtype != torch.int16:
+        raise ValueError("guide must be an int16 tensor")
+    if guide.device != device:
+        raise ValueError("guide must be on %s, got %s" % (device, guide.device))
+    _lib.check_guide_shape(guide.shape, rows, cols)
+    if rows * cols == 0:
+        return None, cols
+    if guide.stride(2) != 1 or (cols > 1 and guide.stride(1) != 2):
+        raise ValueError("guide pairs must be contiguous along a row")
+    pitch = cols
+    if rows > 1:
+        if guide.stride(0) % 2 or guide.stride(0) < 2 * cols:
+            raise ValueError("guide row stride must be an even number of int16 >= 2 * cols")
+        pitch = guide.stride(0) // 2
+    if guide.data_ptr() % 4:
+        raise ValueError("guide must start at a 4-byte aligned address")
+    return guide.data_ptr(), pitch
+
+
 def _stream(device: torch.device, stream=None) -> int:
     s = stream if stream is not None else torch.cuda.current_stream(device)
     return s.cuda_stream
@@ -132,9 +154,15 @@ class Engine:
     def match(self, stack0: torch.Tensor, stack1: torch.Tensor,
               cfg: Optional[MatchConfig] = None, want_corrmap: bool = True,
               out: Optional[torch.Tensor] = None, corrmap: Optional[torch.Tensor] = None,
-              stream=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+              stream=None, guide: Optional[torch.Tensor] = None
+              ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """Full BICOS::match on device stacks. Returns (disparity, corrmap) on the
         device; asynchronous on `stream` (default: torch's current stream).
+
+        guide: an int16 tensor [rows, cols, 2], one disparity window (lo, hi) per left pixel
+        (guide_from_disparity builds one from a prior map; bicos_match_device_guided,
+        include/bicos_c.h "disparity guide"); cfg.disparity_range is the global window beside
+        it, which Consistency's reverse search runs over -- keep it tight.
 
         With the NXC stage and no subpixel step, `out` may also be an int16 tensor: the
         integer disparity map (bicos_match_device_i16), whose float32 conversion is exactly
@@ -164,6 +192,19 @@ class Engine:
         rng = _lib.check_disparity_range(cfg.disparity_range)
         if rng is not None and i16:
             raise ValueError("disparity_range is not supported with an int16 `out` map")
+        if guide is not None:
+            if i16:
+                raise ValueError("guide is not supported with an int16 `out` map")
+            gptr, gpitch = _guide_args(guide, rows, cols, dev)
+            lo, hi = _lib.guide_window(rng)
+            if gptr is None:  # (an empty tensor has no pointer to hand over)
+                return out, corrmap
+            rc = self._L.bicos_match_device_guided(
+                self._h, stack0.data_ptr(), stack1.data_ptr(), n, rows, cols, rp, pp,
+                _depth(stack0), ctypes.byref(c), has_nxcorr, lo, hi, gptr, gpitch, out.data_ptr(),
+                corrmap.data_ptr() if corrmap is not None else None, _stream(dev, stream))
+            _lib.check(rc, "bicos_match_device_guided")
+            return out, corrmap
         if rng is not None:
             rc = self._L.bicos_match_device_range(
                 self._h, stack0.data_ptr(), stack1.data_ptr(), n, rows, cols, rp, pp,
@@ -456,6 +497,59 @@ class Engine:
         _lib.check(rc, "bicos_median_device")
         return out
 
+    # --------------------------------------------------------- disparity guide
+    def guide_from_disparity(self, prior: torch.Tensor, radius: int, spread: int = 0,
+                             scale: int = 1, fallback: Optional[Tuple[int, int]] = None,
+                             shape: Optional[Tuple[int, int]] = None, sentinel: bool = True,
+                             out: Optional[torch.Tensor] = None,
+                             counts: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """bicos_guide_device: the guide of match(guide=) / search(guide=) -- an int16 tensor
+        [rows, cols, 2] of windows (lo, hi) -- from a prior disparity map, int16 or float32
+        [prows, pcols] (invalid: int16 -32768, float NaN, and -32768.0 with `sentinel`);
+        include/bicos_c.h, "disparity guide". The output pixel (r, c) looks at the valid prior
+        values of the (2 spread + 1)^2 window around (r // scale, c // scale), clipped to the
+        prior: lo = scale * floor(min) - radius, hi = scale * ceil(max) + scale - 1 + radius,
+        clamped to +-32767; where there is none, `fallback` (None: every disparity; a pair
+        with lo > hi: do not search there). shape: (rows, cols) of the guide, default the
+        prior's size times scale. `counts`, an int32 [2] tensor on the map's device, receives
+        {from_prior, fallback} (uint32 bits).
+
+        The call NEVER synchronises: one launch on `stream` (default: torch's current stream)."""
+        if not prior.is_cuda:
+            raise ValueError("device API needs CUDA/HIP tensors")
+        if prior.dim() != 2:
+            raise ValueError("prior map must be [rows, cols]")
+        if prior.dtype not in (torch.int16, torch.float32):
+            raise ValueError("prior map must be int16 or float32, got %s" % prior.dtype)
+        if not prior.is_contiguous():
+            raise ValueError("prior map must be contiguous (dense rows)")
+        prows, pcols = prior.shape
+        if prows * pcols >= 2 ** 31:
+            raise ValueError("prior map has more than 2^31 - 1 pixels")
+        r, sp, sc, flo, fhi = _lib.guide_params(radius, spread, scale, fallback)
+        rows, cols = _lib.guide_shape(shape, (prows, pcols), sc)
+        dev = prior.device
+        if out is None:
+            out = torch.empty((rows, cols, 2), dtype=torch.int16, device=dev)
+        gptr, gpitch = _guide_args(out, rows, cols, dev)
+        if counts is not None:
+            _check_out(counts, "counts", (2,), (torch.int32,), dev)
+        if gptr is None:  # (an empty tensor has no pointer to hand over)
+            if counts is not None:
+                s = stream if stream is not None else torch.cuda.current_stream(dev)
+                with torch.cuda.stream(s):
+                    counts.zero_()
+            return out
+        if prows * pcols == 0:
+            raise ValueError("prior map is empty")
+        typ = _lib.CV_32F if prior.dtype == torch.float32 else _lib.CV_16S
+        rc = self._L.bicos_guide_device(
+            self._h, prior.data_ptr(), typ, prows, pcols, rows, cols, sc, r, sp, flo, fhi,
+            _lib.GUIDE_F32_SENTINEL if sentinel else 0, gptr, gpitch,
+            counts.data_ptr() if counts is not None else None, _stream(dev, stream))
+        _lib.check(rc, "bicos_guide_device")
+        return out
+
     # ----------------------------------------------------------- rectification
     def rectify_maps(self, K, D, R, P, size, stream=None):
         """bicos_rectify_maps_device: the float32 lookup maps (map_x, map_y), each [rows, cols]
@@ -542,11 +636,14 @@ class Engine:
     def search(self, desc0: torch.Tensor, desc1: torch.Tensor, cols: int, words: int,
                flags: int = 1, max_lr_diff: int = -1, out: Optional[torch.Tensor] = None,
                stream=None, bits: int = 0,
-               disparity_range: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+               disparity_range: Optional[Tuple[int, int]] = None,
+               guide: Optional[torch.Tensor] = None) -> torch.Tensor:
         """bits: how many low descriptor bits may be set (0 = all; see used_bits) -- the
         matrix-core search skips the K-steps above them (bicos_c.h flags bits 16-24).
         disparity_range: (lo, hi), search only col1 with lo <= col0 - col1 <= hi
-        (bicos_search_device_range)."""
+        (bicos_search_device_range).
+        guide: an int16 tensor [rows, cols, 2], one window (lo, hi) per left pixel, joined with
+        disparity_range (None: no global bound) -- bicos_search_device_guided."""
         rng = _lib.check_disparity_range(disparity_range)
         if not 0 <= bits <= 256:
             raise ValueError("bits must be in [0, 256]")
@@ -561,6 +658,16 @@ class Engine:
         if out is None:
             out = torch.empty((rows, cols), dtype=torch.int16, device=desc0.device)
         _check_out(out, "out", (rows, cols), (torch.int16,), desc0.device)
+        if guide is not None:
+            gptr, gpitch = _guide_args(guide, rows, cols, desc0.device)
+            lo, hi = _lib.guide_window(rng)
+            if gptr is None:  # (an empty tensor has no pointer to hand over)
+                return out
+            rc = self._L.bicos_search_device_guided(
+                self._h, desc0.data_ptr(), desc1.data_ptr(), rows, cols, words, flags, max_lr_diff,
+                lo, hi, gptr, gpitch, out.data_ptr(), _stream(desc0.device, stream))
+            _lib.check(rc, "bicos_search_device_guided")
+            return out
         if rng is not None:
             rc = self._L.bicos_search_device_range(
                 self._h, desc0.data_ptr(), desc1.data_ptr(), rows, cols, words, flags, max_lr_diff,
@@ -630,7 +737,7 @@ def default_engine(device=None) -> Engine:
 
 
 def match_bands(bands0: Sequence[torch.Tensor], bands1: Sequence[torch.Tensor],
-                cfg: Optional[MatchConfig] = None, want_corrmap: bool = True
+                cfg: Optional[MatchConfig] = None, want_corrmap: bool = True, guide=None
                 ) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
     """Single-process multi-GPU match (bicos_match_bands_device):
     bands0[b] / bands1[b] are the planar stacks [n, rows_b, cols] of row band b (bands in
@@ -640,6 +747,8 @@ def match_bands(bands0: Sequence[torch.Tensor], bands1: Sequence[torch.Tensor],
     cfg = cfg or MatchConfig()
     if cfg.disparity_range is not None:
         raise ValueError("disparity_range is not supported with several GPUs yet")
+    if guide is not None:
+        raise ValueError("a disparity guide is not supported with several GPUs yet")
     if len(bands0) == 0 or len(bands0) != len(bands1):
         raise ValueError("need the same number (>= 1) of left and right bands")
     k = len(bands0)

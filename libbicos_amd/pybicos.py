@@ -183,8 +183,21 @@ def _marshal(stack):
     return data, rows, cols, types, keep
 
 
-def match(stack0, stack1, cfg=None, devices=None):
+def _guide_array(guide, rows, cols):
+    """the guide as the host entry reads it: a C-contiguous int16 [rows, cols, 2] array"""
+    g = np.asarray(guide)
+    if g.dtype != np.int16:
+        raise ValueError(f"guide must be an int16 array, got {g.dtype}")
+    _lib.check_guide_shape(g.shape, rows, cols)
+    return np.ascontiguousarray(g)
+
+
+def match(stack0, stack1, cfg=None, devices=None, guide=None):
     """reference pybicos/__init__.py:199-244 -> (disparity, corrmap).
+
+    guide (an extension): an int16 array [rows, cols, 2], one disparity window (lo, hi) per
+    left pixel (guide_from_disparity builds one from a prior map; include/bicos_c.h "disparity
+    guide"); cfg.disparity_range is the global window beside it.
 
     devices (an extension; the reference is single-GPU): a sequence of GPU indices to split
     the frame's rows over from this process (bicos_match_host_multi: one band per device,
@@ -212,6 +225,23 @@ def match(stack0, stack1, cfg=None, devices=None):
     disparity = np.empty((rows, cols), ddtype)
     corrmap = np.empty((rows, cols), cdtype)
     rng = getattr(cfg, "disparity_range", None)
+    if guide is not None:
+        if devices is not None and len(list(devices)) > 1:
+            raise ValueError("a disparity guide is not supported with several GPUs yet")
+        if devices is not None:
+            raise ValueError("a guided match runs on the current device: leave devices unset")
+        g = _guide_array(guide, rows, cols)
+        lo, hi = _lib.guide_window(rng)
+        rc = 0
+        if rows * cols:
+            rc = L.bicos_match_host_guided(None, d0, d1, len(k0), rows, cols, 0, f.dtype.itemsize,
+                                           cfg._c_config, 1, lo, hi, g.ctypes.data, cols,
+                                           disparity.ctypes.data, corrmap.ctypes.data)
+        del k0, k1
+        if rc != 0:
+            raise RuntimeError("BICOS matching failed: " +
+                               L.bicos_last_error().decode(errors="replace"))
+        return disparity, corrmap
     if rng is not None and devices is not None and len(list(devices)) > 1:
         raise ValueError("disparity_range is not supported with several GPUs yet")
     if rng is not None:
@@ -372,6 +402,39 @@ def median_filter(disparity, ksize=3, fill_min=0, sentinel=True):
         raise RuntimeError("BICOS median filter failed: " +
                            L.bicos_last_error().decode(errors="replace"))
     return out, dict(unchanged=counts[0], changed=counts[1], filled=counts[2], invalid=counts[3])
+
+
+def guide_from_disparity(prior, radius, spread=0, scale=1, fallback=None, shape=None,
+                         sentinel=True):
+    """An extension: the guide of match(guide=) -- an int16 array [rows, cols, 2] of disparity
+    windows (lo, hi) -- from a prior disparity map, int16 or float32 [prows, pcols], e.g. the
+    map of a stack pooled by 2 with scale=2 (bicos_guide_host, include/bicos_c.h "disparity
+    guide": on the GPU, integer-exact). The output pixel (r, c) looks at the valid prior values
+    of the (2 spread + 1)^2 window around (r // scale, c // scale): lo = scale * floor(min) -
+    radius, hi = scale * ceil(max) + scale - 1 + radius; where there is none, `fallback` (None:
+    every disparity; lo > hi: do not search there). shape: (rows, cols), default the prior's
+    size times scale. Returns (guide, stats) with stats = dict(from_prior, fallback)."""
+    d = np.ascontiguousarray(prior)
+    if d.ndim != 2:
+        raise ValueError("prior map must be 2-D")
+    if d.dtype != np.int16 and d.dtype != np.float32:
+        raise ValueError(f"Unsupported prior dtype: {d.dtype}")
+    r, sp, sc, flo, fhi = _lib.guide_params(radius, spread, scale, fallback)
+    rows, cols = _lib.guide_shape(shape, d.shape, sc)
+    out = np.empty((rows, cols, 2), np.int16)
+    counts = (ctypes.c_uint32 * 2)()
+    if rows * cols == 0:
+        return out, dict(from_prior=0, fallback=0)
+    if d.size == 0:
+        raise ValueError("prior map is empty")
+    L = _lib.lib()
+    rc = L.bicos_guide_host(None, d.ctypes.data, _get_cv_type(d.dtype), d.shape[0], d.shape[1],
+                            rows, cols, sc, r, sp, flo, fhi,
+                            _lib.GUIDE_F32_SENTINEL if sentinel else 0, out.ctypes.data, cols,
+                            counts)
+    if rc != 0:
+        raise RuntimeError("BICOS guide failed: " + L.bicos_last_error().decode(errors="replace"))
+    return out, dict(from_prior=counts[0], fallback=counts[1])
 
 
 def invalid_disparity(dtype):
