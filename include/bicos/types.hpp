@@ -133,6 +133,15 @@ public:
         return ptr<T>(row)[col];
     }
 
+    // Rows [begin, end) as an image that shares the pixels and keeps them alive (like
+    // cv::Mat::rowRange): the n images of a stack cut out of one planar allocation.
+    HipImage rowRange(int begin, int end) const {
+        HipImage m = *this;
+        m._data = static_cast<char*>(_data) + (size_t)begin * _step;
+        m._rows = end - begin;
+        return m;
+    }
+
     // Copy to host (returns *this when already on the host).
     HipImage download() const;
 

@@ -653,6 +653,101 @@ int bicos_guide_host(bicos_engine* e, const void* prior, int prior_type, int pro
                      int fallback_hi, int flags, int16_t* guide, size_t guide_pitch,
                      uint32_t counts[2]);
 
+/* ---------------------------------------------------------- stack pooling */
+/* An image stack pooled by an integer factor, on the GPU: the first level of a coarse-to-fine
+ * match (the pyramid match below), defined in integers so that every caller gets the same
+ * pooled stack. The reference has no such step.
+ *     src    n planes of rows x cols, u8 (depth 1) or u16 (depth 2), element (t, y, x) at
+ *            base[t*src_plane_pitch + y*src_row_pitch + x]: pitches in ELEMENTS, exactly as
+ *            bicos_match_device takes them. Any base with the element's alignment and any
+ *            pitch >= a row are accepted: views of larger buffers are passed as they lie.
+ *     scale  s in 2 .. 8
+ *     dst    n planes of prows x pcols of the same depth with pitches of its own (elements),
+ *            prows = rows / s, pcols = cols / s (integer division). This is the size
+ *            bicos_guide_device expects of a prior at `scale` s: pr = min(r / s, prows - 1).
+ * For each plane t and output pixel (R, C):
+ *     sum = the s*s source elements of rows s*R .. s*R + s-1 and columns s*C .. s*C + s-1,
+ *           added in uint32 (at most 64 * 65535)
+ *     out = (sum + s*s/2) / (s*s)       integer division: the mean, rounded half up
+ * The result is exact, never above the depth's maximum, and there is no float anywhere. The
+ * trailing rows % s rows and cols % s columns are not read; nor is any byte between rows,
+ * between planes or around either view, and no byte outside the prows x pcols pixels of each
+ * output plane is written. (A numpy mean through float64 with .astype truncates instead of
+ * rounding: it is NOT this stage.)
+ * Alignment selects kernels, never results: a source whose base and two pitches are multiples
+ * of 4 BYTES is read by the dword-load kernel, every other source by the per-element kernel; the
+ * dword-load kernel stores four pixels at once where the output's base and two pitches are
+ * multiples of 4 bytes too, else element by element (bicos_pool_kernel says which).
+ * Argument errors are BICOS_E_ARG (bicos_last_error says which) before any HIP call: n < 1;
+ * depth not 1 or 2; scale outside 2 .. 8; rows < scale or cols < scale; a pitch smaller than a
+ * row; a NULL pointer; a u16 base that is not 2-byte aligned; a host step that is not a multiple
+ * of the element size; dst overlapping src on the device entry; a plane that spans more than
+ * 2^32 - 1 elements. A pitch is only held to be >= a row, so that interleaved layouts pass: an
+ * output whose own rows or planes overlap each other (dst_plane_pitch below (prows - 1) *
+ * dst_row_pitch + pcols without interleaving) is the caller's error, is not detected, and leaves
+ * the overlapping pixels undefined. */
+/* device: asynchronous on `stream`, one launch, no workspace: e may be NULL. */
+int bicos_pool_device(bicos_engine* e, const void* src, int n, int rows, int cols,
+                      size_t src_row_pitch, size_t src_plane_pitch, int depth, int scale,
+                      void* dst, size_t dst_row_pitch, size_t dst_plane_pitch, void* stream);
+/* host buffers, synchronous, e NULL = default engine: n image pointers in (rows x cols, src_step
+ * BYTES per row, 0 = dense) and n out (prows x pcols, dst_step likewise). Uploads what the
+ * launch reads, runs the same launch, downloads. */
+int bicos_pool_host(bicos_engine* e, const void* const* src, int n, int rows, int cols,
+                    size_t src_step, int depth, int scale, void* const* dst, size_t dst_step);
+/* The tile (rows, cols) of OUTPUT pixels one workgroup pools (tests). Returns BICOS_OK. */
+int bicos_pool_tile(int* rows, int* cols);
+/* Which kernel bicos_pool_device runs on these views (tests): bit 0 set: the dword-load kernel,
+ * clear: the per-element kernel; bit 1 set: the output is aligned for vector stores (used by
+ * the dword-load kernel alone). Pitches in elements. No launch. */
+int bicos_pool_kernel(const void* src, size_t src_row_pitch, size_t src_plane_pitch, int depth,
+                      const void* dst, size_t dst_row_pitch, size_t dst_plane_pitch);
+
+/* ---------------------------------------------------------- pyramid match */
+/* The coarse-to-fine match in one call: for scenes whose disparity range is too wide for one
+ * window. DEFINITION: the maps are byte for byte those of these four calls in this order on
+ * the same stream, with prows = rows / scale, pcols = cols / scale:
+ *   1. bicos_pool_device of both stacks with `scale` into dense prows x pcols stacks;
+ *   2. bicos_match_device_range of the pooled stacks with cfg' and the window
+ *      [floor(min_disparity / scale), ceil(max_disparity / scale)] (mathematical rounding, in
+ *      int64; bicos_pyramid_window), corrmap NULL. cfg' is cfg with subpixel_step = -1 and
+ *      nothing else changed; has_nxcorr is passed on. The coarse map's type is
+ *      bicos_output_type(cfg', has_nxcorr): float32 with the NXC stage, else int16;
+ *   3. bicos_guide_device of that map (prior_type its type) with prows, pcols, rows, cols,
+ *      scale, radius, spread, fallback_lo, fallback_hi, the flag BICOS_GUIDE_F32_SENTINEL,
+ *      guide_pitch = cols, and `counts`;
+ *   4. bicos_match_device_guided of the full stacks with cfg, the window [min_disparity,
+ *      max_disparity] and that guide.
+ * Optional outputs, each NULL or a buffer the call fills: `coarse`, the coarse map, dense
+ * prows x pcols; `guide`, dense rows x cols int16 pairs, 4-byte aligned (it can serve as the
+ * next frame's prior input); `counts`, uint32[2] {from_prior, fallback} of step 3. What the
+ * caller does not keep, and the pooled stacks always, lives in a buffer of the engine.
+ * The device entry only enqueues: no host synchronisation, and no allocation but the
+ * stream-ordered growth of the engine's buffers.
+ * Errors: whatever any of the four calls refuses, each detected before any HIP call.
+ * Restrictions, those of the guided entries: the searches run on the matrix cores only
+ * (search_range.hip, search_guided.hip) with separate consistency / agree launches; the
+ * multi-GPU entries have no pyramid form; there is no int16-out form (bicos_match_device_i16).
+ * The host entry uploads each stack once, whole, runs the device pyramid on the engine's own
+ * stream and downloads the maps and what else is asked for; it does not overlap upload and
+ * match band by band as bicos_match_host does. */
+int bicos_match_device_pyramid(bicos_engine* e, const void* stack0, const void* stack1, int n,
+                               int rows, int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                               const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                               int max_disparity, int scale, int radius, int spread,
+                               int fallback_lo, int fallback_hi, void* disparity, void* corrmap,
+                               void* coarse, int16_t* guide, uint32_t* counts, void* stream);
+/* host buffers (coarse, guide and counts too), `step` BYTES per image row (0 = dense),
+ * synchronous, e NULL = default engine */
+int bicos_match_host_pyramid(bicos_engine* e, const void* const* stack0, const void* const* stack1,
+                             int n, int rows, int cols, size_t step, int depth,
+                             const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                             int max_disparity, int scale, int radius, int spread, int fallback_lo,
+                             int fallback_hi, void* disparity, void* corrmap, void* coarse,
+                             int16_t* guide, uint32_t counts[2]);
+/* The coarse window of step 2 (scale 2 .. 8, else BICOS_E_ARG). */
+int bicos_pyramid_window(int min_disparity, int max_disparity, int scale, int* lo, int* hi);
+
 /* Build identification (arch, flags) for reports. */
 const char* bicos_build_info(void);
 

@@ -69,6 +69,8 @@ EXPORTS = (
     "bicos_median_device", "bicos_median_host", "bicos_median_tile",
     "bicos_search_device_guided", "bicos_match_device_guided", "bicos_match_host_guided",
     "bicos_guide_device", "bicos_guide_host",
+    "bicos_pool_device", "bicos_pool_host", "bicos_pool_tile", "bicos_pool_kernel",
+    "bicos_match_device_pyramid", "bicos_match_host_pyramid", "bicos_pyramid_window",
 )
 
 # bicos_match_plan bits (include/bicos_c.h)
@@ -237,6 +239,23 @@ def lib() -> ctypes.CDLL:
     L.bicos_guide_device.restype = I
     L.bicos_guide_host.argtypes = [P, P, I, I, I, I, I, I, I, I, I, I, I, P, Z, P]
     L.bicos_guide_host.restype = I
+    L.bicos_pool_device.argtypes = [P, P, I, I, I, Z, Z, I, I, P, Z, Z, P]
+    L.bicos_pool_device.restype = I
+    L.bicos_pool_host.argtypes = [P, PP, I, I, I, Z, I, I, PP, Z]
+    L.bicos_pool_host.restype = I
+    L.bicos_pool_tile.argtypes = [PI, PI]
+    L.bicos_pool_tile.restype = I
+    L.bicos_pool_kernel.argtypes = [P, Z, Z, I, P, Z, Z]
+    L.bicos_pool_kernel.restype = I
+    L.bicos_match_device_pyramid.argtypes = [P, P, P, I, I, I, Z, Z, I,
+                                             ctypes.POINTER(BicosConfig), I, I, I, I, I, I, I, I,
+                                             P, P, P, P, P, P]
+    L.bicos_match_device_pyramid.restype = I
+    L.bicos_match_host_pyramid.argtypes = [P, PP, PP, I, I, I, Z, I, ctypes.POINTER(BicosConfig),
+                                           I, I, I, I, I, I, I, I, P, P, P, P, P]
+    L.bicos_match_host_pyramid.restype = I
+    L.bicos_pyramid_window.argtypes = [I, I, I, PI, PI]
+    L.bicos_pyramid_window.restype = I
     L.bicos_build_info.restype = ctypes.c_char_p
     L.bicos_build_info.argtypes = []
     _lib = L
@@ -316,6 +335,53 @@ def guide_shape(shape, prior_shape, scale):
     if rows < 0 or cols < 0 or rows * cols >= 2 ** 31:
         raise ValueError("shape must be non-negative with fewer than 2^31 pixels, got %r" % (shape,))
     return rows, cols
+
+
+def pool_scale(scale):
+    """The pooling factor as the bicos_pool_* entries take it: an integer in 2..8 (ValueError
+    otherwise)."""
+    if isinstance(scale, bool) or not hasattr(scale, "__index__"):
+        raise ValueError("scale must be an integer, got %r" % (scale,))
+    scale = int(scale)
+    if not 2 <= scale <= 8:
+        raise ValueError("scale must lie in [2, 8], got %d" % scale)
+    return scale
+
+
+def pool_shape(rows, cols, scale):
+    """(prows, pcols) = (rows // scale, cols // scale) of a pooled image (ValueError for an
+    image smaller than scale x scale)."""
+    if rows < scale or cols < scale:
+        raise ValueError("a %d x %d image is smaller than scale x scale (%d)" % (rows, cols, scale))
+    return rows // scale, cols // scale
+
+
+def pool_tile():
+    """(rows, cols) of the output tile one workgroup pools (bicos_pool_tile)."""
+    r, c = ctypes.c_int(0), ctypes.c_int(0)
+    lib().bicos_pool_tile(ctypes.byref(r), ctypes.byref(c))
+    return r.value, c.value
+
+
+def pyramid_window(rng, scale):
+    """The coarse match's window of a pyramid match: (floor(lo / scale), ceil(hi / scale))
+    (include/bicos_c.h "pyramid match")."""
+    lo, hi = rng
+    return lo // scale, -((-hi) // scale)
+
+
+def pyramid_params(disparity_range, scale=2, radius=2, spread=1, fallback=None):
+    """((lo, hi), scale, radius, spread, fallback_lo, fallback_hi) as the *_pyramid entries take
+    them (ValueError for what they would refuse): disparity_range is required, scale 2..8,
+    radius and spread as guide_params; fallback None is the global window clamped to +-32767."""
+    rng = check_disparity_range(disparity_range)
+    if rng is None:
+        raise ValueError("match_pyramid needs cfg.disparity_range: the global window of both levels")
+    sc = pool_scale(scale)
+    if fallback is None:
+        fallback = (max(rng[0], -32767), min(rng[1], 32767))
+    r, sp, _, flo, fhi = guide_params(radius, spread, sc, fallback)
+    return rng, sc, r, sp, flo, fhi
 
 
 def reproject_q(Q):

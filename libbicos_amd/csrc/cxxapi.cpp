@@ -7,6 +7,7 @@
 //   BICOS::rectify_maps, BICOS::rectify  (bicos/rectify.hpp; no reference counterpart)
 //   BICOS::median_filter  (bicos/median.hpp; no reference counterpart)
 //   BICOS::guide_from_disparity, the guided BICOS::match  (bicos/guide.hpp; likewise)
+//   BICOS::pool_stack, BICOS::match_pyramid  (bicos/pool.hpp; likewise)
 #include "engine.hpp"
 
 #include <algorithm>
@@ -23,6 +24,7 @@
 #include "../../include/bicos/rectify.hpp"
 #include "../../include/bicos/median.hpp"
 #include "../../include/bicos/guide.hpp"
+#include "../../include/bicos/pool.hpp"
 
 using bicos_impl::check_hip;
 
@@ -90,9 +92,17 @@ void match(const std::vector<Image>& stack0, const std::vector<Image>& stack1, I
     impl::hip::match(stack0, stack1, disparity, cfg, corrmap, stream);
 }
 
+// what match_pyramid adds to a match: its parameters and its optional outputs
+struct PyramidCall {
+    PyramidParams params;
+    Image* coarse;
+    Image* guide;
+    uint32_t* counts;
+};
+
 static void match_stacks(const std::vector<Image>& stack0, const std::vector<Image>& stack1,
                          const Image* guide, Image& disparity, Config cfg, Image* corrmap,
-                         hipStream_t stream);
+                         hipStream_t stream, const PyramidCall* pyr = nullptr);
 
 // the backend seam (bicos/hip.hpp; reference include/cpu.hpp:27-33, include/cuda.hpp:27-34)
 void impl::hip::match(const std::vector<Image>& stack0, const std::vector<Image>& stack1,
@@ -106,9 +116,18 @@ void match(const std::vector<Image>& stack0, const std::vector<Image>& stack1, c
     match_stacks(stack0, stack1, &guide, disparity, cfg, corrmap, stream);
 }
 
+// the pyramid match (bicos/pool.hpp): cfg.disparity_range is the global window of both levels
+void match_pyramid(const std::vector<Image>& stack0, const std::vector<Image>& stack1,
+                   Image& disparity, Config cfg, const PyramidParams& params, Image* corrmap,
+                   Image* coarse, Image* guide, uint32_t* counts, hipStream_t stream) {
+    if (!cfg.disparity_range) throw Exception("match_pyramid: cfg.disparity_range is required");
+    const PyramidCall call{params, coarse, guide, counts};
+    match_stacks(stack0, stack1, nullptr, disparity, cfg, corrmap, stream, &call);
+}
+
 static void match_stacks(const std::vector<Image>& stack0, const std::vector<Image>& stack1,
                          const Image* guide, Image& disparity, Config cfg, Image* corrmap,
-                         hipStream_t stream) {
+                         hipStream_t stream, const PyramidCall* pyr) {
     const size_t n = stack0.size();
     if (n < 2) throw Exception("need at least two images");
     if (stack1.size() != n) throw Exception("stacks differ in length");
@@ -158,6 +177,21 @@ static void match_stacks(const std::vector<Image>& stack0, const std::vector<Ima
     }
     const bicos_impl::DispRange* rg = cfg.disparity_range || guide ? &range : nullptr;
     if (cfg.min_variance && *cfg.min_variance < 0) c.min_variance = -1.f;
+    bicos_impl::PyramidJob pj{};
+    if (pyr) {
+        const PyramidParams& p = pyr->params;
+        pj.scale = p.scale;
+        pj.radius = p.radius;
+        pj.spread = p.spread;
+        pj.fallback_lo = p.fallback_window ? std::max(range.min, -32767) : p.fallback_lo;
+        pj.fallback_hi = p.fallback_window ? std::min(range.max, 32767) : p.fallback_hi;
+        // the argument errors of all four steps before an output is created (any non-null
+        // placeholder stands for the buffers that do not exist yet)
+        const void* some = &pj;
+        throw_rc(bicos_impl::check_pyramid(some, some, (int)n, rows, cols, (size_t)cols,
+                                           (size_t)rows * cols, depth, c, has_nxcorr, range, pj,
+                                           some));
+    }
 
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -181,6 +215,21 @@ static void match_stacks(const std::vector<Image>& stack0, const std::vector<Ima
         }
         disparity.create(rows, cols, dtype, Memory::Host);
         if (want_corr) corrmap->create(rows, cols, dbl ? F64 : F32, Memory::Host);
+        if (pyr) {
+            for (size_t t = 0; t < n; ++t)
+                if (st0[t] != st0[0] || st1[t] != st0[0])
+                    throw Exception("match_pyramid: host images must share one step");
+            if (pyr->coarse) pyr->coarse->create(rows / pj.scale, cols / pj.scale, dtype, Memory::Host);
+            if (pyr->guide) pyr->guide->create(rows, 2 * cols, S16, Memory::Host);
+            pj.coarse = pyr->coarse ? pyr->coarse->data() : nullptr;
+            pj.guide = pyr->guide ? (int16_t*)pyr->guide->data() : nullptr;
+            pj.counts = pyr->counts;
+            throw_rc(bicos_impl::match_pyramid_host(
+                e, p0.data(), p1.data(), st0[0], (int)n, rows, cols, depth, c, has_nxcorr,
+                c.nxcorr_threshold, range, pj, disparity.data(),
+                want_corr ? corrmap->data() : nullptr));
+            return;
+        }
         throw_rc(bicos_impl::match_host(e, p0.data(), st0.data(), p1.data(), st1.data(), (int)n,
                                         rows, cols, depth, c, has_nxcorr, c.nxcorr_threshold,
                                         disparity.data(), want_corr ? corrmap->data() : nullptr,
@@ -241,6 +290,18 @@ static void match_stacks(const std::vector<Image>& stack0, const std::vector<Ima
 
     disparity.create(rows, cols, dtype, Memory::Device);
     if (want_corr) corrmap->create(rows, cols, dbl ? F64 : F32, Memory::Device);
+    if (pyr) {
+        if (pyr->coarse) pyr->coarse->create(rows / pj.scale, cols / pj.scale, dtype, Memory::Device);
+        if (pyr->guide) pyr->guide->create(rows, 2 * cols, S16, Memory::Device);
+        pj.coarse = pyr->coarse ? pyr->coarse->data() : nullptr;
+        pj.guide = pyr->guide ? (int16_t*)pyr->guide->data() : nullptr;
+        pj.counts = pyr->counts;
+        throw_rc(bicos_impl::match_pyramid_device(
+            e, s0, s1, (int)n, rows, cols, row_pitch, plane_pitch, depth, c, has_nxcorr,
+            c.nxcorr_threshold, range, pj, disparity.data(),
+            want_corr ? corrmap->data() : nullptr, st));
+        return;
+    }
     throw_rc(bicos_impl::match_device(e, s0, s1, (int)n, rows, cols, row_pitch, plane_pitch, depth,
                                       c, has_nxcorr, c.nxcorr_threshold, disparity.data(),
                                       want_corr ? corrmap->data() : nullptr, st, false, nullptr,
@@ -592,6 +653,72 @@ void rectify(const std::vector<Image>& stack, const Image& map_x, const Image& m
                                       s.step() / depth, s.step() / depth * s.rows(), (int)depth, mx,
                                       my, map_x.step(), rows, cols, o.data(), o.step() / depth,
                                       o.step() / depth * o.rows(), border, t ? nullptr : vp, stream));
+    }
+}
+
+// ---------------------------------------------------------------- BICOS::pool_stack
+// over the C entries (entries.cpp), which validate and launch
+
+void pool_stack(const std::vector<Image>& stack, int scale, std::vector<Image>& out_stack,
+                hipStream_t stream) {
+    if (stack.empty()) throw Exception("pool_stack: empty image stack");
+    const Image& f = stack[0];
+    const int type = f.type();
+    if (type != U8 && type != U16) throw Exception("pool_stack: the images must be U8 or U16");
+    if (scale < 2 || scale > 8) throw Exception("pool_stack: scale must lie in 2 .. 8");
+    if (f.rows() < scale || f.cols() < scale)
+        throw Exception("pool_stack: the images are smaller than scale x scale");
+    const Memory mem = f.memory();
+    for (const Image& im : stack)
+        if (im.rows() != f.rows() || im.cols() != f.cols() || im.type() != type ||
+            im.memory() != mem || !im.data())
+            throw Exception("pool_stack: all images must share size, type and memory");
+    if (&out_stack == &stack) throw Exception("pool_stack: the output must not be the source");
+    const size_t n = stack.size(), depth = f.elemSize();
+    const int prows = f.rows() / scale, pcols = f.cols() / scale;
+    out_stack.resize(n);
+    const bool fresh = std::none_of(out_stack.begin(), out_stack.end(), [&](const Image& o) {
+        return o.data() && o.rows() == prows && o.cols() == pcols && o.type() == type &&
+               o.memory() == mem;
+    });
+    if (fresh && mem == Memory::Device) {
+        // one planar allocation for the n outputs: the one-launch path below, and a stack that
+        // match() reads zero-copy
+        const Image planar = Image::allocate((int)n * prows, pcols, type, mem);
+        for (size_t t = 0; t < n; ++t)
+            out_stack[t] = planar.rowRange((int)t * prows, (int)(t + 1) * prows);
+    } else {
+        for (Image& o : out_stack) o.create(prows, pcols, type, mem);
+    }
+    if (mem == Memory::Host) {
+        std::vector<const void*> src(n);
+        std::vector<void*> dst(n);
+        for (size_t t = 0; t < n; ++t) {
+            if (stack[t].step() != f.step() || out_stack[t].step() != out_stack[0].step())
+                throw Exception("pool_stack: host images of one stack must share one step");
+            src[t] = stack[t].data();
+            dst[t] = out_stack[t].data();
+        }
+        throw_rc(bicos_pool_host(nullptr, src.data(), (int)n, f.rows(), f.cols(), f.step(),
+                                 (int)depth, scale, dst.data(), out_stack[0].step()));
+        return;
+    }
+    if (f.step() % depth || out_stack[0].step() % depth)
+        throw Exception("pool_stack: an image step is not a multiple of the pixel size");
+    const size_t sp = planar_pitch(stack), dp = planar_pitch(out_stack);
+    if (sp && dp) {
+        throw_rc(bicos_pool_device(nullptr, f.data(), (int)n, f.rows(), f.cols(), f.step() / depth,
+                                   sp / depth, (int)depth, scale, out_stack[0].data(),
+                                   out_stack[0].step() / depth, dp / depth, stream));
+        return;
+    }
+    for (size_t t = 0; t < n; ++t) {
+        const Image &s = stack[t], &o = out_stack[t];
+        if (s.step() % depth || o.step() % depth)
+            throw Exception("pool_stack: an image step is not a multiple of the pixel size");
+        throw_rc(bicos_pool_device(nullptr, s.data(), 1, s.rows(), s.cols(), s.step() / depth,
+                                   s.step() / depth * s.rows(), (int)depth, scale, o.data(),
+                                   o.step() / depth, o.step() / depth * o.rows(), stream));
     }
 }
 

@@ -9,6 +9,7 @@
 #include "speckle.hpp"
 #include "median.hpp"
 #include "guide.hpp"
+#include "pool.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -483,17 +484,10 @@ bicos_hip::AgreeArgs agree_args(const int16_t* raw, const void* s0, const void* 
                                 out_f32 ? 1 : 0, corr, span};
 }
 
-int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int rows, int cols,
-                 size_t row_pitch, size_t plane_pitch, int depth, const BicosConfig& cfg,
-                 bool has_nxcorr, float threshold, void* disp, void* corr, hipStream_t st,
-                 bool disp_i16, const uint32_t* ext_d0, const uint32_t* ext_d1,
-                 const DispRange* range) {
-    if (range)
-        if (int rc0 = check_range(range->min, range->max)) return rc0;
-    if (range && range->guide)
-        if (int rc0 = check_guide(range->guide, range->guide_pitch, cols, range->min, range->max))
-            return rc0;
-    if (!e) return fail(BICOS_E_ARG, "null engine");
+int check_match(const void* s0, const void* s1, int n, int rows, int cols, size_t row_pitch,
+                size_t plane_pitch, int depth, const BicosConfig& cfg, bool has_nxcorr,
+                const void* disp, bool disp_i16, MatchShape* out) {
+    *out = MatchShape{};
     if (int rc0 = check_stack_shape(n, depth, rows, cols)) return rc0;
     if (cols > 32767)
         return fail(BICOS_E_ARG, "image width exceeds the int16 disparity range (32767)");
@@ -512,12 +506,33 @@ int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int row
         return fail(BICOS_E_ARG, "subpixel_step too small (more than 65536 interpolation steps)");
     if (disp_i16 && has_step)
         return fail(BICOS_E_ARG, "an int16 disparity map cannot hold subpixel disparities");
+    *out = MatchShape{mode, words, has_step, nsteps, 0};
     if (rows == 0 || cols == 0) return BICOS_OK;
     if (!s0 || !s1 || !disp) return fail(BICOS_E_ARG, "null buffer");
     if (row_pitch < (size_t)cols || plane_pitch < (size_t)rows * row_pitch)
         return fail(BICOS_E_ARG, "row/plane pitch smaller than the image");
-    uint32_t span = 0;
-    if (int rc0 = stack_span(n, rows, cols, row_pitch, plane_pitch, depth, &span)) return rc0;
+    return stack_span(n, rows, cols, row_pitch, plane_pitch, depth, &out->span);
+}
+
+int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int rows, int cols,
+                 size_t row_pitch, size_t plane_pitch, int depth, const BicosConfig& cfg,
+                 bool has_nxcorr, float threshold, void* disp, void* corr, hipStream_t st,
+                 bool disp_i16, const uint32_t* ext_d0, const uint32_t* ext_d1,
+                 const DispRange* range) {
+    if (range)
+        if (int rc0 = check_range(range->min, range->max)) return rc0;
+    if (range && range->guide)
+        if (int rc0 = check_guide(range->guide, range->guide_pitch, cols, range->min, range->max))
+            return rc0;
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    MatchShape shape;
+    if (int rc0 = check_match(s0, s1, n, rows, cols, row_pitch, plane_pitch, depth, cfg, has_nxcorr,
+                              disp, disp_i16, &shape))
+        return rc0;
+    if (rows == 0 || cols == 0) return BICOS_OK;
+    const int mode = shape.mode, words = shape.words, nsteps = shape.nsteps;
+    const bool has_step = shape.has_step;
+    const uint32_t span = shape.span;
 
     const bool consistency = cfg.variant_type != 0;
     const bool dbl = cfg.precision != 0;
@@ -727,9 +742,7 @@ int median_device(const MedianJob& j, hipStream_t st) {
 
 // ------------------------------------------------------------ disparity guide
 
-int check_guide_job(const GuideJob& j) {
-    if (j.prior_type != BICOS_CV_16S && j.prior_type != BICOS_CV_32F)
-        return fail(BICOS_E_ARG, "guide: the prior map must be CV_16S or CV_32F");
+int check_guide_params(const GuideJob& j) {
     if (j.scale < 1 || j.scale > 8) return fail(BICOS_E_ARG, "guide: scale must lie in 1 .. 8");
     if (j.radius < 0 || j.radius > 32767)
         return fail(BICOS_E_ARG, "guide: radius must lie in 0 .. 32767");
@@ -738,6 +751,13 @@ int check_guide_job(const GuideJob& j) {
         j.fallback_hi > 32767)
         return fail(BICOS_E_ARG, "guide: the fallback pair must fit int16");
     if (j.flags & ~BICOS_GUIDE_F32_SENTINEL) return fail(BICOS_E_ARG, "guide: unknown flag bits");
+    return BICOS_OK;
+}
+
+int check_guide_job(const GuideJob& j) {
+    if (j.prior_type != BICOS_CV_16S && j.prior_type != BICOS_CV_32F)
+        return fail(BICOS_E_ARG, "guide: the prior map must be CV_16S or CV_32F");
+    if (int rc0 = check_guide_params(j)) return rc0;
     if (j.rows < 0 || j.cols < 0 || j.prows < 0 || j.pcols < 0)
         return fail(BICOS_E_ARG, "guide: negative image size");
     if ((int64_t)j.rows * j.cols > INT32_MAX || (int64_t)j.prows * j.pcols > INT32_MAX)
@@ -775,6 +795,160 @@ int guide_device(const GuideJob& j, hipStream_t st) {
     a.sentinel = (j.flags & BICOS_GUIDE_F32_SENTINEL) != 0;
     a.counts = j.counts;
     return check_hip(bicos_hip::launch_guide(a, j.prior_type == BICOS_CV_32F, st), "guide launch");
+}
+
+// ------------------------------------------------------------- stack pooling
+
+static bicos_hip::PoolArgs pool_args(const PoolJob& j) {
+    bicos_hip::PoolArgs a{};
+    a.src = j.src;
+    a.dst = j.dst;
+    a.n = j.n;
+    a.prows = j.rows / j.scale;
+    a.pcols = j.cols / j.scale;
+    a.src_row_pitch = (uint32_t)j.src_row_pitch;
+    a.dst_row_pitch = (uint32_t)j.dst_row_pitch;
+    a.src_plane_pitch = j.src_plane_pitch;
+    a.dst_plane_pitch = j.dst_plane_pitch;
+    return a;
+}
+
+int check_pool(const PoolJob& j, bool with_dst) {
+    if (j.n < 1) return fail(BICOS_E_ARG, "pool: need at least one image");
+    if (j.depth != 1 && j.depth != 2)
+        return fail(BICOS_E_ARG, "pool: depth must be 1 (u8) or 2 (u16)");
+    if (j.scale < bicos_hip::POOL_MIN_SCALE || j.scale > bicos_hip::POOL_MAX_SCALE)
+        return fail(BICOS_E_ARG, "pool: scale must lie in 2 .. 8");
+    if (j.rows < j.scale || j.cols < j.scale)
+        return fail(BICOS_E_ARG, "pool: the image is smaller than scale x scale");
+    const int prows = j.rows / j.scale, pcols = j.cols / j.scale;
+    if (j.src_row_pitch < (size_t)j.cols || j.src_plane_pitch < (size_t)j.cols)
+        return fail(BICOS_E_ARG, "pool: a source pitch is smaller than a row");
+    if (with_dst && (j.dst_row_pitch < (size_t)pcols || j.dst_plane_pitch < (size_t)pcols))
+        return fail(BICOS_E_ARG, "pool: an output pitch is smaller than a row");
+    if (!j.src) return fail(BICOS_E_ARG, "pool: null source stack");
+    if (with_dst && !j.dst) return fail(BICOS_E_ARG, "pool: null output stack");
+    if (((uintptr_t)j.src | (with_dst ? (uintptr_t)j.dst : 0)) % (uintptr_t)j.depth)
+        return fail(BICOS_E_ARG, "pool: a u16 stack's base is not 2-byte aligned");
+    // 32-bit offsets within a plane
+    const unsigned long long lim = 0xFFFFFFFFull;
+    const unsigned long long src_plane =
+        (unsigned long long)(j.rows - 1) * j.src_row_pitch + (unsigned long long)j.cols;
+    const unsigned long long dst_plane =
+        with_dst ? (unsigned long long)(prows - 1) * j.dst_row_pitch + (unsigned long long)pcols : 0;
+    if (src_plane > lim || dst_plane > lim)
+        return fail(BICOS_E_ARG, "pool: a plane spans more than 2^32 - 1 elements");
+    if (bicos_hip::pool_blocks(pool_args(j)) > (uint64_t)INT32_MAX)
+        return fail(BICOS_E_ARG, "pool: more tiles than one launch holds");
+    if (with_dst) {
+        const unsigned long long d = (unsigned long long)j.depth;
+        const unsigned long long a = (uintptr_t)j.src, b = (uintptr_t)j.dst;
+        const unsigned long long a_bytes = ((unsigned long long)(j.n - 1) * j.src_plane_pitch + src_plane) * d;
+        const unsigned long long b_bytes = ((unsigned long long)(j.n - 1) * j.dst_plane_pitch + dst_plane) * d;
+        if (a < b + b_bytes && b < a + a_bytes)
+            return fail(BICOS_E_ARG, "pool: the output overlaps the source");
+    }
+    return BICOS_OK;
+}
+
+int pool_device(const PoolJob& j, hipStream_t st) {
+    return check_hip(bicos_hip::launch_pool(pool_args(j), j.depth, j.scale, st), "pool launch");
+}
+
+// ------------------------------------------------------------- pyramid match
+
+void pyramid_window(int min_disparity, int max_disparity, int scale, int* lo, int* hi) {
+    const int64_t s = scale, a = min_disparity, b = max_disparity;
+    // floor and ceil of the quotients (C++ division truncates toward zero)
+    *lo = (int)(a / s - (a % s < 0 ? 1 : 0));
+    *hi = (int)(b / s + (b % s > 0 ? 1 : 0));
+}
+
+int check_pyramid(const void* s0, const void* s1, int n, int rows, int cols, size_t row_pitch,
+                  size_t plane_pitch, int depth, const BicosConfig& cfg, bool has_nxcorr,
+                  const DispRange& range, const PyramidJob& j, const void* disp) {
+    if (int rc0 = check_range(range.min, range.max)) return rc0;
+    for (const void* s : {s0, s1}) {
+        const PoolJob pj{s, n, rows, cols, row_pitch, plane_pitch, depth, j.scale, nullptr, 0, 0};
+        if (int rc0 = check_pool(pj, false)) return rc0;
+    }
+    GuideJob gj{};
+    gj.scale = j.scale;
+    gj.radius = j.radius;
+    gj.spread = j.spread;
+    gj.fallback_lo = j.fallback_lo;
+    gj.fallback_hi = j.fallback_hi;
+    gj.flags = BICOS_GUIDE_F32_SENTINEL;
+    if (int rc0 = check_guide_params(gj)) return rc0;
+    MatchShape shape;
+    if (int rc0 = check_match(s0, s1, n, rows, cols, row_pitch, plane_pitch, depth, cfg, has_nxcorr,
+                              disp, false, &shape))
+        return rc0;
+    if ((int64_t)rows * cols > INT32_MAX)
+        return fail(BICOS_E_ARG, "guide: rows * cols exceeds int32");
+    if ((uintptr_t)j.guide & 3u)
+        return fail(BICOS_E_ARG, "guide: the guide's base is not 4-byte aligned");
+    return BICOS_OK;
+}
+
+int match_pyramid_device(bicos_engine* e, const void* s0, const void* s1, int n, int rows,
+                         int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                         const BicosConfig& cfg, bool has_nxcorr, float threshold,
+                         const DispRange& range, const PyramidJob& j, void* disp, void* corr,
+                         hipStream_t st) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    const int prows = rows / j.scale, pcols = cols / j.scale;
+    const size_t ppix = (size_t)prows * pcols, pix = (size_t)rows * cols;
+    const int coarse_type = has_nxcorr ? BICOS_CV_32F : BICOS_CV_16S;
+    // pooled stack 0 | pooled stack 1 | the coarse map | the guide, the last two only where the
+    // caller does not keep them. Held over all four steps; the inner matches lease ws on the
+    // same stream, which only re-records ws_ready.
+    void *q0 = nullptr, *q1 = nullptr, *coarse = nullptr;
+    int16_t* guide = nullptr;
+    Lease pyr(e, e->pyr, e->pyr_bytes, st);
+    auto carve = [&] {
+        q0 = pyr.take(ppix * n * depth);
+        q1 = pyr.take(ppix * n * depth);
+        coarse = j.coarse ? j.coarse : pyr.take(ppix * (has_nxcorr ? 4 : 2));
+        guide = j.guide ? j.guide : pyr.take<int16_t>(2 * pix);
+    };
+    carve();
+    int rc = pyr.acquire();
+    if (rc) return rc;
+    carve();
+
+    // 1. both stacks pooled into dense prows x pcols planes
+    PoolJob pj{s0, n, rows, cols, row_pitch, plane_pitch, depth, j.scale, q0, (size_t)pcols, ppix};
+    rc = pool_device(pj, st);
+    pj.src = s1;
+    pj.dst = q1;
+    if (!rc) rc = pool_device(pj, st);
+    if (rc) return rc;
+    // 2. the coarse match over the scaled window, without subpixel interpolation
+    BicosConfig coarse_cfg = cfg;
+    coarse_cfg.subpixel_step = -1;
+    DispRange coarse_range{0, 0};
+    pyramid_window(range.min, range.max, j.scale, &coarse_range.min, &coarse_range.max);
+    rc = match_device(e, q0, q1, n, prows, pcols, (size_t)pcols, ppix, depth, coarse_cfg,
+                      has_nxcorr, threshold, coarse, nullptr, st, false, nullptr, nullptr,
+                      &coarse_range);
+    if (rc) return rc;
+    // 3. its map as the prior of a full-size guide
+    const GuideJob gj{coarse, coarse_type, prows, pcols, rows, cols, j.scale, j.radius, j.spread,
+                      j.fallback_lo, j.fallback_hi, BICOS_GUIDE_F32_SENTINEL, guide, (size_t)cols,
+                      j.counts};
+    rc = guide_device(gj, st);
+    if (rc) return rc;
+    // 4. the guided match of the full stacks
+    const DispRange fine{range.min, range.max, guide, (size_t)cols};
+    rc = match_device(e, s0, s1, n, rows, cols, row_pitch, plane_pitch, depth, cfg, has_nxcorr,
+                      threshold, disp, corr, st, false, nullptr, nullptr, &fine);
+    // match_device's last act on `st` is the release of its ws lease (engine.hpp): ws_ready
+    // stands behind its last launch, the last use of the guide, so a second record would only
+    // put one more marker into the queue. BICOS_PYRAMID_SINGLE_RECORD=0 records it all the same
+    // (A/B, read per call: tools/pool_bench.py measures both in one process).
+    if (!rc && env_on("BICOS_PYRAMID_SINGLE_RECORD")) pyr.dismiss();
+    return rc;
 }
 
 // ------------------------------------------------------------- rectification

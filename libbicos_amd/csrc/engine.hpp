@@ -9,13 +9,15 @@
 //               speckle_device (the speckle filter of a disparity map); rectify_device and
 //               rectify_maps_device (raw stacks -> rectified stacks); median_device (the
 //               median filter of a disparity map); guide_device (a prior disparity map ->
-//               per-pixel search windows)
+//               per-pixel search windows); pool_device (a stack pooled by an integer factor);
+//               match_pyramid_device (pool, coarse ranged match, guide, guided match)
 //   host.cpp    the banded host-buffer pipeline (HostPool, match_host); reproject_host;
-//               speckle_host; rectify_host, rectify_maps_host; median_host; guide_host
+//               speckle_host; rectify_host, rectify_maps_host; median_host; guide_host;
+//               pool_host; match_pyramid_host
 //   entries.cpp the bicos_* extern "C" entries (bicos_c.h) but the multi-GPU ones
 //   multi.cpp   bicos_match_host_multi, bicos_match_bands_device
 //   cxxapi.cpp  namespace BICOS (HipImage, match, reproject, filter_speckles, median_filter,
-//               guide_from_disparity)
+//               guide_from_disparity, pool_stack, match_pyramid)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -80,6 +82,11 @@ struct bicos_engine {
     // host-API staging (device): band-major stacks + dense output maps
     void* stage = nullptr;
     size_t stage_bytes = 0;
+    // the pyramid match's own buffers (match_pyramid_device): the pooled stacks, and the coarse
+    // map and the guide where the caller keeps neither. Beside ws, not inside it: the inner
+    // matches lease ws themselves. Ordered by ws_ready like the other two.
+    void* pyr = nullptr;
+    size_t pyr_bytes = 0;
     // host-buffer pipeline (match_host): copy stream, pinned band slots, band events
     hipStream_t copy_stream = nullptr;
     bicos_impl::PinnedBuf pinned;  // K input band slots
@@ -136,7 +143,7 @@ int reserve(void*& buf, size_t& have, size_t bytes, int device, hipStream_t st, 
 constexpr size_t ALIGN = 256;
 inline size_t align_up(size_t x) { return (x + ALIGN - 1) / ALIGN * ALIGN; }
 
-// One use of an engine buffer (ws or stage) on one stream, and the rule that keeps two
+// One use of an engine buffer (ws, stage or pyr) on one stream, and the rule that keeps two
 // streams from racing on it: acquire() reserves the bytes, makes `st` wait for ws_ready
 // (every earlier use, on any stream), and from then on release() -- at the latest the
 // destructor, on every exit path -- records ws_ready on `st`.
@@ -159,6 +166,9 @@ class Lease {
     }
     int acquire();
     void release();
+    // release() without the record, for a holder whose last step on `st` was another lease's
+    // release(): ws_ready already stands behind every use of this buffer
+    void dismiss() { held_ = false; }
     char* base() const { return (char*)buf_; }
     size_t needed() const { return off_; }  // bytes taken so far
 
@@ -175,7 +185,7 @@ class Lease {
 int grow_pinned(PinnedBuf& b, size_t bytes, const char* what);  // failure: null, 0 bytes
 int grow_events(std::vector<hipEvent_t>& v, int count);
 int ensure_stream(hipStream_t& s);  // a non-blocking stream, created on first use
-void free_resources(bicos_engine* e);  // streams, events, pinned buffers; not ws / stage
+void free_resources(bicos_engine* e);  // streams, events, pinned buffers; not ws / stage / pyr
 
 int descriptor_words(int n, int mode);
 
@@ -244,11 +254,27 @@ bicos_hip::AgreeArgs agree_args(const int16_t* raw, const void* s0, const void* 
 // already computed -- the match then runs from its search on (bicos_search_agree_device).
 // range: the search's disparity window (nullptr: the whole row) -- the windowed matrix-core
 // search (search_range.hip), none of the fused or compacted plans.
+// Postcondition that match_pyramid_device relies on: a call that returns BICOS_OK for a
+// non-empty image has leased ws, and the last thing it put on `st` is that lease's record of
+// ws_ready, behind all its launches.
 int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int rows, int cols,
                  size_t row_pitch, size_t plane_pitch, int depth, const BicosConfig& cfg,
                  bool has_nxcorr, float threshold, void* disp, void* corr, hipStream_t st,
                  bool disp_i16 = false, const uint32_t* ext_d0 = nullptr,
                  const uint32_t* ext_d1 = nullptr, const DispRange* range = nullptr);
+
+// What match_device refuses, in its order, and what it derives on the way: BICOS_E_ARG /
+// BICOS_E_BITS (with a message); no HIP call. An empty image (rows or cols 0) passes without
+// its buffers and pitches being looked at.
+struct MatchShape {
+    int mode, words;
+    bool has_step;
+    int nsteps;
+    uint32_t span;
+};
+int check_match(const void* s0, const void* s1, int n, int rows, int cols, size_t row_pitch,
+                size_t plane_pitch, int depth, const BicosConfig& cfg, bool has_nxcorr,
+                const void* disp, bool disp_i16, MatchShape* out);
 
 // What match_device runs after the transform (bicos_match_plan: bits()): the search's part
 // and the agree's (BICOS_PLAN_AGREE_IN_SEARCH, BICOS_PLAN_CONSISTENCY_IN_AGREE)
@@ -298,8 +324,62 @@ struct GuideJob {
     uint32_t* counts;
 };
 int check_guide_job(const GuideJob& j);  // BICOS_E_ARG (with a message); no HIP call
+// ... its part that looks at scale, radius, spread, the fallback pair and the flags alone
+int check_guide_params(const GuideJob& j);
 int guide_device(const GuideJob& j, hipStream_t st);
 int guide_host(bicos_engine* e, const GuideJob& j);
+
+// One pooling of a stack (bicos_c.h "stack pooling"): the arguments of bicos_pool_device, the
+// pointers in device memory, the pitches in elements.
+struct PoolJob {
+    const void* src;
+    int n, rows, cols;
+    size_t src_row_pitch, src_plane_pitch;
+    int depth, scale;
+    void* dst;
+    size_t dst_row_pitch, dst_plane_pitch;
+};
+// BICOS_E_ARG (with a message) for what the entries refuse; no HIP call. with_dst = false: the
+// source side alone (the pyramid match, whose pooled stacks are its own).
+int check_pool(const PoolJob& j, bool with_dst = true);
+// The one launch on `st` (validated arguments); no workspace, no engine.
+int pool_device(const PoolJob& j, hipStream_t st);
+// Host buffers: n plane pointers in and out with their steps in bytes, staged through the
+// engine, the same launch on its own stream. Synchronous.
+int pool_host(bicos_engine* e, const void* const* src, size_t src_step, void* const* dst,
+              size_t dst_step, const PoolJob& j);
+
+// The pyramid match (bicos_c.h "pyramid match"): what it takes besides a ranged match's
+// arguments. coarse, guide and counts are optional outputs, in device memory for
+// match_pyramid_device and in host memory for match_pyramid_host.
+struct PyramidJob {
+    int scale, radius, spread;
+    int fallback_lo, fallback_hi;
+    void* coarse;
+    int16_t* guide;
+    uint32_t* counts;
+};
+// The coarse match's window: [floor(min / scale), ceil(max / scale)]
+void pyramid_window(int min_disparity, int max_disparity, int scale, int* lo, int* hi);
+// BICOS_E_ARG / BICOS_E_BITS (with a message) for what any of the four steps would refuse; no
+// HIP call. s0 / s1: the stacks' bases, device memory or (host entry) any non-null placeholder.
+int check_pyramid(const void* s0, const void* s1, int n, int rows, int cols, size_t row_pitch,
+                  size_t plane_pitch, int depth, const BicosConfig& cfg, bool has_nxcorr,
+                  const DispRange& range, const PyramidJob& j, const void* disp);
+// pool both stacks, match them over the coarse window, build the guide, run the guided match:
+// enqueued on `st`, the pooled stacks (and the coarse map / the guide the caller does not keep)
+// in e->pyr. Validated arguments (check_pyramid); the caller holds e->lock.
+int match_pyramid_device(bicos_engine* e, const void* s0, const void* s1, int n, int rows,
+                         int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                         const BicosConfig& cfg, bool has_nxcorr, float threshold,
+                         const DispRange& range, const PyramidJob& j, void* disp, void* corr,
+                         hipStream_t st);
+// Host buffers: each stack uploaded once, whole, into the engine's staging; the device pyramid
+// on the engine's own stream; the maps and the optional outputs downloaded. Synchronous.
+int match_pyramid_host(bicos_engine* e, const void* const* p0, const void* const* p1, size_t step,
+                       int n, int rows, int cols, int depth, const BicosConfig& cfg,
+                       bool has_nxcorr, float threshold, const DispRange& range,
+                       const PyramidJob& j, void* disp, void* corr);
 
 // One reprojection (bicos_c.h "reprojection"): the arguments of bicos_reproject_device /
 // bicos_reproject_host, the pointers all in device or all in host memory.

@@ -5,6 +5,7 @@
 #include "speckle.hpp"
 #include "median.hpp"
 #include "guide.hpp"
+#include "pool.hpp"
 
 #include <cmath>
 #include <vector>
@@ -163,6 +164,7 @@ void bicos_engine_destroy(bicos_engine* e) {
     // workspaces come from the stream-ordered allocator (reserve)
     if (e->ws) (void)hipFreeAsync(e->ws, e->own_stream);
     if (e->stage) (void)hipFreeAsync(e->stage, e->own_stream);
+    if (e->pyr) (void)hipFreeAsync(e->pyr, e->own_stream);
     (void)hipStreamSynchronize(e->own_stream);
     free_resources(e);
     (void)hipSetDevice(cur);
@@ -610,6 +612,138 @@ int bicos_median_tile(int* rows, int* cols) {
     if (rows) *rows = bicos_hip::MEDIAN_TILE_ROWS;
     if (cols) *cols = bicos_hip::MEDIAN_TILE_COLS;
     return BICOS_OK;
+}
+
+int bicos_pool_device(bicos_engine* e, const void* src, int n, int rows, int cols,
+                      size_t src_row_pitch, size_t src_plane_pitch, int depth, int scale,
+                      void* dst, size_t dst_row_pitch, size_t dst_plane_pitch, void* stream) {
+    (void)e;  // no workspace: one launch on the caller's stream
+    const PoolJob job{src, n, rows, cols, src_row_pitch, src_plane_pitch, depth, scale,
+                      dst, dst_row_pitch, dst_plane_pitch};
+    if (int rc0 = check_pool(job)) return rc0;
+    return guarded([&]() -> int { return pool_device(job, (hipStream_t)stream); });
+}
+
+int bicos_pool_host(bicos_engine* e, const void* const* src, int n, int rows, int cols,
+                    size_t src_step, int depth, int scale, void* const* dst, size_t dst_step) {
+    if (n < 1) return fail(BICOS_E_ARG, "pool: need at least one image");
+    if (depth != 1 && depth != 2) return fail(BICOS_E_ARG, "pool: depth must be 1 (u8) or 2 (u16)");
+    if (!src || !dst) return fail(BICOS_E_ARG, "pool: null image list");
+    if (src_step % (size_t)depth || dst_step % (size_t)depth)
+        return fail(BICOS_E_ARG, "pool: a step is not a multiple of the depth");
+    const int pcols = scale >= 1 && cols > 0 ? cols / scale : 0;
+    const size_t sstep = src_step ? src_step : (size_t)(cols > 0 ? cols : 0) * depth;
+    const size_t dstep = dst_step ? dst_step : (size_t)pcols * depth;
+    for (int t = 0; t < n; ++t) {
+        // every image through the device entry's checks but the overlap (both sides are staged),
+        // as a one-plane stack of its step
+        const PoolJob one{src[t], 1, rows, cols, sstep / depth, sstep / depth, depth, scale,
+                          nullptr, 0, 0};
+        if (int rc0 = check_pool(one, false)) return rc0;
+        if (dstep / depth < (size_t)pcols)
+            return fail(BICOS_E_ARG, "pool: an output pitch is smaller than a row");
+        if (!dst[t]) return fail(BICOS_E_ARG, "pool: null output stack");
+    }
+    const PoolJob job{src[0], n, rows, cols, 0, 0, depth, scale, dst[0], 0, 0};
+    return guarded([&]() -> int {
+        if (!e) {
+            int dev = 0;
+            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
+            if (rc) return rc;
+            e = default_engine(dev);
+            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        }
+        std::lock_guard<std::mutex> g(e->lock);
+        return pool_host(e, src, sstep, dst, dstep, job);
+    });
+}
+
+int bicos_pool_tile(int* rows, int* cols) {
+    if (rows) *rows = bicos_hip::POOL_TILE_ROWS;
+    if (cols) *cols = bicos_hip::POOL_TILE_COLS;
+    return BICOS_OK;
+}
+
+int bicos_pool_kernel(const void* src, size_t src_row_pitch, size_t src_plane_pitch, int depth,
+                      const void* dst, size_t dst_row_pitch, size_t dst_plane_pitch) {
+    if (depth != 1 && depth != 2) return fail(BICOS_E_ARG, "pool: depth must be 1 (u8) or 2 (u16)");
+    bicos_hip::PoolArgs a{};
+    a.src = src;
+    a.dst = (void*)dst;
+    a.src_row_pitch = (uint32_t)src_row_pitch;
+    a.dst_row_pitch = (uint32_t)dst_row_pitch;
+    a.src_plane_pitch = src_plane_pitch;
+    a.dst_plane_pitch = dst_plane_pitch;
+    return (bicos_hip::pool_wide(a, depth) ? 1 : 0) | (bicos_hip::pool_dst_vector(a, depth) ? 2 : 0);
+}
+
+int bicos_pyramid_window(int min_disparity, int max_disparity, int scale, int* lo, int* hi) {
+    if (scale < bicos_hip::POOL_MIN_SCALE || scale > bicos_hip::POOL_MAX_SCALE)
+        return fail(BICOS_E_ARG, "pool: scale must lie in 2 .. 8");
+    if (!lo || !hi) return fail(BICOS_E_ARG, "null out");
+    pyramid_window(min_disparity, max_disparity, scale, lo, hi);
+    return BICOS_OK;
+}
+
+int bicos_match_device_pyramid(bicos_engine* e, const void* stack0, const void* stack1, int n,
+                               int rows, int cols, size_t row_pitch, size_t plane_pitch, int depth,
+                               const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                               int max_disparity, int scale, int radius, int spread,
+                               int fallback_lo, int fallback_hi, void* disparity, void* corrmap,
+                               void* coarse, int16_t* guide, uint32_t* counts, void* stream) {
+    if (!cfg) return fail(BICOS_E_ARG, "null config");
+    const DispRange range{min_disparity, max_disparity};
+    const PyramidJob job{scale, radius, spread, fallback_lo, fallback_hi, coarse, guide, counts};
+    if (int rc0 = check_pyramid(stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth, *cfg,
+                                has_nxcorr != 0, range, job, disparity))
+        return rc0;
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    return guarded([&]() -> int {
+        std::lock_guard<std::mutex> g(e->lock);
+        return match_pyramid_device(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch,
+                                    depth, *cfg, has_nxcorr != 0, nxc_threshold(*cfg), range, job,
+                                    disparity, corrmap, (hipStream_t)stream);
+    });
+}
+
+int bicos_match_host_pyramid(bicos_engine* e, const void* const* stack0, const void* const* stack1,
+                             int n, int rows, int cols, size_t step, int depth,
+                             const BicosConfig* cfg, int has_nxcorr, int min_disparity,
+                             int max_disparity, int scale, int radius, int spread, int fallback_lo,
+                             int fallback_hi, void* disparity, void* corrmap, void* coarse,
+                             int16_t* guide, uint32_t counts[2]) {
+    if (!cfg) return fail(BICOS_E_ARG, "null config");
+    if (n < 1) return fail(BICOS_E_ARG, "pool: need at least one image");
+    if (depth != 1 && depth != 2)
+        return fail(BICOS_E_ARG, "bad input depths, only CV_8UC1 and CV_16UC1 are supported");
+    if (!stack0 || !stack1) return fail(BICOS_E_ARG, "null buffer");
+    if (step % (size_t)depth) return fail(BICOS_E_ARG, "image step is not a multiple of the depth");
+    const size_t row = step ? step : (size_t)(cols > 0 ? cols : 0) * depth;
+    const DispRange range{min_disparity, max_disparity};
+    const PyramidJob job{scale, radius, spread, fallback_lo, fallback_hi, coarse, guide, counts};
+    for (int t = 0; t < n; ++t) {
+        if (!stack0[t] || !stack1[t]) return fail(BICOS_E_ARG, "null image");
+        if (row < (size_t)(cols > 0 ? cols : 0) * depth)
+            return fail(BICOS_E_ARG, "image step smaller than a row");
+    }
+    // the device entry's checks on the stacks as they will lie in the staging: dense
+    if (int rc0 = check_pyramid(stack0[0], stack1[0], n, rows, cols, (size_t)(cols > 0 ? cols : 0),
+                                (size_t)(rows > 0 ? rows : 0) * (size_t)(cols > 0 ? cols : 0),
+                                depth, *cfg, has_nxcorr != 0, range, job, disparity))
+        return rc0;
+    return guarded([&]() -> int {
+        if (!e) {
+            int dev = 0;
+            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
+            if (rc) return rc;
+            e = default_engine(dev);
+            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        }
+        std::lock_guard<std::mutex> g(e->lock);
+        return match_pyramid_host(e, stack0, stack1, row, n, rows, cols, depth, *cfg,
+                                  has_nxcorr != 0, nxc_threshold(*cfg), range, job, disparity,
+                                  corrmap);
+    });
 }
 
 const char* bicos_build_info(void) {

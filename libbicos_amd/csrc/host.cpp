@@ -634,4 +634,107 @@ int guide_host(bicos_engine* e, const GuideJob& j) {
     return rc ? rc : rc2;
 }
 
+// --------------------------------------------------------------- stack pooling
+
+int pool_host(bicos_engine* e, const void* const* src, size_t src_step, void* const* dst,
+              size_t dst_step, const PoolJob& j) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    hipStream_t st = e->own_stream;
+    const size_t d = (size_t)j.depth;
+    const int prows = j.rows / j.scale, pcols = j.cols / j.scale;
+    // only what the launch reads is uploaded: the remainder rows and columns stay on the host
+    const size_t src_row = (size_t)pcols * j.scale * d, dst_row = (size_t)pcols * d;
+    const size_t src_plane = src_row * prows * j.scale, dst_plane = dst_row * prows;
+    PoolJob dj = j;  // the same job on dense staged device buffers
+    dj.rows = prows * j.scale;
+    dj.cols = pcols * j.scale;
+    dj.src_row_pitch = (size_t)dj.cols;
+    dj.src_plane_pitch = (size_t)dj.cols * dj.rows;
+    dj.dst_row_pitch = (size_t)pcols;
+    dj.dst_plane_pitch = (size_t)pcols * prows;
+    Lease stage(e, e->stage, e->stage_bytes, st);
+    char *s = nullptr, *o = nullptr;
+    auto carve = [&] {
+        s = stage.take(src_plane * j.n);
+        o = stage.take(dst_plane * j.n);
+    };
+    carve();
+    int rc = stage.acquire();
+    if (rc) return rc;
+    carve();
+    dj.src = s;
+    dj.dst = o;
+    for (int t = 0; t < j.n && !rc; ++t)
+        rc = check_hip(hipMemcpy2DAsync(s + t * src_plane, src_row, src[t], src_step, src_row,
+                                        (size_t)dj.rows, hipMemcpyHostToDevice, st),
+                       "stack upload");
+    if (!rc) rc = pool_device(dj, st);
+    for (int t = 0; t < j.n && !rc; ++t)
+        rc = check_hip(hipMemcpy2DAsync(dst[t], dst_step, o + t * dst_plane, dst_row, dst_row,
+                                        (size_t)prows, hipMemcpyDeviceToHost, st),
+                       "stack download");
+    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    return rc ? rc : rc2;
+}
+
+// --------------------------------------------------------------- pyramid match
+
+int match_pyramid_host(bicos_engine* e, const void* const* p0, const void* const* p1, size_t step,
+                       int n, int rows, int cols, int depth, const BicosConfig& cfg,
+                       bool has_nxcorr, float threshold, const DispRange& range,
+                       const PyramidJob& j, void* disp, void* corr) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    hipStream_t st = e->own_stream;
+    const size_t row = (size_t)cols * depth, plane = row * rows;
+    const size_t pix = (size_t)rows * cols;
+    const size_t ppix = (size_t)(rows / j.scale) * (size_t)(cols / j.scale);
+    const bool f32 = has_nxcorr;  // bicos_output_type: of the fine map and of the coarse one
+    const size_t esz = f32 ? 4 : 2;
+    const size_t csz = cfg.precision != 0 ? sizeof(double) : sizeof(float);  // of the corrmap
+    PyramidJob dj = j;  // the same job on staged device buffers
+    char *s0 = nullptr, *s1 = nullptr;
+    void *d_disp = nullptr, *d_corr = nullptr;
+    Lease stage(e, e->stage, e->stage_bytes, st);
+    auto carve = [&] {
+        s0 = stage.take(plane * n);
+        s1 = stage.take(plane * n);
+        d_disp = stage.take(pix * esz);
+        d_corr = corr && has_nxcorr ? stage.take(pix * csz) : nullptr;
+        dj.coarse = j.coarse ? stage.take(ppix * esz) : nullptr;
+        dj.guide = j.guide ? stage.take<int16_t>(2 * pix) : nullptr;
+        dj.counts = j.counts ? stage.take<uint32_t>(2) : nullptr;
+    };
+    carve();
+    int rc = stage.acquire();
+    if (rc) return rc;
+    carve();
+    for (int t = 0; t < n && !rc; ++t) {
+        rc = check_hip(hipMemcpy2DAsync(s0 + t * plane, row, p0[t], step, row, (size_t)rows,
+                                        hipMemcpyHostToDevice, st), "stack upload");
+        if (!rc)
+            rc = check_hip(hipMemcpy2DAsync(s1 + t * plane, row, p1[t], step, row, (size_t)rows,
+                                            hipMemcpyHostToDevice, st), "stack upload");
+    }
+    if (!rc)
+        rc = match_pyramid_device(e, s0, s1, n, rows, cols, (size_t)cols, pix, depth, cfg,
+                                  has_nxcorr, threshold, range, dj, d_disp, d_corr, st);
+    if (!rc)
+        rc = check_hip(hipMemcpyAsync(disp, d_disp, pix * esz, hipMemcpyDeviceToHost, st),
+                       "disparity download");
+    if (!rc && d_corr)
+        rc = check_hip(hipMemcpyAsync(corr, d_corr, pix * csz, hipMemcpyDeviceToHost, st),
+                       "corrmap download");
+    if (!rc && j.coarse)
+        rc = check_hip(hipMemcpyAsync(j.coarse, dj.coarse, ppix * esz, hipMemcpyDeviceToHost, st),
+                       "coarse map download");
+    if (!rc && j.guide)
+        rc = check_hip(hipMemcpyAsync(j.guide, dj.guide, pix * 4, hipMemcpyDeviceToHost, st),
+                       "guide download");
+    if (!rc && j.counts)
+        rc = check_hip(hipMemcpyAsync(j.counts, dj.counts, 2 * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, st), "counts download");
+    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    return rc ? rc : rc2;
+}
+
 }  // namespace bicos_impl

@@ -617,6 +617,120 @@ class Engine:
         _lib.check(rc, "bicos_rectify_device")
         return out if val is None else (out, val)
 
+    # ----------------------------------------------------------- stack pooling
+    def pool(self, stack: torch.Tensor, scale: int, *, out: Optional[torch.Tensor] = None,
+             stream=None) -> torch.Tensor:
+        """bicos_pool_device: the planar stack [n, rows, cols] (uint8, or 16 bits in an int16 /
+        uint16 tensor) pooled by `scale` in 2..8 to [n, rows // scale, cols // scale] of the same
+        dtype: each output pixel is (sum of its scale x scale block + scale*scale // 2) //
+        (scale*scale), the mean rounded half up in integers (include/bicos_c.h "stack pooling").
+        The rows % scale last rows and cols % scale last columns are not read. Plane and row
+        strides of `stack` and `out` may be anything (the last dimension contiguous), as for
+        match(); the result can go straight into match(). Returns the stack -- `out` if given.
+
+        The call NEVER synchronises: one launch on `stream` (default: torch's current stream)."""
+        sc = _lib.pool_scale(scale)
+        n, rows, cols, rp, pp = _check_stack(stack)
+        dev = stack.device
+        if n < 1:
+            raise ValueError("pool needs a non-empty stack")
+        prows, pcols = _lib.pool_shape(rows, cols, sc)
+        if out is None:
+            out = torch.empty((n, prows, pcols), dtype=stack.dtype, device=dev)
+        if out.device != dev or out.dtype != stack.dtype or tuple(out.shape) != (n, prows, pcols) \
+                or out.stride(2) != 1:
+            raise ValueError("out must be a %s [%d, %d, %d] tensor on %s with contiguous rows"
+                             % (stack.dtype, n, prows, pcols, dev))
+        rc = self._L.bicos_pool_device(
+            self._h, stack.data_ptr(), n, rows, cols,
+            # (the stride of a dimension of size one means nothing)
+            rp if rows > 1 else cols, pp if n > 1 else cols, _depth(stack), sc, out.data_ptr(),
+            out.stride(1) if prows > 1 else pcols, out.stride(0) if n > 1 else pcols,
+            _stream(dev, stream))
+        _lib.check(rc, "bicos_pool_device")
+        return out
+
+    def pool_kernel(self, stack: torch.Tensor, out: torch.Tensor) -> int:
+        """bicos_pool_kernel: bit 0 set if pool(stack, out=out) runs the dword-load kernel, clear
+        if the per-element kernel (the source's alignment decides); bit 1 set if `out` is aligned
+        for the dword-load kernel's vector stores. The results are the same."""
+        n, rows, cols, rp, pp = _check_stack(stack)
+        return self._L.bicos_pool_kernel(
+            stack.data_ptr(), rp if rows > 1 else cols, pp if n > 1 else cols, _depth(stack),
+            out.data_ptr(), out.stride(1) if out.shape[1] > 1 else out.shape[2],
+            out.stride(0) if n > 1 else out.shape[2])
+
+    # ------------------------------------------------------------ pyramid match
+    def match_pyramid(self, stack0: torch.Tensor, stack1: torch.Tensor,
+                      cfg: Optional[MatchConfig] = None, *, scale: int = 2, radius: int = 2,
+                      spread: int = 1, fallback: Optional[Tuple[int, int]] = None,
+                      return_guide=False, return_coarse=False,
+                      counts: Optional[torch.Tensor] = None, want_corrmap: bool = True,
+                      out: Optional[torch.Tensor] = None, corrmap: Optional[torch.Tensor] = None,
+                      stream=None):
+        """bicos_match_device_pyramid: the coarse-to-fine match in one call, for windows too
+        wide for one search. Byte for byte pool(stack, scale) of both stacks, match() of the
+        pooled stacks without a subpixel step over cfg.disparity_range divided by `scale`
+        (floor, ceil), guide_from_disparity(coarse, radius, spread, scale, fallback,
+        shape=(rows, cols)) and match(guide=) of the full stacks (include/bicos_c.h "pyramid
+        match"). cfg.disparity_range is required. fallback None: the global window, clamped to
+        +-32767; a pair with lo > hi: do not search where the coarse map knows nothing.
+
+        Returns (disparity, corrmap), followed by the guide (int16 [rows, cols, 2]) with
+        return_guide and by the coarse map ([rows // scale, cols // scale], float32 with the
+        NXC stage, else int16) with return_coarse; either may be True or a tensor to fill.
+        `counts`, an int32 [2] tensor, receives the guide's {from_prior, fallback}.
+
+        The call NEVER synchronises: everything is enqueued on `stream`."""
+        cfg = cfg or MatchConfig()
+        rng, sc, r, sp, flo, fhi = _lib.pyramid_params(cfg.disparity_range, scale, radius,
+                                                       spread, fallback)
+        n, rows, cols, rp, pp = _check_stack(stack0)
+        if tuple(stack1.shape) != (n, rows, cols) or stack1.stride() != stack0.stride() or \
+                stack1.dtype != stack0.dtype:
+            raise ValueError("stack1 must match stack0 in shape, strides and dtype")
+        prows, pcols = _lib.pool_shape(rows, cols, sc)
+        c, has_nxcorr = cfg.to_c()
+        dev = stack0.device
+        disp_dtype = torch.float32 if has_nxcorr else torch.int16
+        corr_dtype = torch.float64 if cfg.precision else torch.float32
+        if out is None:
+            out = torch.empty((rows, cols), dtype=disp_dtype, device=dev)
+        _check_out(out, "out", (rows, cols), (disp_dtype,), dev)
+        if has_nxcorr and want_corrmap and corrmap is None:
+            corrmap = torch.empty((rows, cols), device=dev, dtype=corr_dtype)
+        if not (has_nxcorr and want_corrmap):
+            corrmap = None
+        if corrmap is not None:
+            _check_out(corrmap, "corrmap", (rows, cols), (corr_dtype,), dev)
+        guide = coarse = None
+        if return_guide is True:
+            guide = torch.empty((rows, cols, 2), dtype=torch.int16, device=dev)
+        elif return_guide is not False and return_guide is not None:
+            guide = return_guide
+            _check_out(guide, "guide", (rows, cols, 2), (torch.int16,), dev)
+        if return_coarse is True:
+            coarse = torch.empty((prows, pcols), dtype=disp_dtype, device=dev)
+        elif return_coarse is not False and return_coarse is not None:
+            coarse = return_coarse
+            _check_out(coarse, "coarse", (prows, pcols), (disp_dtype,), dev)
+        if counts is not None:
+            _check_out(counts, "counts", (2,), (torch.int32,), dev)
+        rc = self._L.bicos_match_device_pyramid(
+            self._h, stack0.data_ptr(), stack1.data_ptr(), n, rows, cols, rp, pp, _depth(stack0),
+            ctypes.byref(c), has_nxcorr, rng[0], rng[1], sc, r, sp, flo, fhi, out.data_ptr(),
+            corrmap.data_ptr() if corrmap is not None else None,
+            coarse.data_ptr() if coarse is not None else None,
+            guide.data_ptr() if guide is not None else None,
+            counts.data_ptr() if counts is not None else None, _stream(dev, stream))
+        _lib.check(rc, "bicos_match_device_pyramid")
+        res = (out, corrmap)
+        if guide is not None:
+            res += (guide,)
+        if coarse is not None:
+            res += (coarse,)
+        return res
+
     # ----------------------------------------------------------------- stages
     def transform(self, stack: torch.Tensor, mode: int = 0, words: Optional[int] = None,
                   out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:

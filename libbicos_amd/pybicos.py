@@ -437,6 +437,78 @@ def guide_from_disparity(prior, radius, spread=0, scale=1, fallback=None, shape=
     return out, dict(from_prior=counts[0], fallback=counts[1])
 
 
+def _host_stack(stack):
+    """the images of a host stack as C-contiguous 2-D uint8 / uint16 arrays of one size"""
+    imgs = [np.ascontiguousarray(im) for im in stack] if stack is not None else []
+    if not imgs:
+        raise ValueError("Empty image stack")
+    f = imgs[0]
+    if f.ndim != 2 or f.dtype not in (np.uint8, np.uint16):
+        raise ValueError("images must be 2-D uint8 or uint16 arrays")
+    if any(im.shape != f.shape or im.dtype != f.dtype for im in imgs):
+        raise ValueError("all images must share size and type")
+    return imgs
+
+
+def pool_stack(stack, scale):
+    """An extension: the images of `stack` -- a list of 2-D uint8 or uint16 arrays of one size,
+    or one [n, rows, cols] array -- pooled by `scale` in 2..8 on the GPU (bicos_pool_host,
+    include/bicos_c.h "stack pooling"): each output pixel is (sum of its scale x scale block +
+    scale*scale // 2) // (scale*scale), the mean rounded half up, in integers. Returns an [n,
+    rows // scale, cols // scale] array of the input dtype, ready for match(); the rows % scale
+    last rows and cols % scale last columns are not read. (A numpy .mean().astype() truncates
+    instead: it is not this function.)"""
+    sc = _lib.pool_scale(scale)
+    imgs = _host_stack(stack)
+    f = imgs[0]
+    n = len(imgs)
+    prows, pcols = _lib.pool_shape(f.shape[0], f.shape[1], sc)
+    out = np.empty((n, prows, pcols), f.dtype)
+    src = (ctypes.c_void_p * n)(*[im.ctypes.data for im in imgs])
+    dst = (ctypes.c_void_p * n)(*[out[t].ctypes.data for t in range(n)])
+    L = _lib.lib()
+    rc = L.bicos_pool_host(None, src, n, f.shape[0], f.shape[1], 0, f.dtype.itemsize, sc, dst, 0)
+    if rc != 0:
+        raise RuntimeError("BICOS pooling failed: " + L.bicos_last_error().decode(errors="replace"))
+    return out
+
+
+def match_pyramid(stack0, stack1, cfg, scale=2, radius=2, spread=1, fallback=None):
+    """An extension: the coarse-to-fine match in one call, for disparity windows too wide for
+    one search (bicos_match_host_pyramid, include/bicos_c.h "pyramid match"). Byte for byte:
+    pool_stack of both stacks by `scale`; match() of the pooled stacks without a subpixel step
+    over cfg.disparity_range divided by scale (floor, ceil); guide_from_disparity(coarse,
+    radius, spread, scale, fallback, shape=(rows, cols)); match(guide=) of the full stacks.
+    cfg.disparity_range is required. fallback None: the global window clamped to +-32767; a
+    pair with lo > hi: do not search where the coarse map knows nothing. Each stack is uploaded
+    once. Returns (disparity, corrmap, stats) with stats = dict(from_prior, fallback)."""
+    if cfg is None:
+        raise ValueError("match_pyramid needs a Config with a disparity_range")
+    rng, sc, r, sp, flo, fhi = _lib.pyramid_params(getattr(cfg, "disparity_range", None), scale,
+                                                   radius, spread, fallback)
+    im0, im1 = _host_stack(stack0), _host_stack(stack1)
+    f = im0[0]
+    if len(im0) != len(im1) or im1[0].shape != f.shape or im1[0].dtype != f.dtype:
+        raise ValueError("both stacks must share length, size and type")
+    rows, cols = f.shape
+    _lib.pool_shape(rows, cols, sc)
+    n = len(im0)
+    L = _lib.lib()
+    ddtype = _get_np_dtype(L.bicos_output_type(cfg._c_config, 1))
+    cdtype = np.float64 if cfg._c_config.contents.precision else np.float32
+    disparity = np.empty((rows, cols), ddtype)
+    corrmap = np.empty((rows, cols), cdtype)
+    counts = (ctypes.c_uint32 * 2)()
+    d0 = (ctypes.c_void_p * n)(*[im.ctypes.data for im in im0])
+    d1 = (ctypes.c_void_p * n)(*[im.ctypes.data for im in im1])
+    rc = L.bicos_match_host_pyramid(None, d0, d1, n, rows, cols, 0, f.dtype.itemsize,
+                                    cfg._c_config, 1, rng[0], rng[1], sc, r, sp, flo, fhi,
+                                    disparity.ctypes.data, corrmap.ctypes.data, None, None, counts)
+    if rc != 0:
+        raise RuntimeError("BICOS matching failed: " + L.bicos_last_error().decode(errors="replace"))
+    return disparity, corrmap, dict(from_prior=counts[0], fallback=counts[1])
+
+
 def invalid_disparity(dtype):
     """reference pybicos/__init__.py:246-252."""
     L = _lib.lib()
