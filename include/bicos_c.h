@@ -575,6 +575,89 @@ int bicos_median_host(bicos_engine* e, const void* disparity, int disp_type, int
 /* The output tile (rows, cols) of one workgroup (tests). Returns BICOS_OK. */
 int bicos_median_tile(int* rows, int* cols);
 
+/* --------------------------------------------------------- surface normals */
+/* One unit normal per pixel of a dense rows x cols disparity map (BICOS_CV_16S or BICOS_CV_32F),
+ * oriented towards the camera, on the GPU: the least-squares plane of the disparities over a
+ * small window in (column, row, disparity), carried through Q. A plane there is a plane in 3-D
+ * because Q is projective, and disparity noise is homogeneous there, where the noise of the 3-D
+ * points grows with Z^2 along the ray. The reference has no such step.
+ * The stage is for SUBPIXEL maps. On integer disparities a surface that moves less than one
+ * level per window fits as a fronto-parallel stair step, whatever its tilt: this is no
+ * alternative to the subpixel step of the match.
+ * Inputs: the map; Q, 16 doubles, row-major; flags; radius in 1 .. 4; max_diff, a float >= 0 and
+ * not NaN (+inf is legal); min_points in 3 .. (2*radius+1)^2.
+ * Flags: BICOS_NORMALS_ALLOW_NEGATIVE_Z and BICOS_NORMALS_F32_SENTINEL have the meanings and
+ * values of BICOS_REPROJECT_ALLOW_NEGATIVE_Z and BICOS_REPROJECT_F32_SENTINEL.
+ * Arithmetic: everything below is IEEE double, one rounding per written operation and no
+ * contraction, unless it says float32.
+ *     reproj(x, y, d)   o[i] = ((Q[4i]*x + Q[4i+1]*y) + Q[4i+2]*d) + Q[4i+3], iw = 1.0/o[3],
+ *                       returning (o[0]*iw, o[1]*iw, o[2]*iw) as doubles: the formula of
+ *                       "reprojection" without the final cast.
+ * For pixel p = (row y, column x) with disparity dp:
+ *     1. own point   if bicos_reproject_* with the same map, Q and flags does not keep p, the
+ *                    class is no_point (its classes invalid, nonfinite and negative_z).
+ *     2. members     the window pixels q within `radius` of p in both axes, clipped to the image
+ *                    without replication, that are valid in the sense of step 1's invalid test
+ *                    and satisfy fabsf((float)dq - (float)dp) <= max_diff: one float32
+ *                    subtraction, the speckle filter's link. p itself is always a member.
+ *     3. sums        over the members in row-major window order, with du = col_q - x,
+ *                    dv = row_q - y and e = (double)dq - (double)dp (one subtraction):
+ *                    integers, exact: m (the member count), Su, Sv, Suu, Suv, Svv;
+ *                    doubles, starting at 0.0: Sd = Sd + e; Sud = Sud + (double)du*e;
+ *                    Svd = Svd + (double)dv*e, each a product and then an add. (For int16 maps
+ *                    every one of these is an exact integer in any order.)
+ *     4. sparse      m < min_points: the class is sparse.
+ *     5. determinant in integers (every value is below 2^31):
+ *                        C00 = Svv*m - Sv*Sv    C01 = Su*Sv - Suv*m     C02 = Suv*Sv - Svv*Su
+ *                        C11 = Suu*m - Su*Su    C12 = Suv*Su - Suu*Sv   C22 = Suu*Svv - Suv*Suv
+ *                        det = Suu*C00 + Suv*C01 + Su*C02
+ *                    det == 0 (collinear members): the class is degenerate.
+ *     6. plane       with the C's and det converted to double:
+ *                        a = ((C00*Sud + C01*Svd) + C02*Sd) / det
+ *                        b = ((C01*Sud + C11*Svd) + C12*Sd) / det
+ *                        c = ((C02*Sud + C12*Svd) + C22*Sd) / det
+ *                    the plane e ~ a*du + b*dv + c.
+ *     7. vectors     d0 = (double)dp + c; P0 = reproj(x, y, d0); P1 = reproj(x + 1.0, y, d0 + a);
+ *                    P2 = reproj(x, y + 1.0, d0 + b); U = P1 - P0; V = P2 - P0;
+ *                    N = (Uy*Vz - Uz*Vy, Uz*Vx - Ux*Vz, Ux*Vy - Uy*Vx).
+ *                    If (Nx*P0x + Ny*P0y) + Nz*P0z > 0, N is negated: the normal then faces the
+ *                    origin of Q's frame.
+ *     8. length      L = sqrt((Nx*Nx + Ny*Ny) + Nz*Nz); L zero or not finite: degenerate.
+ *     9. result      otherwise the class is normal and the result is
+ *                    ((float)(Nx/L), (float)(Ny/L), (float)(Nz/L)).
+ * A pixel of any class but normal gets three NaNs (0x7FC00000).
+ * Outputs, either alone or both:
+ *     normal_map  float32 [rows][cols][3].
+ *     normals     float32 [count][3], with index (int32 [count], as bicos_reproject_* writes
+ *                 it): normals[i] is the normal of pixel index[i], bit for bit the map's. An
+ *                 index outside 0 .. rows*cols-1 gives three NaNs and reads nothing.
+ *     counts      optional, uint32[4] = {normal, no_point, sparse, degenerate} over the whole
+ *                 map; they sum to rows*cols. Allowed only together with normal_map.
+ * rows*cols must fit int32. rows == 0 or cols == 0 is legal: the counts are all zero and no map
+ * is launched (a list then holds NaNs alone).
+ * Argument errors are BICOS_E_ARG before any HIP call, and bicos_last_error says which: a type
+ * other than 16S / 32F; unknown flag bits; radius, max_diff or min_points out of range; a
+ * negative size or too many pixels for int32; a NULL map or Q on a non-empty map; no output at
+ * all; normals without index or index without normals; counts without normal_map; an output
+ * overlapping the map.
+ * The results are deterministic, and equal to a float64 CPU evaluation of the text above bit for
+ * bit. */
+#define BICOS_NORMALS_ALLOW_NEGATIVE_Z 1
+#define BICOS_NORMALS_F32_SENTINEL 2
+/* device: asynchronous on `stream`. Needs no workspace: e may be NULL. */
+int bicos_normals_device(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                         const double Q[16], int flags, int radius, float max_diff, int min_points,
+                         float* normal_map, const int32_t* index, size_t count, float* normals,
+                         uint32_t* counts, void* stream);
+/* host buffers, synchronous, e NULL = default engine: uploads the map (and index), runs the same
+ * launches, downloads what was asked for. */
+int bicos_normals_host(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                       const double Q[16], int flags, int radius, float max_diff, int min_points,
+                       float* normal_map, const int32_t* index, size_t count, float* normals,
+                       uint32_t counts[4]);
+/* The tile (rows, cols) of the dense map one workgroup stages (tests). Returns BICOS_OK. */
+int bicos_normals_tile(int* rows, int* cols);
+
 /* --------------------------------------------------------- disparity guide */
 /* The search restricted to one disparity window PER LEFT PIXEL, from a prior: the previous
  * frame's map of a continuous scan, the match of a downsampled stack, a CAD pose, a

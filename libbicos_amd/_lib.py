@@ -67,6 +67,7 @@ EXPORTS = (
     "bicos_rectify_maps_device", "bicos_rectify_maps_host", "bicos_rectify_device",
     "bicos_rectify_host", "bicos_rectify_tile",
     "bicos_median_device", "bicos_median_host", "bicos_median_tile",
+    "bicos_normals_device", "bicos_normals_host", "bicos_normals_tile",
     "bicos_search_device_guided", "bicos_match_device_guided", "bicos_match_host_guided",
     "bicos_guide_device", "bicos_guide_host",
     "bicos_pool_device", "bicos_pool_host", "bicos_pool_tile", "bicos_pool_kernel",
@@ -91,6 +92,11 @@ SPECKLE_F32_SENTINEL = 1
 
 # bicos_median_* flag (include/bicos_c.h)
 MEDIAN_F32_SENTINEL = 1
+
+# bicos_normals_* flags (include/bicos_c.h): the values of the bicos_reproject_* flags
+NORMALS_ALLOW_NEGATIVE_Z = 1
+NORMALS_F32_SENTINEL = 2
+NORMALS_MAX_RADIUS = 4
 
 # bicos_guide_* flag (include/bicos_c.h)
 GUIDE_F32_SENTINEL = 1
@@ -227,6 +233,12 @@ def lib() -> ctypes.CDLL:
     L.bicos_median_host.restype = I
     L.bicos_median_tile.argtypes = [PI, PI]
     L.bicos_median_tile.restype = I
+    L.bicos_normals_device.argtypes = [P, P, I, I, I, PD, I, I, F, I, P, P, Z, P, P, P]
+    L.bicos_normals_device.restype = I
+    L.bicos_normals_host.argtypes = [P, P, I, I, I, PD, I, I, F, I, P, P, Z, P, P]
+    L.bicos_normals_host.restype = I
+    L.bicos_normals_tile.argtypes = [PI, PI]
+    L.bicos_normals_tile.restype = I
     L.bicos_search_device_guided.argtypes = [P, P, P, I, I, I, I, I, I, I, P, Z, P, P]
     L.bicos_search_device_guided.restype = I
     L.bicos_match_device_guided.argtypes = [P, P, P, I, I, I, Z, Z, I,
@@ -435,6 +447,38 @@ def median_tile():
     """(rows, cols) of the output tile of one workgroup (bicos_median_tile)."""
     r, c = ctypes.c_int(0), ctypes.c_int(0)
     lib().bicos_median_tile(ctypes.byref(r), ctypes.byref(c))
+    return r.value, c.value
+
+
+def normals_flags(allow_negative_z: bool, sentinel: bool) -> int:
+    return (NORMALS_ALLOW_NEGATIVE_Z if allow_negative_z else 0) | \
+        (NORMALS_F32_SENTINEL if sentinel else 0)
+
+
+def normals_params(radius, max_diff, min_points):
+    """(int radius, float max_diff, int min_points) as the bicos_normals_* entries take them
+    (ValueError for what they would refuse: a radius outside 1 .. 4, a negative or NaN
+    max_diff, a min_points outside 3 .. (2 * radius + 1)^2)."""
+    try:
+        r, m, diff = int(radius), int(min_points), float(max_diff)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("radius and min_points must be integers and max_diff a number, got "
+                         "%r, %r, %r" % (radius, min_points, max_diff))
+    if r != radius or r < 1 or r > NORMALS_MAX_RADIUS:
+        raise ValueError("radius must be an integer in [1, %d], got %r"
+                         % (NORMALS_MAX_RADIUS, radius))
+    if not diff >= 0:
+        raise ValueError("max_diff must be >= 0 and not NaN, got %r" % (max_diff,))
+    if m != min_points or m < 3 or m > (2 * r + 1) ** 2:
+        raise ValueError("min_points must be an integer in [3, %d], got %r"
+                         % ((2 * r + 1) ** 2, min_points))
+    return r, diff, m
+
+
+def normals_tile():
+    """(rows, cols) of the tile of the dense map one workgroup stages (bicos_normals_tile)."""
+    r, c = ctypes.c_int(0), ctypes.c_int(0)
+    lib().bicos_normals_tile(ctypes.byref(r), ctypes.byref(c))
     return r.value, c.value
 
 

@@ -6,6 +6,8 @@
 //   bicos-cli folder0 [folder1] [-t 0.75] [-v VAR] [-s STEP] [-o bicosdisp.png] [-n N]
 //             [-q Q.yml] [--allow-negative-z] [-m MAXDIFF] [--double] [--limited]
 //             [--corrmap] [--no-dupes] [-h]
+// and, beyond the reference: --speckle-size / --speckle-diff, --median / --median-fill,
+// --rectify, --normals / --normals-diff / --normals-min (see USAGE below).
 //
 // Same options, defaults and semantics as the reference (FULL transform unless --limited;
 // --threshold <= 0 disables the NXC filter; --corrmap without a threshold computes with
@@ -61,6 +63,15 @@ const char* USAGE =
     "      --median-fill M     also fill an invalid pixel whose window holds at least M valid\n"
     "                          disparities (K*K/2 + 1: only surrounded holes; 0: none; only\n"
     "                          with --median)\n"
+    "      --normals R         with a Q matrix: also estimate a unit surface normal per point,\n"
+    "                          towards the camera, from the plane fitted to the disparities of\n"
+    "                          the (2R+1) x (2R+1) window (R in 1..4); each .xyz line becomes\n"
+    "                          X Y Z NX NY NZ, with 0 0 0 where a point has no normal. Meant\n"
+    "                          for subpixel maps (--step): integer disparities stair-step\n"
+    "      --normals-diff F    a window pixel takes part if its disparity lies within F of the\n"
+    "                          centre's (1; only with --normals)\n"
+    "      --normals-min M     least number of window pixels for a normal (3; only with\n"
+    "                          --normals)\n"
     "      --rectify FILE      the inputs are raw frames: OpenCV FileStorage (YAML/XML) with\n"
     "                          the matrices M1 D1 R1 P1 M2 D2 R2 P2 of cv::stereoRectify;\n"
     "                          both stacks are rectified to their own size before the match.\n"
@@ -88,7 +99,8 @@ Args parse(int argc, char** argv) {
         {"stacksize", true}, {"qmatrix", true}, {"lr-maxdiff", true}, {"help", false},
         {"allow-negative-z", false}, {"double", false}, {"limited", false},
         {"corrmap", false}, {"no-dupes", false}, {"speckle-size", true}, {"speckle-diff", true},
-        {"rectify", true}, {"median", true}, {"median-fill", true}};
+        {"rectify", true}, {"median", true}, {"median-fill", true}, {"normals", true},
+        {"normals-diff", true}, {"normals-min", true}};
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i];
@@ -306,17 +318,46 @@ int run(int argc, char** argv) {
         // the points come from the GPU (bicos_reproject_host: bicos_cli::write_xyz's arithmetic
         // bit for bit); only the text is made here
         const size_t pixels = (size_t)disp.rows() * disp.cols();
+        const bool with_normals = args.has("normals");
         std::vector<float> points(3 * pixels + 1);
+        std::vector<int32_t> index(with_normals ? pixels + 1 : 0);
         uint32_t counts[4] = {0, 0, 0, 0};  // kept, invalid, nonfinite, negative_z
+        const int flags = args.has("allow-negative-z") ? BICOS_REPROJECT_ALLOW_NEGATIVE_Z : 0;
         if (bicos_reproject_host(nullptr, disp.data(), disp.type(), disp.rows(), disp.cols(),
-                                 Q.data(), args.has("allow-negative-z") ? BICOS_REPROJECT_ALLOW_NEGATIVE_Z : 0,
-                                 nullptr, points.data(), nullptr, pixels, counts) != BICOS_OK)
+                                 Q.data(), flags, nullptr, points.data(),
+                                 with_normals ? index.data() : nullptr, pixels, counts) != BICOS_OK)
             throw std::runtime_error(std::string("reprojection failed: ") + bicos_last_error());
-        bicos_cli::write_xyz_points(xyz.string(), points.data(), counts[0]);
+        if (with_normals) {
+            // one normal per point of the list, on the same map with the same flags (the two
+            // flag sets share their values)
+            const unsigned radius = as_uint(args, "normals");
+            const float max_diff = args.has("normals-diff") ? as_float(args, "normals-diff") : 1.0f;
+            const unsigned min_points = args.has("normals-min") ? as_uint(args, "normals-min") : 3u;
+            if (radius < 1 || radius > 4) throw std::invalid_argument("--normals: R must lie in 1 .. 4");
+            if (min_points < 3 || min_points > (2 * radius + 1) * (2 * radius + 1))
+                throw std::invalid_argument("--normals-min: M must lie in 3 .. (2R+1)^2");
+            std::vector<float> normals(3 * pixels + 1);
+            if (bicos_normals_host(nullptr, disp.data(), disp.type(), disp.rows(), disp.cols(),
+                                   Q.data(), flags, (int)radius, max_diff, (int)min_points, nullptr,
+                                   index.data(), counts[0], normals.data(), nullptr) != BICOS_OK)
+                throw std::runtime_error(std::string("normals failed: ") + bicos_last_error());
+            size_t have = 0;
+            for (size_t i = 0; i < counts[0]; ++i) have += normals[3 * i] == normals[3 * i];
+            bicos_cli::write_xyz_points_normals(xyz.string(), points.data(), normals.data(), counts[0]);
+            std::cout << "Normals:\t" << have << " of " << counts[0] << " points" << std::endl;
+        } else {
+            bicos_cli::write_xyz_points(xyz.string(), points.data(), counts[0]);
+        }
         std::cout << "Saved pointcloud in ascii-format to\t" << xyz << std::endl;
         if (counts[2]) std::cerr << "Skipped " << counts[2] << " points with non-finite fp values" << std::endl;
         if (counts[3]) std::cerr << "Skipped " << counts[3] << " points with negative Z values" << std::endl;
     }
+    if (!q_store)
+        for (const char* k : {"normals", "normals-diff", "normals-min"})
+            if (args.has(k)) std::cerr << "'" << k << "' has no effect without a Q matrix.\n";
+    if (q_store && !args.has("normals"))
+        for (const char* k : {"normals-diff", "normals-min"})
+            if (args.has(k)) std::cerr << "'" << k << "' has no effect without 'normals'.\n";
     return 0;
 }
 

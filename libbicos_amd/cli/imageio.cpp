@@ -471,6 +471,20 @@ void write_xyz_points(const std::string& path, const float* points, size_t count
         xyz << p[0] << ' ' << p[1] << ' ' << p[2] << '\n';
 }
 
+void write_xyz_points_normals(const std::string& path, const float* points, const float* normals,
+                              size_t count) {
+    std::ofstream xyz(path);
+    if (!xyz) throw std::runtime_error("cannot write " + path);
+    for (size_t i = 0; i < count; ++i) {
+        const float *p = points + 3 * i, *n = normals + 3 * i;
+        xyz << p[0] << ' ' << p[1] << ' ' << p[2];
+        if (n[0] != n[0])  // (a point without a normal has three NaNs)
+            xyz << " 0 0 0\n";
+        else
+            xyz << ' ' << n[0] << ' ' << n[1] << ' ' << n[2] << '\n';
+    }
+}
+
 void read_stacks(const std::string& folder0, const std::optional<std::string>& folder1,
                  std::vector<Gray>& left, std::vector<Gray>& right) {
     namespace fs = std::filesystem;

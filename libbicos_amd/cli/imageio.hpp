@@ -76,6 +76,9 @@ XyzStats write_xyz(const std::string& path, const BICOS::Image& disparity,
                    const std::array<double, 16>& Q, bool allow_negative_z);
 // The same lines for `count` points (x, y, z each) already reprojected (bicos_reproject_host).
 void write_xyz_points(const std::string& path, const float* points, size_t count);
+// ... with a normal per point: "X Y Z NX NY NZ", and "0 0 0" where normals[i] is three NaNs
+void write_xyz_points_normals(const std::string& path, const float* points, const float* normals,
+                              size_t count);
 
 // reference read_sequence + sort_sequence_to_stack (src/fileutils.cpp:60-154): with two
 // folders, files named <idx>.<ext> in each (16-bit kept); with one, <idx>_left.<ext> and

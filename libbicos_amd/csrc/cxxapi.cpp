@@ -6,6 +6,7 @@
 //   BICOS::filter_speckles  (bicos/speckle.hpp; no reference counterpart)
 //   BICOS::rectify_maps, BICOS::rectify  (bicos/rectify.hpp; no reference counterpart)
 //   BICOS::median_filter  (bicos/median.hpp; no reference counterpart)
+//   BICOS::normals  (bicos/normals.hpp; no reference counterpart)
 //   BICOS::guide_from_disparity, the guided BICOS::match  (bicos/guide.hpp; likewise)
 //   BICOS::pool_stack, BICOS::match_pyramid  (bicos/pool.hpp; likewise)
 #include "engine.hpp"
@@ -23,6 +24,7 @@
 #include "../../include/bicos/speckle.hpp"
 #include "../../include/bicos/rectify.hpp"
 #include "../../include/bicos/median.hpp"
+#include "../../include/bicos/normals.hpp"
 #include "../../include/bicos/guide.hpp"
 #include "../../include/bicos/pool.hpp"
 
@@ -504,6 +506,94 @@ MedianStats median_filter(const Image& disparity, Image& out, int ksize, int fil
                            "counts download"));
     }
     return MedianStats{counts[0], counts[1], counts[2], counts[3]};
+}
+
+// ------------------------------------------------------------------ BICOS::normals
+// over the C entries (entries.cpp), which validate and launch
+
+namespace {
+
+void check_normals_map(const Image& disparity) {
+    if (disparity.type() != S16 && disparity.type() != F32)
+        throw Exception("normals: the disparity map must be S16 or F32");
+    if (disparity.step() != (size_t)disparity.cols() * disparity.elemSize() && disparity.rows() > 1)
+        throw Exception("normals: the disparity map must be dense");
+    if ((int64_t)disparity.cols() * 3 > INT32_MAX) throw Exception("normals: map too wide");
+}
+
+}  // namespace
+
+void normals(const Image& disparity, const Matx44d& Q, Image& normal_map,
+             const NormalsParams& p, hipStream_t stream) {
+    check_normals_map(disparity);
+    const int rows = disparity.rows(), cols = disparity.cols();
+    normal_map.create(rows, 3 * cols, F32, disparity.memory());
+    if (disparity.memory() == Memory::Host)
+        throw_rc(bicos_normals_host(nullptr, disparity.data(), disparity.type(), rows, cols,
+                                    Q.data(), p.flags, p.radius, p.max_diff, p.min_points,
+                                    (float*)normal_map.data(), nullptr, 0, nullptr, nullptr));
+    else
+        throw_rc(bicos_normals_device(nullptr, disparity.data(), disparity.type(), rows, cols,
+                                      Q.data(), p.flags, p.radius, p.max_diff, p.min_points,
+                                      (float*)normal_map.data(), nullptr, 0, nullptr, nullptr,
+                                      stream));
+}
+
+void normals(const Image& disparity, const Matx44d& Q, float* normal_map, const int32_t* index,
+             size_t count, float* normals_out, uint32_t* counts, const NormalsParams& p,
+             hipStream_t stream) {
+    check_normals_map(disparity);
+    if (disparity.memory() != Memory::Device)
+        throw Exception("normals: device buffers need a device map");
+    throw_rc(bicos_normals_device(nullptr, disparity.data(), disparity.type(), disparity.rows(),
+                                  disparity.cols(), Q.data(), p.flags, p.radius, p.max_diff,
+                                  p.min_points, normal_map, index, count, normals_out, counts,
+                                  stream));
+}
+
+NormalStats normals(const Image& disparity, const Matx44d& Q, const std::vector<int32_t>& index,
+                    std::vector<float>& normals_out, const NormalsParams& p, Image* normal_map) {
+    check_normals_map(disparity);
+    const int rows = disparity.rows(), cols = disparity.cols();
+    const size_t count = index.size();
+    uint32_t counts[4] = {0, 0, 0, 0};
+    if (normal_map) normal_map->create(rows, 3 * cols, F32, disparity.memory());
+    float* map = normal_map ? (float*)normal_map->data() : nullptr;
+    std::vector<float> list(3 * count + 1);  // (+1: never a null pointer)
+    std::vector<int32_t> idx(index);
+    idx.push_back(0);  // (likewise)
+    if (disparity.memory() == Memory::Host) {
+        throw_rc(bicos_normals_host(nullptr, disparity.data(), disparity.type(), rows, cols,
+                                    Q.data(), p.flags, p.radius, p.max_diff, p.min_points, map,
+                                    idx.data(), count, list.data(), normal_map ? counts : nullptr));
+    } else {
+        // counts | normals | index in one allocation
+        const size_t words = 4 + 3 * count + count;
+        void* raw = nullptr;
+        throw_rc(check_hip(hipMalloc(&raw, words * 4), "hipMalloc(normals)"));
+        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
+        uint32_t* d_counts = (uint32_t*)raw;
+        float* d_list = (float*)raw + 4;
+        int32_t* d_index = (int32_t*)raw + 4 + 3 * count;
+        if (count)
+            throw_rc(check_hip(hipMemcpy(d_index, index.data(), count * sizeof(int32_t),
+                                         hipMemcpyHostToDevice), "index upload"));
+        throw_rc(bicos_normals_device(nullptr, disparity.data(), disparity.type(), rows, cols,
+                                      Q.data(), p.flags, p.radius, p.max_diff, p.min_points, map,
+                                      d_index, count, d_list, normal_map ? d_counts : nullptr,
+                                      nullptr));
+        if (normal_map)
+            throw_rc(check_hip(hipMemcpy(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost),
+                               "counts download"));
+        if (count)
+            throw_rc(check_hip(hipMemcpy(list.data(), d_list, count * 3 * sizeof(float),
+                                         hipMemcpyDeviceToHost), "normals download"));
+        else
+            throw_rc(check_hip(hipStreamSynchronize(nullptr), "hipStreamSynchronize"));
+    }
+    list.resize(3 * count);
+    normals_out.swap(list);
+    return NormalStats{counts[0], counts[1], counts[2], counts[3]};
 }
 
 // ------------------------------------------------------ BICOS::guide_from_disparity

@@ -8,6 +8,7 @@
 #include "reproject.hpp"
 #include "speckle.hpp"
 #include "median.hpp"
+#include "normals.hpp"
 #include "guide.hpp"
 #include "pool.hpp"
 
@@ -738,6 +739,81 @@ int median_device(const MedianJob& j, hipStream_t st) {
     a.counts = j.counts;
     return check_hip(bicos_hip::launch_median(a, j.disp_type == BICOS_CV_32F, j.ksize, st),
                      "median launch");
+}
+
+// ----------------------------------------------------------- surface normals
+
+int check_normals(const NormalsJob& j) {
+    if (j.disp_type != BICOS_CV_16S && j.disp_type != BICOS_CV_32F)
+        return fail(BICOS_E_ARG, "normals: the disparity map must be CV_16S or CV_32F");
+    if (j.flags & ~(BICOS_NORMALS_ALLOW_NEGATIVE_Z | BICOS_NORMALS_F32_SENTINEL))
+        return fail(BICOS_E_ARG, "normals: unknown flag bits");
+    if (j.radius < 1 || j.radius > bicos_hip::NORMALS_MAX_RADIUS)
+        return fail(BICOS_E_ARG, "normals: radius must lie in 1 .. 4");
+    if (!(j.max_diff >= 0.0f))
+        return fail(BICOS_E_ARG, "normals: max_diff must be >= 0 and not NaN");
+    if (j.min_points < 3 || j.min_points > (2 * j.radius + 1) * (2 * j.radius + 1))
+        return fail(BICOS_E_ARG, "normals: min_points must lie in 3 .. (2 * radius + 1)^2");
+    if (j.rows < 0 || j.cols < 0) return fail(BICOS_E_ARG, "normals: negative image size");
+    if ((int64_t)j.rows * j.cols > INT32_MAX)
+        return fail(BICOS_E_ARG, "normals: rows * cols exceeds int32");
+    if (!j.normal_map && !j.normals && !j.index)
+        return fail(BICOS_E_ARG, "normals: no output (normal_map and normals both null)");
+    if (j.normals && !j.index) return fail(BICOS_E_ARG, "normals: normals without index");
+    if (j.index && !j.normals) return fail(BICOS_E_ARG, "normals: index without normals");
+    if (j.counts && !j.normal_map)
+        return fail(BICOS_E_ARG, "normals: counts need normal_map (they count over the map)");
+    if (j.rows > 0 && j.cols > 0) {
+        if (!j.disp) return fail(BICOS_E_ARG, "normals: null disparity map");
+        if (!j.Q) return fail(BICOS_E_ARG, "normals: null Q");
+        const uintptr_t pixels = (uintptr_t)j.rows * j.cols;
+        const uintptr_t a = (uintptr_t)j.disp;
+        const uintptr_t bytes = pixels * (j.disp_type == BICOS_CV_32F ? 4 : 2);
+        auto overlaps = [&](const void* p, uintptr_t n) {
+            const uintptr_t b = (uintptr_t)p;
+            return p && n && a < b + n && b < a + bytes;
+        };
+        if (overlaps(j.normal_map, pixels * 12))
+            return fail(BICOS_E_ARG, "normals: normal_map overlaps the map");
+        if (overlaps(j.normals, (uintptr_t)j.count * 12))
+            return fail(BICOS_E_ARG, "normals: normals overlaps the map");
+        if (overlaps(j.counts, 4 * sizeof(uint32_t)))
+            return fail(BICOS_E_ARG, "normals: counts overlaps the map");
+    }
+    return BICOS_OK;
+}
+
+int normals_device(const NormalsJob& j, hipStream_t st) {
+    const size_t pixels = (size_t)j.rows * j.cols;
+    bicos_hip::NormalsArgs a{};
+    a.disp = j.disp;
+    a.rows = j.rows;
+    a.cols = j.cols;
+    a.flags = j.flags;
+    a.radius = j.radius;
+    a.max_diff = j.max_diff;
+    a.min_points = j.min_points;
+    if (j.Q) std::copy(j.Q, j.Q + 16, a.Q.q);  // (may be null for an empty map: nothing reads it)
+    a.normal_map = j.normal_map;
+    a.counts = j.counts;
+    a.index = j.index;
+    a.normals = j.normals;
+    a.count = j.count;
+    const bool f32 = j.disp_type == BICOS_CV_32F;
+    if (j.normal_map) {
+        if (pixels == 0) {  // no map to launch: the counts are all zero
+            if (j.counts)
+                if (int rc = check_hip(hipMemsetAsync(j.counts, 0, 4 * sizeof(uint32_t), st),
+                                       "hipMemsetAsync(counts)"))
+                    return rc;
+        } else if (int rc = check_hip(bicos_hip::launch_normals_map(a, f32, st),
+                                      "normals map launch")) {
+            return rc;
+        }
+    }
+    if (j.normals && j.count > 0)
+        return check_hip(bicos_hip::launch_normals_list(a, f32, st), "normals list launch");
+    return BICOS_OK;
 }
 
 // ------------------------------------------------------------ disparity guide

@@ -8,16 +8,17 @@
 //               and match_device; reproject_device (disparity map -> 3-D points);
 //               speckle_device (the speckle filter of a disparity map); rectify_device and
 //               rectify_maps_device (raw stacks -> rectified stacks); median_device (the
-//               median filter of a disparity map); guide_device (a prior disparity map ->
+//               median filter of a disparity map); normals_device (a disparity map -> unit
+//               surface normals); guide_device (a prior disparity map ->
 //               per-pixel search windows); pool_device (a stack pooled by an integer factor);
 //               match_pyramid_device (pool, coarse ranged match, guide, guided match)
 //   host.cpp    the banded host-buffer pipeline (HostPool, match_host); reproject_host;
-//               speckle_host; rectify_host, rectify_maps_host; median_host; guide_host;
-//               pool_host; match_pyramid_host
+//               speckle_host; rectify_host, rectify_maps_host; median_host; normals_host;
+//               guide_host; pool_host; match_pyramid_host
 //   entries.cpp the bicos_* extern "C" entries (bicos_c.h) but the multi-GPU ones
 //   multi.cpp   bicos_match_host_multi, bicos_match_bands_device
 //   cxxapi.cpp  namespace BICOS (HipImage, match, reproject, filter_speckles, median_filter,
-//               guide_from_disparity, pool_stack, match_pyramid)
+//               normals, guide_from_disparity, pool_stack, match_pyramid)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -443,6 +444,31 @@ int median_device(const MedianJob& j, hipStream_t st);
 // Host buffers: the map uploaded into the engine's staging, the same launch on the engine's
 // own stream, the map and the counts downloaded. Synchronous.
 int median_host(bicos_engine* e, const MedianJob& j);
+
+// One normal estimation (bicos_c.h "surface normals"): the arguments of bicos_normals_device /
+// bicos_normals_host, the pointers all in device or all in host memory.
+struct NormalsJob {
+    const void* disp;
+    int disp_type, rows, cols;
+    const double* Q;
+    int flags, radius;
+    float max_diff;
+    int min_points;
+    float* normal_map;
+    const int32_t* index;
+    size_t count;
+    float* normals;
+    uint32_t* counts;
+};
+// BICOS_E_ARG (with a message) for what the entries refuse; no HIP call.
+int check_normals(const NormalsJob& j);
+// The launches on `st` (validated arguments): the dense map, the list, or both. They need
+// nothing of an engine.
+int normals_device(const NormalsJob& j, hipStream_t st);
+// Host buffers: the map and the index uploaded into the engine's staging, the same launches on
+// the engine's own stream, the map, the list and the counts downloaded as asked. Synchronous.
+// rows * cols > 0 (bicos_normals_host answers an empty map itself, without an engine).
+int normals_host(bicos_engine* e, const NormalsJob& j);
 
 // One remap of a stack (bicos_c.h "rectification"): the arguments of bicos_rectify_device, the
 // pointers all in device memory, the stack pitches in elements, map_pitch in bytes (0 = dense).

@@ -4,10 +4,13 @@
 #include "reproject.hpp"
 #include "speckle.hpp"
 #include "median.hpp"
+#include "normals.hpp"
 #include "guide.hpp"
 #include "pool.hpp"
 
+#include <algorithm>
 #include <cmath>
+#include <limits>
 #include <vector>
 
 using namespace bicos_impl;
@@ -611,6 +614,49 @@ int bicos_median_host(bicos_engine* e, const void* disparity, int disp_type, int
 int bicos_median_tile(int* rows, int* cols) {
     if (rows) *rows = bicos_hip::MEDIAN_TILE_ROWS;
     if (cols) *cols = bicos_hip::MEDIAN_TILE_COLS;
+    return BICOS_OK;
+}
+
+int bicos_normals_device(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                         const double Q[16], int flags, int radius, float max_diff, int min_points,
+                         float* normal_map, const int32_t* index, size_t count, float* normals,
+                         uint32_t* counts, void* stream) {
+    const NormalsJob job{disparity, disp_type, rows, cols, Q, flags, radius, max_diff, min_points,
+                         normal_map, index, count, normals, counts};
+    if (int rc0 = check_normals(job)) return rc0;
+    (void)e;  // no workspace: nothing of the engine is used, so it may be NULL and is not locked
+    return guarded([&]() -> int { return normals_device(job, (hipStream_t)stream); });
+}
+
+int bicos_normals_host(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                       const double Q[16], int flags, int radius, float max_diff, int min_points,
+                       float* normal_map, const int32_t* index, size_t count, float* normals,
+                       uint32_t counts[4]) {
+    const NormalsJob job{disparity, disp_type, rows, cols, Q, flags, radius, max_diff, min_points,
+                         normal_map, index, count, normals, counts};
+    if (int rc0 = check_normals(job)) return rc0;
+    if (rows == 0 || cols == 0) {
+        // no map, and every list entry lies outside it: nothing to run, no engine to find
+        if (counts) std::fill(counts, counts + 4, 0u);
+        if (normals) std::fill(normals, normals + count * 3, std::numeric_limits<float>::quiet_NaN());
+        return BICOS_OK;
+    }
+    return guarded([&]() -> int {
+        if (!e) {
+            int dev = 0;
+            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
+            if (rc) return rc;
+            e = default_engine(dev);
+            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        }
+        std::lock_guard<std::mutex> g(e->lock);
+        return normals_host(e, job);
+    });
+}
+
+int bicos_normals_tile(int* rows, int* cols) {
+    if (rows) *rows = bicos_hip::NORMALS_TILE_ROWS;
+    if (cols) *cols = bicos_hip::NORMALS_TILE_COLS;
     return BICOS_OK;
 }
 

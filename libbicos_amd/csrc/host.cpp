@@ -597,6 +597,51 @@ int median_host(bicos_engine* e, const MedianJob& j) {
     return rc ? rc : rc2;
 }
 
+int normals_host(bicos_engine* e, const NormalsJob& j) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    if (int rc0 = check_normals(j)) return rc0;
+    const size_t pixels = (size_t)j.rows * j.cols;
+    const size_t count = j.normals ? j.count : 0;
+    if (pixels == 0) return fail(BICOS_E_ARG, "normals: empty map (the entry answers it)");
+    hipStream_t st = e->own_stream;
+    const size_t esz = j.disp_type == BICOS_CV_32F ? 4 : 2;
+    NormalsJob d = j;  // the same job on staged device buffers
+    Lease stage(e, e->stage, e->stage_bytes, st);
+    void* map = nullptr;
+    int32_t* index = nullptr;
+    auto carve = [&] {
+        map = stage.take(pixels * esz);
+        d.disp = map;
+        d.normal_map = j.normal_map ? stage.take<float>(pixels * 3) : nullptr;
+        index = count ? stage.take<int32_t>(count) : nullptr;
+        d.index = index;
+        d.normals = count ? stage.take<float>(count * 3) : nullptr;
+        d.count = count;
+        d.counts = j.counts ? stage.take<uint32_t>(4) : nullptr;
+    };
+    carve();
+    int rc = stage.acquire();
+    if (rc) return rc;
+    carve();
+    rc = check_hip(hipMemcpyAsync(map, j.disp, pixels * esz, hipMemcpyHostToDevice, st),
+                   "disparity upload");
+    if (!rc && count)
+        rc = check_hip(hipMemcpyAsync(index, j.index, count * sizeof(int32_t),
+                                      hipMemcpyHostToDevice, st), "index upload");
+    if (!rc) rc = normals_device(d, st);
+    if (!rc && j.normal_map)
+        rc = check_hip(hipMemcpyAsync(j.normal_map, d.normal_map, pixels * 3 * sizeof(float),
+                                      hipMemcpyDeviceToHost, st), "normal map download");
+    if (!rc && count)
+        rc = check_hip(hipMemcpyAsync(j.normals, d.normals, count * 3 * sizeof(float),
+                                      hipMemcpyDeviceToHost, st), "normals download");
+    if (!rc && j.counts)
+        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 4 * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, st), "counts download");
+    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    return rc ? rc : rc2;
+}
+
 int guide_host(bicos_engine* e, const GuideJob& j) {
     if (!e) return fail(BICOS_E_ARG, "null engine");
     if (int rc0 = check_guide_job(j)) return rc0;

@@ -497,6 +497,91 @@ class Engine:
         _lib.check(rc, "bicos_median_device")
         return out
 
+    # --------------------------------------------------------- surface normals
+    def normals_map(self, disp: torch.Tensor, Q, *, radius: int = 2, max_diff: float = 1.0,
+                    min_points: int = 3, allow_negative_z: bool = False,
+                    sentinel: bool = False, out: Optional[torch.Tensor] = None,
+                    counts: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """bicos_normals_device, the dense map: one unit surface normal per pixel of an int16
+        or float32 disparity map [rows, cols], oriented towards the camera, as a float32
+        [rows, cols, 3] tensor; include/bicos_c.h, "surface normals". The normal is that of the
+        least-squares plane of the disparities over the (2 * radius + 1)^2 window (radius 1 ..
+        4) in (column, row, disparity), carried through the 4x4 matrix Q; a window pixel takes
+        part if it is valid and its disparity lies within max_diff of the centre's. Three NaNs
+        where reproject_map with the same flags keeps no point, where fewer than min_points
+        pixels take part, or where they are collinear. Meant for SUBPIXEL maps: integer
+        disparities stair-step.
+
+        `counts`, an int32 [4] tensor on the map's device, receives {normal, no_point, sparse,
+        degenerate} (uint32 bits). The call NEVER synchronises: everything is enqueued on
+        `stream` (default: torch's current stream)."""
+        rows, cols, typ, q = self._reproject_args(disp, Q)
+        r, diff, m = _lib.normals_params(radius, max_diff, min_points)
+        dev = disp.device
+        if out is None:
+            out = torch.empty((rows, cols, 3), dtype=torch.float32, device=dev)
+        _check_out(out, "out", (rows, cols, 3), (torch.float32,), dev)
+        if counts is not None:
+            _check_out(counts, "counts", (4,), (torch.int32,), dev)
+        if rows * cols == 0:  # (an empty tensor has no pointer to hand over)
+            if counts is not None:
+                s = stream if stream is not None else torch.cuda.current_stream(dev)
+                with torch.cuda.stream(s):
+                    counts.zero_()
+            return out
+        rc = self._L.bicos_normals_device(
+            self._h, disp.data_ptr(), typ, rows, cols, q,
+            _lib.normals_flags(allow_negative_z, sentinel), r, diff, m, out.data_ptr(), None, 0,
+            None, counts.data_ptr() if counts is not None else None, _stream(dev, stream))
+        _lib.check(rc, "bicos_normals_device")
+        return out
+
+    def normals_points(self, disp: torch.Tensor, Q, index: torch.Tensor, *, radius: int = 2,
+                       max_diff: float = 1.0, min_points: int = 3,
+                       allow_negative_z: bool = False, sentinel: bool = False,
+                       out: Optional[torch.Tensor] = None,
+                       normal_map: Optional[torch.Tensor] = None,
+                       counts: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """bicos_normals_device, the list: the normal of every pixel of `index` (int32 [count],
+        row * cols + col, as reproject_points writes it with with_index) as a float32 [count, 3]
+        tensor, bit for bit the rows of normals_map; three NaNs for an entry outside the map.
+        With `normal_map`, a float32 [rows, cols, 3] tensor, the dense map is written by the
+        same call, and `counts` (normals_map's) may be given with it. The parameters are
+        normals_map's. The call NEVER synchronises."""
+        rows, cols, typ, q = self._reproject_args(disp, Q)
+        r, diff, m = _lib.normals_params(radius, max_diff, min_points)
+        dev = disp.device
+        if index.dim() != 1:
+            raise ValueError("index must be [count]")
+        count = index.shape[0]
+        _check_out(index, "index", (count,), (torch.int32,), dev)
+        if out is None:
+            out = torch.empty((count, 3), dtype=torch.float32, device=dev)
+        _check_out(out, "out", (count, 3), (torch.float32,), dev)
+        if normal_map is not None:
+            _check_out(normal_map, "normal_map", (rows, cols, 3), (torch.float32,), dev)
+        if counts is not None:
+            if normal_map is None:
+                raise ValueError("counts need normal_map: they count over the map")
+            _check_out(counts, "counts", (4,), (torch.int32,), dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        if rows * cols == 0:  # (an empty tensor has no pointer to hand over)
+            with torch.cuda.stream(s):
+                out.fill_(float("nan"))
+                if counts is not None:
+                    counts.zero_()
+            return out
+        if count == 0 and normal_map is None:
+            return out
+        rc = self._L.bicos_normals_device(
+            self._h, disp.data_ptr(), typ, rows, cols, q,
+            _lib.normals_flags(allow_negative_z, sentinel), r, diff, m,
+            normal_map.data_ptr() if normal_map is not None else None,
+            index.data_ptr() if count else None, count, out.data_ptr() if count else None,
+            counts.data_ptr() if counts is not None else None, s.cuda_stream)
+        _lib.check(rc, "bicos_normals_device")
+        return out
+
     # --------------------------------------------------------- disparity guide
     def guide_from_disparity(self, prior: torch.Tensor, radius: int, spread: int = 0,
                              scale: int = 1, fallback: Optional[Tuple[int, int]] = None,

@@ -293,6 +293,51 @@ def reproject(disparity, Q, allow_negative_z=False, sentinel=True):
     return points[:counts[0]].copy()
 
 
+def normals(disparity, Q, radius=2, max_diff=1.0, min_points=3, allow_negative_z=False,
+            sentinel=True, index=None):
+    """An extension (the reference has no such step): one unit surface normal per pixel of a
+    disparity map from match() -- int16 or float32, [rows, cols] --, oriented towards the
+    camera: the least-squares plane of the disparities over the (2 * radius + 1)^2 window in
+    (column, row, disparity), carried through the rig's 4x4 matrix Q (bicos_normals_host,
+    include/bicos_c.h "surface normals": on the GPU, bit for bit the double-precision text). A
+    window pixel takes part if it is valid and within max_diff of the centre's disparity.
+    Returns the float32 [rows, cols, 3] map, or with `index` (int32 pixel indices row * cols +
+    col, as the reprojection orders its points) the float32 [len(index), 3] list. Three NaNs
+    where reproject() with the same flags keeps no point, where fewer than min_points pixels
+    take part or where they are collinear. Meant for subpixel (float32) maps: integer
+    disparities stair-step."""
+    d = np.ascontiguousarray(disparity)
+    if d.ndim != 2:
+        raise ValueError("disparity map must be 2-D")
+    if d.dtype != np.int16 and d.dtype != np.float32:
+        raise ValueError(f"Unsupported disparity dtype: {d.dtype}")
+    rows, cols = d.shape
+    q = _lib.reproject_q(Q)
+    r, diff, m = _lib.normals_params(radius, max_diff, min_points)
+    flags = _lib.normals_flags(allow_negative_z, sentinel)
+    L = _lib.lib()
+    if index is None:
+        out = np.empty((rows, cols, 3), np.float32)
+        if rows * cols == 0:
+            return out
+        rc = L.bicos_normals_host(None, d.ctypes.data, _get_cv_type(d.dtype), rows, cols, q,
+                                  flags, r, diff, m, out.ctypes.data, None, 0, None, None)
+    else:
+        idx = np.ascontiguousarray(index, dtype=np.int32)
+        if idx.ndim != 1:
+            raise ValueError("index must be 1-D")
+        out = np.full((idx.shape[0], 3), np.nan, np.float32)
+        if rows * cols == 0 or idx.shape[0] == 0:
+            return out
+        rc = L.bicos_normals_host(None, d.ctypes.data, _get_cv_type(d.dtype), rows, cols, q,
+                                  flags, r, diff, m, None, idx.ctypes.data, idx.shape[0],
+                                  out.ctypes.data, None)
+    if rc != 0:
+        raise RuntimeError("BICOS normals failed: " +
+                           L.bicos_last_error().decode(errors="replace"))
+    return out
+
+
 def filter_speckles(disparity, max_size, max_diff=1.0, sentinel=True):
     """An extension (the reference has no such step; cv2.filterSpeckles is the CPU
     counterpart): removes from a disparity map of match() -- int16 or float32, [rows, cols] --
