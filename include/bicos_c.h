@@ -658,6 +658,73 @@ int bicos_normals_host(bicos_engine* e, const void* disparity, int disp_type, in
 /* The tile (rows, cols) of the dense map one workgroup stages (tests). Returns BICOS_OK. */
 int bicos_normals_tile(int* rows, int* cols);
 
+/* -------------------------------------------------------------------- mesh */
+/* A dense rows x cols disparity map triangulated on the GPU. The map is an organised grid, so
+ * every 2x2 block of pixels is a quad of at most two triangles and no neighbour search is
+ * needed. The reference has no such step.
+ * Inputs: the map, BICOS_CV_16S or BICOS_CV_32F; Q, 16 doubles, row-major; flags,
+ * BICOS_MESH_ALLOW_NEGATIVE_Z and BICOS_MESH_F32_SENTINEL with the values and meanings of the
+ * BICOS_REPROJECT_* flags; max_diff, a float >= 0 and not NaN (+inf is legal).
+ * Vertices: exactly the ordered point list of bicos_reproject_* for the same map, Q and flags:
+ *     the kept points in row-major pixel order, the same optional index, the same counts[4] =
+ *     {kept, invalid, nonfinite, negative_z}. Vertex number v is position v in that list. Kept
+ *     points that no triangle uses stay in the list, so normals[i] of bicos_normals_* with the
+ *     same index is the normal of vertex i.
+ * Link: two pixels p, q are linked iff fabsf((float)d_p - (float)d_q) <= max_diff, with one
+ *     float32 subtraction: the speckle filter's link. It is only ever evaluated between kept
+ *     pixels, so both values are finite numbers.
+ * Quads: one for every (r, c) with 0 <= r < rows-1 and 0 <= c < cols-1, with the corners
+ *     A = (r, c), B = (r, c+1), C = (r+1, c), D = (r+1, c+1). Its candidate triangles:
+ *         kept corners   condition                                        T0         T1
+ *         all four       fabsf((float)dA-(float)dD) <= fabsf((float)dB-(float)dC)
+ *                        (diagonal AD; a tie takes AD)                    (A,C,D)    (A,D,B)
+ *         all four       otherwise (diagonal BC)                          (A,C,B)    (B,C,D)
+ *         three, D missing                                                (A,C,B)    -
+ *         three, A missing                                                (B,C,D)    -
+ *         three, B missing                                                (A,C,D)    -
+ *         three, C missing                                                (A,D,B)    -
+ *         fewer than three                                                none       none
+ *     A candidate is emitted iff all three of its edges are linked. Every triangle therefore
+ *     turns the same way in the image: with x to the right and y down, (p1-p0) x (p2-p0) has a
+ *     negative z.
+ * Outputs:
+ *     points, index, counts   the vertices, as bicos_reproject_* writes them; vertex_capacity
+ *                 behaves as its capacity does. index may be NULL.
+ *     triangles   int32 [tri_capacity][3]: the vertex numbers of each triangle's corners in the
+ *                 order written above. Quads come in row-major order, and within a quad T0 comes
+ *                 before T1. Integers only: the output is deterministic. With more triangles
+ *                 than tri_capacity the first tri_capacity are written and nothing past them.
+ *     mesh_counts uint32[4] = {triangles, quads with 2 triangles, quads with 1, quads with 0}.
+ *                 The last three sum to (rows-1)*(cols-1), which is 0 when rows < 2 or cols < 2;
+ *                 the first is 2*q2 + q1, the full number whatever tri_capacity is.
+ *     vertex_map  optional, int32 [rows][cols]: the pixel's vertex number, or -1 where the pixel
+ *                 is not kept. When given, the stage uses it as its rank array; otherwise that
+ *                 array lives in the engine's workspace (as the speckle filter's labels do).
+ *     Triangle entries and vertex_map always use the numbering of the full list, also when
+ *     kept > vertex_capacity; the caller sees that in counts[0].
+ * rows*cols must fit int32. rows == 0 or cols == 0 is legal: all counts are zero and nothing is
+ * launched. rows == 1 or cols == 1 gives vertices and no triangles.
+ * Argument errors are BICOS_E_ARG before any HIP call, and bicos_last_error says which: a type
+ * other than 16S / 32F; unknown flag bits; a negative or NaN max_diff; a negative size; too many
+ * pixels for int32; a NULL map, Q, points, triangles, counts or mesh_counts on a non-empty map; a
+ * NULL engine on the device entry; any output overlapping the map or another output. */
+#define BICOS_MESH_ALLOW_NEGATIVE_Z 1
+#define BICOS_MESH_F32_SENTINEL 2
+/* device: asynchronous on `stream`; e is required (workspace). */
+int bicos_mesh_device(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                      const double Q[16], int flags, float max_diff, float* points, int32_t* index,
+                      size_t vertex_capacity, uint32_t* counts, int32_t* triangles,
+                      size_t tri_capacity, uint32_t* mesh_counts, int32_t* vertex_map, void* stream);
+/* host buffers, synchronous, e NULL = default engine: uploads the map, runs the same launches,
+ * downloads the counts first, then only the first min(kept, vertex_capacity) points and
+ * min(triangles, tri_capacity) triangles (and vertex_map whole, where given). */
+int bicos_mesh_host(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                    const double Q[16], int flags, float max_diff, float* points, int32_t* index,
+                    size_t vertex_capacity, uint32_t counts[4], int32_t* triangles,
+                    size_t tri_capacity, uint32_t mesh_counts[4], int32_t* vertex_map);
+/* Pixels per segment of the mesh's launches: bicos_reproject_segment's (tests). */
+int bicos_mesh_segment(void);
+
 /* --------------------------------------------------------- disparity guide */
 /* The search restricted to one disparity window PER LEFT PIXEL, from a prior: the previous
  * frame's map of a continuous scan, the match of a downsampled stack, a CAD pose, a

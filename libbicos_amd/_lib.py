@@ -68,6 +68,7 @@ EXPORTS = (
     "bicos_rectify_host", "bicos_rectify_tile",
     "bicos_median_device", "bicos_median_host", "bicos_median_tile",
     "bicos_normals_device", "bicos_normals_host", "bicos_normals_tile",
+    "bicos_mesh_device", "bicos_mesh_host", "bicos_mesh_segment",
     "bicos_search_device_guided", "bicos_match_device_guided", "bicos_match_host_guided",
     "bicos_guide_device", "bicos_guide_host",
     "bicos_pool_device", "bicos_pool_host", "bicos_pool_tile", "bicos_pool_kernel",
@@ -97,6 +98,10 @@ MEDIAN_F32_SENTINEL = 1
 NORMALS_ALLOW_NEGATIVE_Z = 1
 NORMALS_F32_SENTINEL = 2
 NORMALS_MAX_RADIUS = 4
+
+# bicos_mesh_* flags (include/bicos_c.h): the values of the bicos_reproject_* flags
+MESH_ALLOW_NEGATIVE_Z = 1
+MESH_F32_SENTINEL = 2
 
 # bicos_guide_* flag (include/bicos_c.h)
 GUIDE_F32_SENTINEL = 1
@@ -239,6 +244,12 @@ def lib() -> ctypes.CDLL:
     L.bicos_normals_host.restype = I
     L.bicos_normals_tile.argtypes = [PI, PI]
     L.bicos_normals_tile.restype = I
+    L.bicos_mesh_device.argtypes = [P, P, I, I, I, PD, I, F, P, P, Z, P, P, Z, P, P, P]
+    L.bicos_mesh_device.restype = I
+    L.bicos_mesh_host.argtypes = [P, P, I, I, I, PD, I, F, P, P, Z, P, P, Z, P, P]
+    L.bicos_mesh_host.restype = I
+    L.bicos_mesh_segment.argtypes = []
+    L.bicos_mesh_segment.restype = I
     L.bicos_search_device_guided.argtypes = [P, P, P, I, I, I, I, I, I, I, P, Z, P, P]
     L.bicos_search_device_guided.restype = I
     L.bicos_match_device_guided.argtypes = [P, P, P, I, I, I, Z, Z, I,
@@ -453,6 +464,28 @@ def median_tile():
 def normals_flags(allow_negative_z: bool, sentinel: bool) -> int:
     return (NORMALS_ALLOW_NEGATIVE_Z if allow_negative_z else 0) | \
         (NORMALS_F32_SENTINEL if sentinel else 0)
+
+
+def mesh_flags(allow_negative_z: bool, sentinel: bool) -> int:
+    return (MESH_ALLOW_NEGATIVE_Z if allow_negative_z else 0) | \
+        (MESH_F32_SENTINEL if sentinel else 0)
+
+
+def mesh_max_diff(max_diff) -> float:
+    """float max_diff as the bicos_mesh_* entries take it (ValueError for what they would
+    refuse: a negative or NaN value, or no number at all)."""
+    try:
+        diff = float(max_diff)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("max_diff must be a number, got %r" % (max_diff,))
+    if not diff >= 0:
+        raise ValueError("max_diff must be >= 0 and not NaN, got %r" % (max_diff,))
+    return diff
+
+
+def mesh_quads(rows: int, cols: int) -> int:
+    """(rows - 1) * (cols - 1): the quads of a map, 0 without a second row or column"""
+    return 0 if rows < 2 or cols < 2 else (rows - 1) * (cols - 1)
 
 
 def normals_params(radius, max_diff, min_points):

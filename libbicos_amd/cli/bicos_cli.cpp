@@ -7,7 +7,7 @@
 //             [-q Q.yml] [--allow-negative-z] [-m MAXDIFF] [--double] [--limited]
 //             [--corrmap] [--no-dupes] [-h]
 // and, beyond the reference: --speckle-size / --speckle-diff, --median / --median-fill,
-// --rectify, --normals / --normals-diff / --normals-min (see USAGE below).
+// --rectify, --normals / --normals-diff / --normals-min, --mesh / --mesh-diff (see USAGE below).
 //
 // Same options, defaults and semantics as the reference (FULL transform unless --limited;
 // --threshold <= 0 disables the NXC filter; --corrmap without a threshold computes with
@@ -72,6 +72,12 @@ const char* USAGE =
     "                          centre's (1; only with --normals)\n"
     "      --normals-min M     least number of window pixels for a normal (3; only with\n"
     "                          --normals)\n"
+    "      --mesh              with a Q matrix: also triangulate the disparity map and write\n"
+    "                          <out>.ply beside the .xyz (binary little-endian): its vertices\n"
+    "                          are the .xyz points, and every 2x2 block of pixels gives at most\n"
+    "                          two triangles\n"
+    "      --mesh-diff F       a triangle's edge may join disparities that differ by at most F\n"
+    "                          (1; only with --mesh)\n"
     "      --rectify FILE      the inputs are raw frames: OpenCV FileStorage (YAML/XML) with\n"
     "                          the matrices M1 D1 R1 P1 M2 D2 R2 P2 of cv::stereoRectify;\n"
     "                          both stacks are rectified to their own size before the match.\n"
@@ -100,7 +106,7 @@ Args parse(int argc, char** argv) {
         {"allow-negative-z", false}, {"double", false}, {"limited", false},
         {"corrmap", false}, {"no-dupes", false}, {"speckle-size", true}, {"speckle-diff", true},
         {"rectify", true}, {"median", true}, {"median-fill", true}, {"normals", true},
-        {"normals-diff", true}, {"normals-min", true}};
+        {"normals-diff", true}, {"normals-min", true}, {"mesh", false}, {"mesh-diff", true}};
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i];
@@ -323,10 +329,32 @@ int run(int argc, char** argv) {
         std::vector<int32_t> index(with_normals ? pixels + 1 : 0);
         uint32_t counts[4] = {0, 0, 0, 0};  // kept, invalid, nonfinite, negative_z
         const int flags = args.has("allow-negative-z") ? BICOS_REPROJECT_ALLOW_NEGATIVE_Z : 0;
-        if (bicos_reproject_host(nullptr, disp.data(), disp.type(), disp.rows(), disp.cols(),
-                                 Q.data(), flags, nullptr, points.data(),
-                                 with_normals ? index.data() : nullptr, pixels, counts) != BICOS_OK)
+        if (args.has("mesh")) {
+            // the mesh's vertices are the reprojection's list (same flags: the two flag sets
+            // share their values), so this one call gives the points, the index and the faces
+            const float max_diff = args.has("mesh-diff") ? as_float(args, "mesh-diff") : 1.0f;
+            const size_t quads = disp.rows() < 2 || disp.cols() < 2
+                                     ? 0
+                                     : (size_t)(disp.rows() - 1) * (disp.cols() - 1);
+            std::vector<int32_t> triangles(3 * 2 * quads + 1);
+            uint32_t mesh_counts[4] = {0, 0, 0, 0};  // triangles, quads with 2, 1, 0
+            if (bicos_mesh_host(nullptr, disp.data(), disp.type(), disp.rows(), disp.cols(),
+                                Q.data(), flags, max_diff, points.data(),
+                                with_normals ? index.data() : nullptr, pixels, counts,
+                                triangles.data(), 2 * quads, mesh_counts, nullptr) != BICOS_OK)
+                throw std::runtime_error(std::string("mesh failed: ") + bicos_last_error());
+            fs::path ply = outfile;
+            ply.replace_extension("ply");
+            bicos_cli::write_ply(ply.string(), points.data(), counts[0], triangles.data(),
+                                 mesh_counts[0]);
+            std::cout << "Saved mesh (" << counts[0] << " vertices, " << mesh_counts[0]
+                      << " triangles) to\t" << ply << std::endl;
+        } else if (bicos_reproject_host(nullptr, disp.data(), disp.type(), disp.rows(),
+                                        disp.cols(), Q.data(), flags, nullptr, points.data(),
+                                        with_normals ? index.data() : nullptr, pixels,
+                                        counts) != BICOS_OK) {
             throw std::runtime_error(std::string("reprojection failed: ") + bicos_last_error());
+        }
         if (with_normals) {
             // one normal per point of the list, on the same map with the same flags (the two
             // flag sets share their values)
@@ -353,11 +381,13 @@ int run(int argc, char** argv) {
         if (counts[3]) std::cerr << "Skipped " << counts[3] << " points with negative Z values" << std::endl;
     }
     if (!q_store)
-        for (const char* k : {"normals", "normals-diff", "normals-min"})
+        for (const char* k : {"normals", "normals-diff", "normals-min", "mesh", "mesh-diff"})
             if (args.has(k)) std::cerr << "'" << k << "' has no effect without a Q matrix.\n";
     if (q_store && !args.has("normals"))
         for (const char* k : {"normals-diff", "normals-min"})
             if (args.has(k)) std::cerr << "'" << k << "' has no effect without 'normals'.\n";
+    if (q_store && !args.has("mesh") && args.has("mesh-diff"))
+        std::cerr << "'mesh-diff' has no effect without 'mesh'.\n";
     return 0;
 }
 

@@ -485,6 +485,29 @@ void write_xyz_points_normals(const std::string& path, const float* points, cons
     }
 }
 
+void write_ply(const std::string& path, const float* points, size_t vertices,
+               const int32_t* triangles, size_t faces) {
+    std::ofstream ply(path, std::ios::binary);
+    if (!ply) throw std::runtime_error("cannot write " + path);
+    ply << "ply\nformat binary_little_endian 1.0\ncomment bicos-cli\n"
+        << "element vertex " << vertices << "\nproperty float x\nproperty float y\n"
+        << "property float z\nelement face " << faces
+        << "\nproperty list uchar int vertex_indices\nend_header\n";
+    // (the hosts of this engine are little-endian: the records are the arrays' own bytes)
+    ply.write((const char*)points, (std::streamsize)(vertices * 3 * sizeof(float)));
+    std::vector<char> rec(13 * std::min<size_t>(faces, 4096));
+    for (size_t f = 0; f < faces;) {
+        const size_t n = std::min<size_t>(faces - f, 4096);
+        for (size_t i = 0; i < n; ++i) {
+            rec[13 * i] = 3;
+            std::memcpy(&rec[13 * i + 1], triangles + 3 * (f + i), 12);
+        }
+        ply.write(rec.data(), (std::streamsize)(13 * n));
+        f += n;
+    }
+    if (!ply) throw std::runtime_error("cannot write " + path);
+}
+
 void read_stacks(const std::string& folder0, const std::optional<std::string>& folder1,
                  std::vector<Gray>& left, std::vector<Gray>& right) {
     namespace fs = std::filesystem;

@@ -79,6 +79,12 @@ void write_xyz_points(const std::string& path, const float* points, size_t count
 // ... with a normal per point: "X Y Z NX NY NZ", and "0 0 0" where normals[i] is three NaNs
 void write_xyz_points_normals(const std::string& path, const float* points, const float* normals,
                               size_t count);
+// A binary little-endian .ply: the header lines ply / format binary_little_endian 1.0 / comment
+// bicos-cli / element vertex N / property float x, y, z / element face M / property list uchar
+// int vertex_indices / end_header, then N records of three float32 and M records of the byte 3
+// and three int32 (bicos_mesh_host's points and triangles).
+void write_ply(const std::string& path, const float* points, size_t vertices,
+               const int32_t* triangles, size_t faces);
 
 // reference read_sequence + sort_sequence_to_stack (src/fileutils.cpp:60-154): with two
 // folders, files named <idx>.<ext> in each (16-bit kept); with one, <idx>_left.<ext> and

@@ -7,6 +7,7 @@
 //   BICOS::rectify_maps, BICOS::rectify  (bicos/rectify.hpp; no reference counterpart)
 //   BICOS::median_filter  (bicos/median.hpp; no reference counterpart)
 //   BICOS::normals  (bicos/normals.hpp; no reference counterpart)
+//   BICOS::mesh  (bicos/mesh.hpp; likewise)
 //   BICOS::guide_from_disparity, the guided BICOS::match  (bicos/guide.hpp; likewise)
 //   BICOS::pool_stack, BICOS::match_pyramid  (bicos/pool.hpp; likewise)
 #include "engine.hpp"
@@ -25,6 +26,7 @@
 #include "../../include/bicos/rectify.hpp"
 #include "../../include/bicos/median.hpp"
 #include "../../include/bicos/normals.hpp"
+#include "../../include/bicos/mesh.hpp"
 #include "../../include/bicos/guide.hpp"
 #include "../../include/bicos/pool.hpp"
 
@@ -594,6 +596,94 @@ NormalStats normals(const Image& disparity, const Matx44d& Q, const std::vector<
     list.resize(3 * count);
     normals_out.swap(list);
     return NormalStats{counts[0], counts[1], counts[2], counts[3]};
+}
+
+// --------------------------------------------------------------------- BICOS::mesh
+// over the C entries (entries.cpp), which validate, lock the engine and launch
+
+namespace {
+
+void check_mesh_map(const Image& disparity) {
+    if (disparity.type() != S16 && disparity.type() != F32)
+        throw Exception("mesh: the disparity map must be S16 or F32");
+    if (disparity.step() != (size_t)disparity.cols() * disparity.elemSize() && disparity.rows() > 1)
+        throw Exception("mesh: the disparity map must be dense");
+}
+
+}  // namespace
+
+void mesh(const Image& disparity, const Matx44d& Q, float* points, int32_t* index,
+          size_t vertex_capacity, uint32_t* counts, int32_t* triangles, size_t tri_capacity,
+          uint32_t* mesh_counts, float max_diff, int flags, int32_t* vertex_map,
+          hipStream_t stream) {
+    check_mesh_map(disparity);
+    if (disparity.memory() != Memory::Device)
+        throw Exception("mesh: device buffers need a device map");
+    throw_rc(bicos_mesh_device(current_engine(), disparity.data(), disparity.type(),
+                               disparity.rows(), disparity.cols(), Q.data(), flags, max_diff,
+                               points, index, vertex_capacity, counts, triangles, tri_capacity,
+                               mesh_counts, vertex_map, stream));
+}
+
+MeshStats mesh(const Image& disparity, const Matx44d& Q, std::vector<float>& points,
+               std::vector<int32_t>& triangles, float max_diff, int flags,
+               std::vector<int32_t>* index) {
+    check_mesh_map(disparity);
+    const int rows = disparity.rows(), cols = disparity.cols();
+    const size_t pixels = (size_t)(rows > 0 ? rows : 0) * (size_t)(cols > 0 ? cols : 0);
+    const size_t tris = rows < 2 || cols < 2 ? 0 : 2 * (size_t)(rows - 1) * (size_t)(cols - 1);
+    uint32_t counts[4] = {0, 0, 0, 0}, mesh_counts[4] = {0, 0, 0, 0};
+    if (disparity.memory() == Memory::Host) {
+        points.resize(3 * pixels + 1);  // (+1: never a null pointer)
+        triangles.resize(3 * tris + 1);
+        if (index) index->resize(pixels + 1);
+        throw_rc(bicos_mesh_host(nullptr, disparity.data(), disparity.type(), rows, cols, Q.data(),
+                                 flags, max_diff, points.data(), index ? index->data() : nullptr,
+                                 pixels, counts, triangles.data(), tris, mesh_counts, nullptr));
+    } else {
+        // device buffers for every pixel and quad, then only what was kept and emitted comes
+        // down: counts | mesh_counts | points | triangles | index in one allocation
+        const size_t words = 8 + 3 * pixels + 3 * tris + (index ? pixels : 0);
+        void* raw = nullptr;
+        throw_rc(check_hip(hipMalloc(&raw, words * 4), "hipMalloc(mesh)"));
+        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
+        uint32_t* d_counts = (uint32_t*)raw;
+        float* d_points = (float*)raw + 8;
+        int32_t* d_tris = (int32_t*)raw + 8 + 3 * pixels;
+        int32_t* d_index = index ? d_tris + 3 * tris : nullptr;
+        // (a map without pixels launches nothing and needs no buffers: the entry zeroes the counts)
+        throw_rc(bicos_mesh_device(current_engine(), disparity.data(), disparity.type(), rows,
+                                   cols, Q.data(), flags, max_diff, d_points, d_index, pixels,
+                                   d_counts, d_tris, tris, d_counts + 4, nullptr, nullptr));
+        uint32_t both[8];
+        throw_rc(check_hip(hipMemcpy(both, d_counts, sizeof both, hipMemcpyDeviceToHost),
+                           "counts download"));
+        std::copy(both, both + 4, counts);
+        std::copy(both + 4, both + 8, mesh_counts);
+        points.resize(3 * (size_t)counts[0]);
+        triangles.resize(3 * (size_t)mesh_counts[0]);
+        if (index) index->resize(counts[0]);
+        if (counts[0])
+            throw_rc(check_hip(hipMemcpy(points.data(), d_points, points.size() * sizeof(float),
+                                         hipMemcpyDeviceToHost), "points download"));
+        if (counts[0] && index)
+            throw_rc(check_hip(hipMemcpy(index->data(), d_index, index->size() * sizeof(int32_t),
+                                         hipMemcpyDeviceToHost), "index download"));
+        if (mesh_counts[0])
+            throw_rc(check_hip(hipMemcpy(triangles.data(), d_tris,
+                                         triangles.size() * sizeof(int32_t),
+                                         hipMemcpyDeviceToHost), "triangles download"));
+    }
+    points.resize(3 * (size_t)counts[0]);
+    triangles.resize(3 * (size_t)mesh_counts[0]);
+    if (index) index->resize(counts[0]);
+    MeshStats s;
+    s.vertices = ReprojectStats{counts[0], counts[1], counts[2], counts[3]};
+    s.triangles = mesh_counts[0];
+    s.quads_full = mesh_counts[1];
+    s.quads_half = mesh_counts[2];
+    s.quads_empty = mesh_counts[3];
+    return s;
 }
 
 // ------------------------------------------------------ BICOS::guide_from_disparity

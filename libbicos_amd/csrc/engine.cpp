@@ -9,6 +9,7 @@
 #include "speckle.hpp"
 #include "median.hpp"
 #include "normals.hpp"
+#include "mesh.hpp"
 #include "guide.hpp"
 #include "pool.hpp"
 
@@ -814,6 +815,101 @@ int normals_device(const NormalsJob& j, hipStream_t st) {
     if (j.normals && j.count > 0)
         return check_hip(bicos_hip::launch_normals_list(a, f32, st), "normals list launch");
     return BICOS_OK;
+}
+
+// ---------------------------------------------------------------------- mesh
+
+namespace {
+// quads of a rows x cols map: (rows-1) * (cols-1), 0 for a map without a second row or column
+size_t mesh_quads(int rows, int cols) {
+    return rows < 2 || cols < 2 ? 0 : (size_t)(rows - 1) * (size_t)(cols - 1);
+}
+}  // namespace
+
+int check_mesh(const MeshJob& j, const bicos_engine* e, bool needs_engine) {
+    if (j.disp_type != BICOS_CV_16S && j.disp_type != BICOS_CV_32F)
+        return fail(BICOS_E_ARG, "mesh: the disparity map must be CV_16S or CV_32F");
+    if (j.flags & ~(BICOS_MESH_ALLOW_NEGATIVE_Z | BICOS_MESH_F32_SENTINEL))
+        return fail(BICOS_E_ARG, "mesh: unknown flag bits");
+    if (!(j.max_diff >= 0.0f)) return fail(BICOS_E_ARG, "mesh: max_diff must be >= 0 and not NaN");
+    if (j.rows < 0 || j.cols < 0) return fail(BICOS_E_ARG, "mesh: negative image size");
+    if ((int64_t)j.rows * j.cols > INT32_MAX)
+        return fail(BICOS_E_ARG, "mesh: rows * cols exceeds int32");
+    if (needs_engine && !e) return fail(BICOS_E_ARG, "mesh: null engine (workspace)");
+    if (j.rows == 0 || j.cols == 0) return BICOS_OK;
+    if (!j.disp) return fail(BICOS_E_ARG, "mesh: null disparity map");
+    if (!j.Q) return fail(BICOS_E_ARG, "mesh: null Q");
+    if (!j.points) return fail(BICOS_E_ARG, "mesh: null points");
+    if (!j.triangles) return fail(BICOS_E_ARG, "mesh: null triangles");
+    if (!j.counts) return fail(BICOS_E_ARG, "mesh: null counts");
+    if (!j.mesh_counts) return fail(BICOS_E_ARG, "mesh: null mesh_counts");
+    // the map, then every output with the bytes the call may write
+    const uintptr_t pixels = (uintptr_t)j.rows * j.cols;
+    const uintptr_t verts = (uintptr_t)std::min<size_t>(j.vertex_capacity, pixels);
+    const uintptr_t tris =
+        (uintptr_t)std::min<size_t>(j.tri_capacity, 2 * mesh_quads(j.rows, j.cols));
+    const struct {
+        const void* p;
+        uintptr_t bytes;
+        const char* name;
+    } span[] = {{j.disp, pixels * (j.disp_type == BICOS_CV_32F ? 4 : 2), "the map"},
+                {j.points, verts * 12, "points"},
+                {j.index, verts * 4, "index"},
+                {j.counts, 16, "counts"},
+                {j.triangles, tris * 12, "triangles"},
+                {j.mesh_counts, 16, "mesh_counts"},
+                {j.vertex_map, pixels * 4, "vertex_map"}};
+    const int n = (int)(sizeof span / sizeof span[0]);
+    for (int i = 1; i < n; ++i)
+        for (int k = 0; k < i; ++k) {
+            const uintptr_t a = (uintptr_t)span[i].p, b = (uintptr_t)span[k].p;
+            if (a && b && span[i].bytes && span[k].bytes && a < b + span[k].bytes &&
+                b < a + span[i].bytes)
+                return fail(BICOS_E_ARG, std::string("mesh: ") + span[i].name + " overlaps " +
+                                             span[k].name);
+        }
+    return BICOS_OK;
+}
+
+int mesh_device(bicos_engine* e, const MeshJob& j, hipStream_t st) {
+    const uint32_t pixels = (uint32_t)j.rows * (uint32_t)j.cols;
+    if (pixels == 0) {  // nothing to launch: the counts are all zero
+        if (j.counts)
+            if (int rc = check_hip(hipMemsetAsync(j.counts, 0, 4 * sizeof(uint32_t), st),
+                                   "hipMemsetAsync(counts)"))
+                return rc;
+        return j.mesh_counts ? check_hip(hipMemsetAsync(j.mesh_counts, 0, 4 * sizeof(uint32_t), st),
+                                         "hipMemsetAsync(mesh_counts)")
+                             : (int)BICOS_OK;
+    }
+    bicos_hip::MeshArgs a{};
+    a.v.disp = j.disp;
+    a.v.cols = j.cols;
+    a.v.pixels = pixels;
+    a.v.flags = j.flags;  // (the BICOS_MESH_* flags are the BICOS_REPROJECT_* flags)
+    std::copy(j.Q, j.Q + 16, a.v.Q.q);
+    a.v.points = j.points;
+    a.v.index = j.index;
+    a.v.capacity = (uint32_t)std::min<size_t>(j.vertex_capacity, pixels);
+    a.v.counts = j.counts;
+    a.rows = j.rows;
+    a.max_diff = j.max_diff;
+    a.triangles = j.triangles;
+    a.tri_capacity = (uint32_t)std::min<size_t>(j.tri_capacity, 2 * mesh_quads(j.rows, j.cols));
+    a.mesh_counts = j.mesh_counts;
+    const uint32_t segments = bicos_hip::reproject_segments(pixels);
+    Lease ws(e, e->ws, e->ws_bytes, st);
+    auto carve = [&] {
+        a.v.seg_counts = ws.take<uint32_t>((size_t)segments * 4);
+        a.v.seg_offsets = ws.take<uint32_t>(segments);
+        a.tri_counts = ws.take<uint32_t>((size_t)segments * 4);
+        a.tri_offsets = ws.take<uint32_t>(segments);
+        a.rank = j.vertex_map ? j.vertex_map : ws.take<int32_t>(pixels);
+    };
+    carve();
+    if (int rc = ws.acquire()) return rc;
+    carve();
+    return check_hip(bicos_hip::launch_mesh(a, j.disp_type == BICOS_CV_32F, st), "mesh launches");
 }
 
 // ------------------------------------------------------------ disparity guide

@@ -9,16 +9,17 @@
 //               speckle_device (the speckle filter of a disparity map); rectify_device and
 //               rectify_maps_device (raw stacks -> rectified stacks); median_device (the
 //               median filter of a disparity map); normals_device (a disparity map -> unit
-//               surface normals); guide_device (a prior disparity map ->
+//               surface normals); mesh_device (a disparity map -> a triangle mesh over the
+//               reprojection's point list); guide_device (a prior disparity map ->
 //               per-pixel search windows); pool_device (a stack pooled by an integer factor);
 //               match_pyramid_device (pool, coarse ranged match, guide, guided match)
 //   host.cpp    the banded host-buffer pipeline (HostPool, match_host); reproject_host;
 //               speckle_host; rectify_host, rectify_maps_host; median_host; normals_host;
-//               guide_host; pool_host; match_pyramid_host
+//               mesh_host; guide_host; pool_host; match_pyramid_host
 //   entries.cpp the bicos_* extern "C" entries (bicos_c.h) but the multi-GPU ones
 //   multi.cpp   bicos_match_host_multi, bicos_match_bands_device
 //   cxxapi.cpp  namespace BICOS (HipImage, match, reproject, filter_speckles, median_filter,
-//               normals, guide_from_disparity, pool_stack, match_pyramid)
+//               normals, mesh, guide_from_disparity, pool_stack, match_pyramid)
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -469,6 +470,34 @@ int normals_device(const NormalsJob& j, hipStream_t st);
 // the engine's own stream, the map, the list and the counts downloaded as asked. Synchronous.
 // rows * cols > 0 (bicos_normals_host answers an empty map itself, without an engine).
 int normals_host(bicos_engine* e, const NormalsJob& j);
+
+// One triangulation (bicos_c.h "mesh"): the arguments of bicos_mesh_device / bicos_mesh_host,
+// the pointers all in device or all in host memory.
+struct MeshJob {
+    const void* disp;
+    int disp_type, rows, cols;
+    const double* Q;
+    int flags;
+    float max_diff;
+    float* points;
+    int32_t* index;
+    size_t vertex_capacity;
+    uint32_t* counts;
+    int32_t* triangles;
+    size_t tri_capacity;
+    uint32_t* mesh_counts;
+    int32_t* vertex_map;
+};
+// BICOS_E_ARG (with a message) for what the entries refuse; no HIP call. needs_engine: a NULL
+// engine is an error (the device entry; the host entry has a default engine).
+int check_mesh(const MeshJob& j, const bicos_engine* e, bool needs_engine);
+// The six launches on `st` (validated arguments), with the segment counts and (unless
+// j.vertex_map is given) the rank array in the engine's workspace.
+int mesh_device(bicos_engine* e, const MeshJob& j, hipStream_t st);
+// Host buffers: the map uploaded into the engine's staging, the same launches on the engine's
+// own stream, both counts downloaded and then min(kept, vertex_capacity) points and
+// min(triangles, tri_capacity) triangles. Synchronous.
+int mesh_host(bicos_engine* e, const MeshJob& j);
 
 // One remap of a stack (bicos_c.h "rectification"): the arguments of bicos_rectify_device, the
 // pointers all in device memory, the stack pitches in elements, map_pitch in bytes (0 = dense).

@@ -469,6 +469,47 @@ int bicos_reproject_host(bicos_engine* e, const void* disparity, int disp_type, 
 
 int bicos_reproject_segment(void) { return bicos_hip::REPROJECT_SEGMENT; }
 
+int bicos_mesh_device(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                      const double Q[16], int flags, float max_diff, float* points, int32_t* index,
+                      size_t vertex_capacity, uint32_t* counts, int32_t* triangles,
+                      size_t tri_capacity, uint32_t* mesh_counts, int32_t* vertex_map,
+                      void* stream) {
+    const MeshJob job{disparity, disp_type, rows, cols, Q, flags, max_diff, points, index,
+                      vertex_capacity, counts, triangles, tri_capacity, mesh_counts, vertex_map};
+    if (int rc0 = check_mesh(job, e, true)) return rc0;
+    return guarded([&]() -> int {
+        std::lock_guard<std::mutex> g(e->lock);
+        return mesh_device(e, job, (hipStream_t)stream);
+    });
+}
+
+int bicos_mesh_host(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
+                    const double Q[16], int flags, float max_diff, float* points, int32_t* index,
+                    size_t vertex_capacity, uint32_t counts[4], int32_t* triangles,
+                    size_t tri_capacity, uint32_t mesh_counts[4], int32_t* vertex_map) {
+    const MeshJob job{disparity, disp_type, rows, cols, Q, flags, max_diff, points, index,
+                      vertex_capacity, counts, triangles, tri_capacity, mesh_counts, vertex_map};
+    if (int rc0 = check_mesh(job, e, false)) return rc0;
+    if (rows == 0 || cols == 0) {  // all counts zero, without an engine or a HIP call
+        if (counts) std::fill(counts, counts + 4, 0u);
+        if (mesh_counts) std::fill(mesh_counts, mesh_counts + 4, 0u);
+        return BICOS_OK;
+    }
+    return guarded([&]() -> int {
+        if (!e) {
+            int dev = 0;
+            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
+            if (rc) return rc;
+            e = default_engine(dev);
+            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        }
+        std::lock_guard<std::mutex> g(e->lock);
+        return mesh_host(e, job);
+    });
+}
+
+int bicos_mesh_segment(void) { return bicos_hip::REPROJECT_SEGMENT; }
+
 int bicos_speckle_device(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
                          int max_size, float max_diff, int flags, void* out, int32_t* labels,
                          uint32_t* counts, void* stream) {

@@ -441,6 +441,65 @@ int reproject_host(bicos_engine* e, const ReprojectJob& j) {
     return rc ? rc : rc2;
 }
 
+int mesh_host(bicos_engine* e, const MeshJob& j) {
+    if (!e) return fail(BICOS_E_ARG, "null engine");
+    if (int rc0 = check_mesh(j, e, false)) return rc0;
+    const size_t pixels = (size_t)j.rows * j.cols;
+    if (pixels == 0) {
+        if (j.counts) std::fill(j.counts, j.counts + 4, 0u);
+        if (j.mesh_counts) std::fill(j.mesh_counts, j.mesh_counts + 4, 0u);
+        return BICOS_OK;
+    }
+    hipStream_t st = e->own_stream;
+    const size_t esz = j.disp_type == BICOS_CV_32F ? 4 : 2;
+    const size_t quads = j.rows < 2 || j.cols < 2 ? 0 : (size_t)(j.rows - 1) * (j.cols - 1);
+    const size_t vcap = std::min(j.vertex_capacity, pixels);
+    const size_t tcap = std::min(j.tri_capacity, 2 * quads);
+    MeshJob d = j;  // the same job on staged device buffers
+    Lease stage(e, e->stage, e->stage_bytes, st);
+    auto carve = [&] {
+        d.disp = stage.take(pixels * esz);
+        d.points = stage.take<float>(3 * vcap + 1);  // (non-null at capacity 0)
+        d.index = j.index ? stage.take<int32_t>(vcap + 1) : nullptr;
+        d.counts = stage.take<uint32_t>(4);
+        d.triangles = stage.take<int32_t>(3 * tcap + 1);
+        d.mesh_counts = stage.take<uint32_t>(4);
+        d.vertex_map = j.vertex_map ? stage.take<int32_t>(pixels) : nullptr;
+    };
+    carve();
+    int rc = stage.acquire();
+    if (rc) return rc;
+    carve();
+    d.vertex_capacity = vcap;
+    d.tri_capacity = tcap;
+    rc = check_hip(hipMemcpyAsync((void*)d.disp, j.disp, pixels * esz, hipMemcpyHostToDevice, st),
+                   "disparity upload");
+    if (!rc) rc = mesh_device(e, d, st);
+    if (!rc)
+        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 4 * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, st), "counts download");
+    if (!rc)
+        rc = check_hip(hipMemcpyAsync(j.mesh_counts, d.mesh_counts, 4 * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, st), "mesh_counts download");
+    if (!rc) rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    const size_t verts = rc ? 0 : std::min<size_t>(j.counts[0], vcap);
+    const size_t tris = rc ? 0 : std::min<size_t>(j.mesh_counts[0], tcap);
+    if (!rc && verts)
+        rc = check_hip(hipMemcpyAsync(j.points, d.points, verts * 3 * sizeof(float),
+                                      hipMemcpyDeviceToHost, st), "points download");
+    if (!rc && verts && j.index)
+        rc = check_hip(hipMemcpyAsync(j.index, d.index, verts * sizeof(int32_t),
+                                      hipMemcpyDeviceToHost, st), "index download");
+    if (!rc && tris)
+        rc = check_hip(hipMemcpyAsync(j.triangles, d.triangles, tris * 3 * sizeof(int32_t),
+                                      hipMemcpyDeviceToHost, st), "triangles download");
+    if (!rc && j.vertex_map)
+        rc = check_hip(hipMemcpyAsync(j.vertex_map, d.vertex_map, pixels * sizeof(int32_t),
+                                      hipMemcpyDeviceToHost, st), "vertex_map download");
+    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
+    return rc ? rc : rc2;
+}
+
 int speckle_host(bicos_engine* e, const SpeckleJob& j) {
     if (!e) return fail(BICOS_E_ARG, "null engine");
     if (int rc0 = check_speckle(j, e, false)) return rc0;

@@ -582,6 +582,74 @@ class Engine:
         _lib.check(rc, "bicos_normals_device")
         return out
 
+    # -------------------------------------------------------------------- mesh
+    def mesh(self, disp: torch.Tensor, Q, *, max_diff: float = 1.0,
+             allow_negative_z: bool = False, sentinel: bool = True, with_index: bool = False,
+             with_vertex_map: bool = False, out_points: Optional[torch.Tensor] = None,
+             out_triangles: Optional[torch.Tensor] = None, stream=None):
+        """bicos_mesh_device: an int16 or float32 disparity map [rows, cols] triangulated;
+        include/bicos_c.h, "mesh". Returns (points[:kept], triangles[:T], index or None,
+        vertex_map or None, stats). The vertices are exactly reproject_points' list for the same
+        map, Q and flags (float32 [kept, 3], with with_index each vertex's pixel row * cols + col,
+        which is what normals_points takes). Every 2x2 block of pixels gives at most two
+        triangles (int32 [T, 3], vertex numbers), split along the diagonal with the smaller
+        disparity step; a triangle is emitted where its corners are kept and every edge joins
+        disparities within max_diff. with_vertex_map: the int32 [rows, cols] map of each pixel's
+        vertex number, -1 where the pixel is not kept. stats = dict(kept, invalid, nonfinite,
+        negative_z, triangles, quads_full, quads_half, quads_empty).
+
+        `out_points`, a float32 [capacity, 3] tensor, and `out_triangles`, an int32
+        [capacity, 3] tensor, receive the results; without them rows * cols points and
+        2 * (rows - 1) * (cols - 1) triangles are allocated. The launches are asynchronous on
+        `stream`, but the call then synchronises that stream ONCE to read the counts. A
+        RuntimeError says so if an out tensor was too small (its rows are then valid up to its
+        capacity)."""
+        rows, cols, typ, q = self._reproject_args(disp, Q)
+        diff = _lib.mesh_max_diff(max_diff)
+        dev = disp.device
+        quads = _lib.mesh_quads(rows, cols)
+        if out_points is None:
+            out_points = torch.empty((rows * cols, 3), dtype=torch.float32, device=dev)
+        if out_points.dim() != 2:
+            raise ValueError("out_points must be [capacity, 3]")
+        vcap = out_points.shape[0]
+        _check_out(out_points, "out_points", (vcap, 3), (torch.float32,), dev)
+        if out_triangles is None:
+            out_triangles = torch.empty((max(2 * quads, 1), 3), dtype=torch.int32, device=dev)
+        if out_triangles.dim() != 2:
+            raise ValueError("out_triangles must be [capacity, 3]")
+        tcap = out_triangles.shape[0]
+        _check_out(out_triangles, "out_triangles", (tcap, 3), (torch.int32,), dev)
+        index = torch.empty((vcap,), dtype=torch.int32, device=dev) if with_index else None
+        vmap = torch.empty((rows, cols), dtype=torch.int32, device=dev) if with_vertex_map else None
+        keys = ("kept", "invalid", "nonfinite", "negative_z", "triangles", "quads_full",
+                "quads_half", "quads_empty")
+        if rows * cols == 0:  # (an empty tensor has no pointer to hand over)
+            return out_points[:0], out_triangles[:0], (index[:0] if with_index else None), vmap, \
+                dict.fromkeys(keys, 0)
+        if vcap == 0 or tcap == 0:
+            raise ValueError("out_points and out_triangles must hold at least one entry")
+        counts = torch.empty((8,), dtype=torch.int32, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream(dev)
+        rc = self._L.bicos_mesh_device(
+            self._h, disp.data_ptr(), typ, rows, cols, q,
+            _lib.mesh_flags(allow_negative_z, sentinel), diff, out_points.data_ptr(),
+            index.data_ptr() if index is not None else None, vcap, counts.data_ptr(),
+            out_triangles.data_ptr(), tcap, counts.data_ptr() + 16,
+            vmap.data_ptr() if vmap is not None else None, s.cuda_stream)
+        _lib.check(rc, "bicos_mesh_device")
+        with torch.cuda.stream(s):
+            host = counts.cpu()  # the one synchronisation
+        stats = dict(zip(keys, (int(v) & 0xFFFFFFFF for v in host.tolist())))
+        kept, tris = stats["kept"], stats["triangles"]
+        if kept > vcap:
+            raise RuntimeError("mesh: out_points holds %d points, %d were kept" % (vcap, kept))
+        if tris > tcap:
+            raise RuntimeError("mesh: out_triangles holds %d triangles, %d were emitted"
+                               % (tcap, tris))
+        return out_points[:kept], out_triangles[:tris], \
+            (index[:kept] if index is not None else None), vmap, stats
+
     # --------------------------------------------------------- disparity guide
     def guide_from_disparity(self, prior: torch.Tensor, radius: int, spread: int = 0,
                              scale: int = 1, fallback: Optional[Tuple[int, int]] = None,

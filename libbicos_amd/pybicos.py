@@ -338,6 +338,37 @@ def normals(disparity, Q, radius=2, max_diff=1.0, min_points=3, allow_negative_z
     return out
 
 
+def mesh(disparity, Q, max_diff=1.0, allow_negative_z=False, sentinel=True):
+    """An extension (the reference has no such step): a disparity map from match() -- int16 or
+    float32, [rows, cols] -- triangulated (bicos_mesh_host, include/bicos_c.h "mesh": on the
+    GPU, exact). Returns (points, triangles): the float32 [kept, 3] points of reproject() with
+    the same flags, and int32 [T, 3] vertex numbers into them. Every 2x2 block of pixels gives
+    at most two triangles, split along the diagonal with the smaller disparity step; a triangle
+    is emitted where its three corners are kept points and every edge joins disparities that
+    differ by at most max_diff."""
+    d = np.ascontiguousarray(disparity)
+    if d.ndim != 2:
+        raise ValueError("disparity map must be 2-D")
+    if d.dtype != np.int16 and d.dtype != np.float32:
+        raise ValueError(f"Unsupported disparity dtype: {d.dtype}")
+    rows, cols = d.shape
+    q = _lib.reproject_q(Q)
+    diff = _lib.mesh_max_diff(max_diff)
+    tcap = 2 * _lib.mesh_quads(rows, cols)
+    points = np.empty((max(rows * cols, 1), 3), np.float32)
+    triangles = np.empty((max(tcap, 1), 3), np.int32)
+    counts = (ctypes.c_uint32 * 4)()
+    mesh_counts = (ctypes.c_uint32 * 4)()
+    L = _lib.lib()
+    rc = L.bicos_mesh_host(None, d.ctypes.data, _get_cv_type(d.dtype), rows, cols, q,
+                           _lib.mesh_flags(allow_negative_z, sentinel), diff, points.ctypes.data,
+                           None, rows * cols, counts, triangles.ctypes.data, tcap, mesh_counts,
+                           None)
+    if rc != 0:
+        raise RuntimeError("BICOS mesh failed: " + L.bicos_last_error().decode(errors="replace"))
+    return points[:counts[0]].copy(), triangles[:mesh_counts[0]].copy()
+
+
 def filter_speckles(disparity, max_size, max_diff=1.0, sentinel=True):
     """An extension (the reference has no such step; cv2.filterSpeckles is the CPU
     counterpart): removes from a disparity map of match() -- int16 or float32, [rows, cols] --
