@@ -317,12 +317,41 @@ static void match_stacks(const std::vector<Image>& stack0, const std::vector<Ima
 
 namespace {
 
-void check_map(const Image& disparity) {
-    if (disparity.type() != S16 && disparity.type() != F32)
-        throw Exception("reproject: the disparity map must be S16 or F32");
-    if (disparity.step() != (size_t)disparity.cols() * disparity.elemSize() && disparity.rows() > 1)
-        throw Exception("reproject: the disparity map must be dense");
+// What every map stage asks of its map, `name` being the function's in the messages: S16 or
+// F32, dense and, where the stage writes an image of `channels` values per pixel, narrow enough
+// for that image's width to fit an int
+void check_map(const std::string& name, const Image& map, int channels = 0,
+               const char* what = "disparity") {
+    if (map.type() != S16 && map.type() != F32)
+        throw Exception(name + ": the " + what + " map must be S16 or F32");
+    if (map.step() != (size_t)map.cols() * map.elemSize() && map.rows() > 1)
+        throw Exception(name + ": the " + what + " map must be dense");
+    if ((int64_t)map.cols() * channels > INT32_MAX) throw Exception(name + ": map too wide");
 }
+
+// One device allocation sliced into counts | a | b (32-bit words each), for the overloads that
+// run a device entry on buffers of their own and bring down the counts, then what they call for
+class DeviceBlock {
+  public:
+    DeviceBlock(const char* what, size_t counts, size_t a = 0, size_t b = 0) : n_(counts), a_(a) {
+        void* raw = nullptr;
+        throw_rc(check_hip(hipMalloc(&raw, (counts + a + b) * 4), what));
+        own_.reset(raw, [](void* q) { (void)hipFree(q); });
+    }
+    uint32_t* counts() const { return (uint32_t*)own_.get(); }
+    template <class T>
+    T* a() const { return (T*)(counts() + n_); }
+    template <class T>
+    T* b() const { return (T*)(counts() + n_ + a_); }
+    void counts_down(uint32_t* host) const { down(host, counts(), n_ * 4, "counts download"); }
+    static void down(void* host, const void* dev, size_t bytes, const char* what) {
+        throw_rc(check_hip(hipMemcpy(host, dev, bytes, hipMemcpyDeviceToHost), what));
+    }
+
+  private:
+    std::shared_ptr<void> own_;
+    size_t n_, a_;
+};
 
 bicos_engine* current_engine() {
     int dev = 0;
@@ -336,9 +365,8 @@ bicos_engine* current_engine() {
 
 void reproject(const Image& disparity, const Matx44d& Q, Image& xyz, int flags,
                hipStream_t stream) {
-    check_map(disparity);
+    check_map("reproject", disparity, 3);
     const int rows = disparity.rows(), cols = disparity.cols();
-    if ((int64_t)cols * 3 > INT32_MAX) throw Exception("reproject: map too wide");
     xyz.create(rows, 3 * cols, F32, disparity.memory());
     if (disparity.memory() == Memory::Host)
         throw_rc(bicos_reproject_host(nullptr, disparity.data(), disparity.type(), rows, cols,
@@ -352,7 +380,7 @@ void reproject(const Image& disparity, const Matx44d& Q, Image& xyz, int flags,
 
 void reproject(const Image& disparity, const Matx44d& Q, float* points, int32_t* index,
                size_t capacity, uint32_t* counts, int flags, hipStream_t stream) {
-    check_map(disparity);
+    check_map("reproject", disparity);
     if (disparity.memory() != Memory::Device)
         throw Exception("reproject: device buffers need a device map");
     if (!points) throw Exception("reproject: null points");
@@ -363,7 +391,7 @@ void reproject(const Image& disparity, const Matx44d& Q, float* points, int32_t*
 
 ReprojectStats reproject(const Image& disparity, const Matx44d& Q, std::vector<float>& points,
                          int flags, std::vector<int32_t>* index) {
-    check_map(disparity);
+    check_map("reproject", disparity);
     const int rows = disparity.rows(), cols = disparity.cols();
     const size_t pixels = (size_t)(rows > 0 ? rows : 0) * (size_t)(cols > 0 ? cols : 0);
     uint32_t counts[4] = {0, 0, 0, 0};
@@ -376,25 +404,17 @@ ReprojectStats reproject(const Image& disparity, const Matx44d& Q, std::vector<f
     } else {
         // device buffers for every pixel, then only the kept points come down
         // counts | points | index in one allocation
-        const size_t words = 4 + 3 * pixels + (index ? pixels : 0);
-        void* raw = nullptr;
-        throw_rc(check_hip(hipMalloc(&raw, words * 4), "hipMalloc(points)"));
-        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
-        uint32_t* d_counts = (uint32_t*)raw;
-        float* d_points = (float*)raw + 4;
-        int32_t* d_index = index ? (int32_t*)raw + 4 + 3 * pixels : nullptr;
+        const DeviceBlock d("hipMalloc(points)", 4, 3 * pixels, index ? pixels : 0);
+        float* d_points = d.a<float>();
+        int32_t* d_index = index ? d.b<int32_t>() : nullptr;
         throw_rc(bicos_reproject_device(current_engine(), disparity.data(), disparity.type(), rows,
                                         cols, Q.data(), flags, nullptr, d_points, d_index, pixels,
-                                        d_counts, nullptr));
-        throw_rc(check_hip(hipMemcpy(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost),
-                           "counts download"));
+                                        d.counts(), nullptr));
+        d.counts_down(counts);
         const size_t kept = counts[0];
-        if (kept)
-            throw_rc(check_hip(hipMemcpy(points.data(), d_points, kept * 3 * sizeof(float),
-                                         hipMemcpyDeviceToHost), "points download"));
+        if (kept) d.down(points.data(), d_points, kept * 3 * sizeof(float), "points download");
         if (kept && index)
-            throw_rc(check_hip(hipMemcpy(index->data(), d_index, kept * sizeof(int32_t),
-                                         hipMemcpyDeviceToHost), "index download"));
+            d.down(index->data(), d_index, kept * sizeof(int32_t), "index download");
     }
     points.resize(3 * (size_t)counts[0]);
     if (index) index->resize(counts[0]);
@@ -404,20 +424,9 @@ ReprojectStats reproject(const Image& disparity, const Matx44d& Q, std::vector<f
 // ---------------------------------------------------------- BICOS::filter_speckles
 // over the C entries (entries.cpp), which validate, lock the engine and launch
 
-namespace {
-
-void check_speckle_map(const Image& disparity) {
-    if (disparity.type() != S16 && disparity.type() != F32)
-        throw Exception("filter_speckles: the disparity map must be S16 or F32");
-    if (disparity.step() != (size_t)disparity.cols() * disparity.elemSize() && disparity.rows() > 1)
-        throw Exception("filter_speckles: the disparity map must be dense");
-}
-
-}  // namespace
-
 void filter_speckles(const Image& disparity, Image& out, int max_size, float max_diff, int flags,
                      int32_t* labels, uint32_t* counts, hipStream_t stream) {
-    check_speckle_map(disparity);
+    check_map("filter_speckles", disparity);
     if (disparity.memory() != Memory::Device)
         throw Exception("filter_speckles: device buffers need a device map");
     const void* map = disparity.data();  // (out may be the same header)
@@ -429,7 +438,7 @@ void filter_speckles(const Image& disparity, Image& out, int max_size, float max
 
 SpeckleStats filter_speckles(const Image& disparity, Image& out, int max_size, float max_diff,
                              int flags, std::vector<int32_t>* labels) {
-    check_speckle_map(disparity);
+    check_map("filter_speckles", disparity);
     const void* map = disparity.data();
     const int rows = disparity.rows(), cols = disparity.cols(), type = disparity.type();
     const Memory mem = disparity.memory();
@@ -442,18 +451,13 @@ SpeckleStats filter_speckles(const Image& disparity, Image& out, int max_size, f
                                     out.data(), labels ? labels->data() : nullptr, counts));
     } else {
         // counts | labels in one device allocation, downloaded after the launches
-        void* raw = nullptr;
-        throw_rc(check_hip(hipMalloc(&raw, (4 + (labels ? pixels : 0)) * 4), "hipMalloc(labels)"));
-        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
-        uint32_t* d_counts = (uint32_t*)raw;
-        int32_t* d_labels = labels ? (int32_t*)raw + 4 : nullptr;
+        const DeviceBlock d("hipMalloc(labels)", 4, labels ? pixels : 0);
+        int32_t* d_labels = labels ? d.a<int32_t>() : nullptr;
         throw_rc(bicos_speckle_device(current_engine(), map, type, rows, cols, max_size, max_diff,
-                                      flags, out.data(), d_labels, d_counts, nullptr));
-        throw_rc(check_hip(hipMemcpy(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost),
-                           "counts download"));
+                                      flags, out.data(), d_labels, d.counts(), nullptr));
+        d.counts_down(counts);
         if (labels && pixels)
-            throw_rc(check_hip(hipMemcpy(labels->data(), d_labels, pixels * sizeof(int32_t),
-                                         hipMemcpyDeviceToHost), "labels download"));
+            d.down(labels->data(), d_labels, pixels * sizeof(int32_t), "labels download");
     }
     return SpeckleStats{counts[0], counts[1], counts[2], counts[3]};
 }
@@ -461,20 +465,9 @@ SpeckleStats filter_speckles(const Image& disparity, Image& out, int max_size, f
 // ------------------------------------------------------------ BICOS::median_filter
 // over the C entries (entries.cpp), which validate and launch
 
-namespace {
-
-void check_median_map(const Image& disparity) {
-    if (disparity.type() != S16 && disparity.type() != F32)
-        throw Exception("median_filter: the disparity map must be S16 or F32");
-    if (disparity.step() != (size_t)disparity.cols() * disparity.elemSize() && disparity.rows() > 1)
-        throw Exception("median_filter: the disparity map must be dense");
-}
-
-}  // namespace
-
 void median_filter(const Image& disparity, Image& out, int ksize, int fill_min, int flags,
                    uint32_t* counts, hipStream_t stream) {
-    check_median_map(disparity);
+    check_map("median_filter", disparity);
     if (disparity.memory() != Memory::Device)
         throw Exception("median_filter: device buffers need a device map");
     if (&out == &disparity)
@@ -486,7 +479,7 @@ void median_filter(const Image& disparity, Image& out, int ksize, int fill_min, 
 }
 
 MedianStats median_filter(const Image& disparity, Image& out, int ksize, int fill_min, int flags) {
-    check_median_map(disparity);
+    check_map("median_filter", disparity);
     const void* map = disparity.data();  // (a host out may be the same header)
     const int rows = disparity.rows(), cols = disparity.cols(), type = disparity.type();
     const Memory mem = disparity.memory();
@@ -499,13 +492,10 @@ MedianStats median_filter(const Image& disparity, Image& out, int ksize, int fil
         if (&out == &disparity)
             throw Exception("median_filter: a device map cannot be filtered in place");
         out.create(rows, cols, type, mem);
-        void* raw = nullptr;
-        throw_rc(check_hip(hipMalloc(&raw, sizeof counts), "hipMalloc(counts)"));
-        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
+        const DeviceBlock d("hipMalloc(counts)", 4);
         throw_rc(bicos_median_device(current_engine(), map, type, rows, cols, ksize, fill_min,
-                                     flags, out.data(), (uint32_t*)raw, nullptr));
-        throw_rc(check_hip(hipMemcpy(counts, raw, sizeof counts, hipMemcpyDeviceToHost),
-                           "counts download"));
+                                     flags, out.data(), d.counts(), nullptr));
+        d.counts_down(counts);
     }
     return MedianStats{counts[0], counts[1], counts[2], counts[3]};
 }
@@ -513,21 +503,9 @@ MedianStats median_filter(const Image& disparity, Image& out, int ksize, int fil
 // ------------------------------------------------------------------ BICOS::normals
 // over the C entries (entries.cpp), which validate and launch
 
-namespace {
-
-void check_normals_map(const Image& disparity) {
-    if (disparity.type() != S16 && disparity.type() != F32)
-        throw Exception("normals: the disparity map must be S16 or F32");
-    if (disparity.step() != (size_t)disparity.cols() * disparity.elemSize() && disparity.rows() > 1)
-        throw Exception("normals: the disparity map must be dense");
-    if ((int64_t)disparity.cols() * 3 > INT32_MAX) throw Exception("normals: map too wide");
-}
-
-}  // namespace
-
 void normals(const Image& disparity, const Matx44d& Q, Image& normal_map,
              const NormalsParams& p, hipStream_t stream) {
-    check_normals_map(disparity);
+    check_map("normals", disparity, 3);
     const int rows = disparity.rows(), cols = disparity.cols();
     normal_map.create(rows, 3 * cols, F32, disparity.memory());
     if (disparity.memory() == Memory::Host)
@@ -544,7 +522,7 @@ void normals(const Image& disparity, const Matx44d& Q, Image& normal_map,
 void normals(const Image& disparity, const Matx44d& Q, float* normal_map, const int32_t* index,
              size_t count, float* normals_out, uint32_t* counts, const NormalsParams& p,
              hipStream_t stream) {
-    check_normals_map(disparity);
+    check_map("normals", disparity, 3);
     if (disparity.memory() != Memory::Device)
         throw Exception("normals: device buffers need a device map");
     throw_rc(bicos_normals_device(nullptr, disparity.data(), disparity.type(), disparity.rows(),
@@ -555,7 +533,7 @@ void normals(const Image& disparity, const Matx44d& Q, float* normal_map, const 
 
 NormalStats normals(const Image& disparity, const Matx44d& Q, const std::vector<int32_t>& index,
                     std::vector<float>& normals_out, const NormalsParams& p, Image* normal_map) {
-    check_normals_map(disparity);
+    check_map("normals", disparity, 3);
     const int rows = disparity.rows(), cols = disparity.cols();
     const size_t count = index.size();
     uint32_t counts[4] = {0, 0, 0, 0};
@@ -570,26 +548,19 @@ NormalStats normals(const Image& disparity, const Matx44d& Q, const std::vector<
                                     idx.data(), count, list.data(), normal_map ? counts : nullptr));
     } else {
         // counts | normals | index in one allocation
-        const size_t words = 4 + 3 * count + count;
-        void* raw = nullptr;
-        throw_rc(check_hip(hipMalloc(&raw, words * 4), "hipMalloc(normals)"));
-        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
-        uint32_t* d_counts = (uint32_t*)raw;
-        float* d_list = (float*)raw + 4;
-        int32_t* d_index = (int32_t*)raw + 4 + 3 * count;
+        const DeviceBlock d("hipMalloc(normals)", 4, 3 * count, count);
+        float* d_list = d.a<float>();
+        int32_t* d_index = d.b<int32_t>();
         if (count)
             throw_rc(check_hip(hipMemcpy(d_index, index.data(), count * sizeof(int32_t),
                                          hipMemcpyHostToDevice), "index upload"));
         throw_rc(bicos_normals_device(nullptr, disparity.data(), disparity.type(), rows, cols,
                                       Q.data(), p.flags, p.radius, p.max_diff, p.min_points, map,
-                                      d_index, count, d_list, normal_map ? d_counts : nullptr,
+                                      d_index, count, d_list, normal_map ? d.counts() : nullptr,
                                       nullptr));
-        if (normal_map)
-            throw_rc(check_hip(hipMemcpy(counts, d_counts, sizeof counts, hipMemcpyDeviceToHost),
-                               "counts download"));
+        if (normal_map) d.counts_down(counts);
         if (count)
-            throw_rc(check_hip(hipMemcpy(list.data(), d_list, count * 3 * sizeof(float),
-                                         hipMemcpyDeviceToHost), "normals download"));
+            d.down(list.data(), d_list, count * 3 * sizeof(float), "normals download");
         else
             throw_rc(check_hip(hipStreamSynchronize(nullptr), "hipStreamSynchronize"));
     }
@@ -601,22 +572,11 @@ NormalStats normals(const Image& disparity, const Matx44d& Q, const std::vector<
 // --------------------------------------------------------------------- BICOS::mesh
 // over the C entries (entries.cpp), which validate, lock the engine and launch
 
-namespace {
-
-void check_mesh_map(const Image& disparity) {
-    if (disparity.type() != S16 && disparity.type() != F32)
-        throw Exception("mesh: the disparity map must be S16 or F32");
-    if (disparity.step() != (size_t)disparity.cols() * disparity.elemSize() && disparity.rows() > 1)
-        throw Exception("mesh: the disparity map must be dense");
-}
-
-}  // namespace
-
 void mesh(const Image& disparity, const Matx44d& Q, float* points, int32_t* index,
           size_t vertex_capacity, uint32_t* counts, int32_t* triangles, size_t tri_capacity,
           uint32_t* mesh_counts, float max_diff, int flags, int32_t* vertex_map,
           hipStream_t stream) {
-    check_mesh_map(disparity);
+    check_map("mesh", disparity);
     if (disparity.memory() != Memory::Device)
         throw Exception("mesh: device buffers need a device map");
     throw_rc(bicos_mesh_device(current_engine(), disparity.data(), disparity.type(),
@@ -628,7 +588,7 @@ void mesh(const Image& disparity, const Matx44d& Q, float* points, int32_t* inde
 MeshStats mesh(const Image& disparity, const Matx44d& Q, std::vector<float>& points,
                std::vector<int32_t>& triangles, float max_diff, int flags,
                std::vector<int32_t>* index) {
-    check_mesh_map(disparity);
+    check_map("mesh", disparity);
     const int rows = disparity.rows(), cols = disparity.cols();
     const size_t pixels = (size_t)(rows > 0 ? rows : 0) * (size_t)(cols > 0 ? cols : 0);
     const size_t tris = rows < 2 || cols < 2 ? 0 : 2 * (size_t)(rows - 1) * (size_t)(cols - 1);
@@ -643,36 +603,29 @@ MeshStats mesh(const Image& disparity, const Matx44d& Q, std::vector<float>& poi
     } else {
         // device buffers for every pixel and quad, then only what was kept and emitted comes
         // down: counts | mesh_counts | points | triangles | index in one allocation
-        const size_t words = 8 + 3 * pixels + 3 * tris + (index ? pixels : 0);
-        void* raw = nullptr;
-        throw_rc(check_hip(hipMalloc(&raw, words * 4), "hipMalloc(mesh)"));
-        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
-        uint32_t* d_counts = (uint32_t*)raw;
-        float* d_points = (float*)raw + 8;
-        int32_t* d_tris = (int32_t*)raw + 8 + 3 * pixels;
+        const DeviceBlock d("hipMalloc(mesh)", 8, 3 * pixels, 3 * tris + (index ? pixels : 0));
+        uint32_t* d_counts = d.counts();
+        float* d_points = d.a<float>();
+        int32_t* d_tris = d.b<int32_t>();
         int32_t* d_index = index ? d_tris + 3 * tris : nullptr;
         // (a map without pixels launches nothing and needs no buffers: the entry zeroes the counts)
         throw_rc(bicos_mesh_device(current_engine(), disparity.data(), disparity.type(), rows,
                                    cols, Q.data(), flags, max_diff, d_points, d_index, pixels,
                                    d_counts, d_tris, tris, d_counts + 4, nullptr, nullptr));
         uint32_t both[8];
-        throw_rc(check_hip(hipMemcpy(both, d_counts, sizeof both, hipMemcpyDeviceToHost),
-                           "counts download"));
+        d.counts_down(both);
         std::copy(both, both + 4, counts);
         std::copy(both + 4, both + 8, mesh_counts);
         points.resize(3 * (size_t)counts[0]);
         triangles.resize(3 * (size_t)mesh_counts[0]);
         if (index) index->resize(counts[0]);
         if (counts[0])
-            throw_rc(check_hip(hipMemcpy(points.data(), d_points, points.size() * sizeof(float),
-                                         hipMemcpyDeviceToHost), "points download"));
+            d.down(points.data(), d_points, points.size() * sizeof(float), "points download");
         if (counts[0] && index)
-            throw_rc(check_hip(hipMemcpy(index->data(), d_index, index->size() * sizeof(int32_t),
-                                         hipMemcpyDeviceToHost), "index download"));
+            d.down(index->data(), d_index, index->size() * sizeof(int32_t), "index download");
         if (mesh_counts[0])
-            throw_rc(check_hip(hipMemcpy(triangles.data(), d_tris,
-                                         triangles.size() * sizeof(int32_t),
-                                         hipMemcpyDeviceToHost), "triangles download"));
+            d.down(triangles.data(), d_tris, triangles.size() * sizeof(int32_t),
+                   "triangles download");
     }
     points.resize(3 * (size_t)counts[0]);
     triangles.resize(3 * (size_t)mesh_counts[0]);
@@ -689,21 +642,9 @@ MeshStats mesh(const Image& disparity, const Matx44d& Q, std::vector<float>& poi
 // ------------------------------------------------------ BICOS::guide_from_disparity
 // over the C entries (entries.cpp), which validate and launch
 
-namespace {
-
-void check_prior_map(const Image& prior) {
-    if (prior.type() != S16 && prior.type() != F32)
-        throw Exception("guide_from_disparity: the prior map must be S16 or F32");
-    if (prior.step() != (size_t)prior.cols() * prior.elemSize() && prior.rows() > 1)
-        throw Exception("guide_from_disparity: the prior map must be dense");
-    if ((int64_t)prior.cols() * 2 > INT32_MAX) throw Exception("guide_from_disparity: map too wide");
-}
-
-}  // namespace
-
 void guide_from_disparity(const Image& prior, Image& guide, int rows, int cols,
                           const GuideParams& p, uint32_t* counts, hipStream_t stream) {
-    check_prior_map(prior);
+    check_map("guide_from_disparity", prior, 2, "prior");
     if (prior.memory() != Memory::Device)
         throw Exception("guide_from_disparity: device buffers need a device map");
     if (rows < 0 || cols < 0 || cols > INT32_MAX / 2)
@@ -717,7 +658,7 @@ void guide_from_disparity(const Image& prior, Image& guide, int rows, int cols,
 
 GuideStats guide_from_disparity(const Image& prior, Image& guide, int rows, int cols,
                                 const GuideParams& p) {
-    check_prior_map(prior);
+    check_map("guide_from_disparity", prior, 2, "prior");
     if (rows < 0 || cols < 0 || cols > INT32_MAX / 2)
         throw Exception("guide_from_disparity: bad guide size");
     uint32_t counts[2] = {0, 0};
@@ -728,12 +669,9 @@ GuideStats guide_from_disparity(const Image& prior, Image& guide, int rows, int 
                                   p.fallback_hi, p.flags, (int16_t*)guide.data(),
                                   guide.step() / 4, counts));
     } else {
-        void* raw = nullptr;
-        throw_rc(check_hip(hipMalloc(&raw, sizeof counts), "hipMalloc(counts)"));
-        const std::shared_ptr<void> owner(raw, [](void* q) { (void)hipFree(q); });
-        guide_from_disparity(prior, guide, rows, cols, p, (uint32_t*)raw, nullptr);
-        throw_rc(check_hip(hipMemcpy(counts, raw, sizeof counts, hipMemcpyDeviceToHost),
-                           "counts download"));
+        const DeviceBlock d("hipMalloc(counts)", 2);
+        guide_from_disparity(prior, guide, rows, cols, p, d.counts(), nullptr);
+        d.counts_down(counts);
     }
     return GuideStats{counts[0], counts[1]};
 }

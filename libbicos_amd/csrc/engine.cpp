@@ -595,14 +595,43 @@ int match_device(bicos_engine* e, const void* s0, const void* s1, int n, int row
     return check_hip(bicos_hip::launch_agree(aa, depth, dbl, st), "agree launch");
 }
 
+// ------------------------------------------- what the map stages check alike
+
+namespace {
+// "<stage>: the <what> must be CV_16S or CV_32F"
+int check_map_type(const char* stage, int type, const char* what = "disparity map") {
+    if (type == BICOS_CV_16S || type == BICOS_CV_32F) return BICOS_OK;
+    return fail(BICOS_E_ARG, std::string(stage) + ": the " + what + " must be CV_16S or CV_32F");
+}
+
+// "<stage>: negative image size", then "<stage>: rows * cols exceeds int32"
+int check_map_size(const char* stage, int rows, int cols) {
+    if (rows < 0 || cols < 0)
+        return fail(BICOS_E_ARG, std::string(stage) + ": negative image size");
+    if ((int64_t)rows * cols > INT32_MAX)
+        return fail(BICOS_E_ARG, std::string(stage) + ": rows * cols exceeds int32");
+    return BICOS_OK;
+}
+
+// whether [p, p + n) and [q, q + m) share a byte; a null pointer or an empty span shares none
+bool overlaps(const void* p, uintptr_t n, const void* q, uintptr_t m) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a && b && n && m && a < b + m && b < a + n;
+}
+
+// no pixels, nothing to launch: the `n` counts (if asked for) are all zero
+int zero_counts(uint32_t* counts, size_t n, hipStream_t st,
+                const char* what = "hipMemsetAsync(counts)") {
+    return counts ? check_hip(hipMemsetAsync(counts, 0, n * sizeof(uint32_t), st), what)
+                  : (int)BICOS_OK;
+}
+}  // namespace
+
 // -------------------------------------------------------------- reprojection
 
 int check_reproject(const ReprojectJob& j, const bicos_engine* e, bool needs_engine) {
-    if (j.disp_type != BICOS_CV_16S && j.disp_type != BICOS_CV_32F)
-        return fail(BICOS_E_ARG, "reproject: the disparity map must be CV_16S or CV_32F");
-    if (j.rows < 0 || j.cols < 0) return fail(BICOS_E_ARG, "reproject: negative image size");
-    if ((int64_t)j.rows * j.cols > INT32_MAX)
-        return fail(BICOS_E_ARG, "reproject: rows * cols exceeds int32");
+    if (int rc0 = check_map_type("reproject", j.disp_type)) return rc0;
+    if (int rc0 = check_map_size("reproject", j.rows, j.cols)) return rc0;
     if (j.flags & ~(BICOS_REPROJECT_ALLOW_NEGATIVE_Z | BICOS_REPROJECT_F32_SENTINEL))
         return fail(BICOS_E_ARG, "reproject: unknown flag bits");
     if (!j.xyz_map && !j.points)
@@ -618,10 +647,7 @@ int check_reproject(const ReprojectJob& j, const bicos_engine* e, bool needs_eng
 
 int reproject_device(bicos_engine* e, const ReprojectJob& j, hipStream_t st) {
     const uint32_t pixels = (uint32_t)j.rows * (uint32_t)j.cols;
-    if (pixels == 0)  // nothing to launch: the counts are all zero
-        return j.points ? check_hip(hipMemsetAsync(j.counts, 0, 4 * sizeof(uint32_t), st),
-                                    "hipMemsetAsync(counts)")
-                        : (int)BICOS_OK;
+    if (pixels == 0) return zero_counts(j.points ? j.counts : nullptr, 4, st);
     bicos_hip::ReprojectArgs a{};
     a.disp = j.disp;
     a.cols = j.cols;
@@ -651,11 +677,8 @@ int reproject_device(bicos_engine* e, const ReprojectJob& j, hipStream_t st) {
 // ------------------------------------------------------------ speckle filter
 
 int check_speckle(const SpeckleJob& j, const bicos_engine* e, bool needs_engine) {
-    if (j.disp_type != BICOS_CV_16S && j.disp_type != BICOS_CV_32F)
-        return fail(BICOS_E_ARG, "speckle: the disparity map must be CV_16S or CV_32F");
-    if (j.rows < 0 || j.cols < 0) return fail(BICOS_E_ARG, "speckle: negative image size");
-    if ((int64_t)j.rows * j.cols > INT32_MAX)
-        return fail(BICOS_E_ARG, "speckle: rows * cols exceeds int32");
+    if (int rc0 = check_map_type("speckle", j.disp_type)) return rc0;
+    if (int rc0 = check_map_size("speckle", j.rows, j.cols)) return rc0;
     if (j.flags & ~BICOS_SPECKLE_F32_SENTINEL)
         return fail(BICOS_E_ARG, "speckle: unknown flag bits");
     if (!(j.max_diff >= 0.0f))
@@ -665,9 +688,8 @@ int check_speckle(const SpeckleJob& j, const bicos_engine* e, bool needs_engine)
     if (j.rows > 0 && j.cols > 0) {
         if (!j.disp) return fail(BICOS_E_ARG, "speckle: null disparity map");
         if (!j.out) return fail(BICOS_E_ARG, "speckle: null out");
-        const uintptr_t a = (uintptr_t)j.disp, b = (uintptr_t)j.out;
         const uintptr_t bytes = (uintptr_t)j.rows * j.cols * (j.disp_type == BICOS_CV_32F ? 4 : 2);
-        if (a != b && a < b + bytes && b < a + bytes)
+        if (j.out != j.disp && overlaps(j.out, bytes, j.disp, bytes))
             return fail(BICOS_E_ARG, "speckle: out overlaps the map partially (in place: out == map)");
     }
     return BICOS_OK;
@@ -675,10 +697,7 @@ int check_speckle(const SpeckleJob& j, const bicos_engine* e, bool needs_engine)
 
 int speckle_device(bicos_engine* e, const SpeckleJob& j, hipStream_t st) {
     const size_t pixels = (size_t)j.rows * j.cols;
-    if (pixels == 0)  // nothing to launch: the counts are all zero
-        return j.counts ? check_hip(hipMemsetAsync(j.counts, 0, 4 * sizeof(uint32_t), st),
-                                    "hipMemsetAsync(counts)")
-                        : (int)BICOS_OK;
+    if (pixels == 0) return zero_counts(j.counts, 4, st);
     bicos_hip::SpeckleArgs a{};
     a.disp = j.disp;
     a.out = j.out;
@@ -704,32 +723,25 @@ int speckle_device(bicos_engine* e, const SpeckleJob& j, hipStream_t st) {
 // ------------------------------------------------------------- median filter
 
 int check_median(const MedianJob& j, bool device) {
-    if (j.disp_type != BICOS_CV_16S && j.disp_type != BICOS_CV_32F)
-        return fail(BICOS_E_ARG, "median: the disparity map must be CV_16S or CV_32F");
+    if (int rc0 = check_map_type("median", j.disp_type)) return rc0;
     if (j.ksize != 3 && j.ksize != 5) return fail(BICOS_E_ARG, "median: ksize must be 3 or 5");
     if (j.fill_min < 0 || j.fill_min > j.ksize * j.ksize)
         return fail(BICOS_E_ARG, "median: fill_min must lie in 0 .. ksize * ksize");
     if (j.flags & ~BICOS_MEDIAN_F32_SENTINEL)
         return fail(BICOS_E_ARG, "median: unknown flag bits");
-    if (j.rows < 0 || j.cols < 0) return fail(BICOS_E_ARG, "median: negative image size");
-    if ((int64_t)j.rows * j.cols > INT32_MAX)
-        return fail(BICOS_E_ARG, "median: rows * cols exceeds int32");
+    if (int rc0 = check_map_size("median", j.rows, j.cols)) return rc0;
     if (j.rows > 0 && j.cols > 0) {
         if (!j.disp) return fail(BICOS_E_ARG, "median: null disparity map");
         if (!j.out) return fail(BICOS_E_ARG, "median: null out");
-        const uintptr_t a = (uintptr_t)j.disp, b = (uintptr_t)j.out;
         const uintptr_t bytes = (uintptr_t)j.rows * j.cols * (j.disp_type == BICOS_CV_32F ? 4 : 2);
-        if (device && a < b + bytes && b < a + bytes)
+        if (device && overlaps(j.out, bytes, j.disp, bytes))
             return fail(BICOS_E_ARG, "median: out overlaps the map (the filter reads neighbours)");
     }
     return BICOS_OK;
 }
 
 int median_device(const MedianJob& j, hipStream_t st) {
-    if ((size_t)j.rows * j.cols == 0)  // nothing to launch: the counts are all zero
-        return j.counts ? check_hip(hipMemsetAsync(j.counts, 0, 4 * sizeof(uint32_t), st),
-                                    "hipMemsetAsync(counts)")
-                        : (int)BICOS_OK;
+    if ((size_t)j.rows * j.cols == 0) return zero_counts(j.counts, 4, st);
     bicos_hip::MedianArgs a{};
     a.disp = j.disp;
     a.out = j.out;
@@ -745,8 +757,7 @@ int median_device(const MedianJob& j, hipStream_t st) {
 // ----------------------------------------------------------- surface normals
 
 int check_normals(const NormalsJob& j) {
-    if (j.disp_type != BICOS_CV_16S && j.disp_type != BICOS_CV_32F)
-        return fail(BICOS_E_ARG, "normals: the disparity map must be CV_16S or CV_32F");
+    if (int rc0 = check_map_type("normals", j.disp_type)) return rc0;
     if (j.flags & ~(BICOS_NORMALS_ALLOW_NEGATIVE_Z | BICOS_NORMALS_F32_SENTINEL))
         return fail(BICOS_E_ARG, "normals: unknown flag bits");
     if (j.radius < 1 || j.radius > bicos_hip::NORMALS_MAX_RADIUS)
@@ -755,9 +766,7 @@ int check_normals(const NormalsJob& j) {
         return fail(BICOS_E_ARG, "normals: max_diff must be >= 0 and not NaN");
     if (j.min_points < 3 || j.min_points > (2 * j.radius + 1) * (2 * j.radius + 1))
         return fail(BICOS_E_ARG, "normals: min_points must lie in 3 .. (2 * radius + 1)^2");
-    if (j.rows < 0 || j.cols < 0) return fail(BICOS_E_ARG, "normals: negative image size");
-    if ((int64_t)j.rows * j.cols > INT32_MAX)
-        return fail(BICOS_E_ARG, "normals: rows * cols exceeds int32");
+    if (int rc0 = check_map_size("normals", j.rows, j.cols)) return rc0;
     if (!j.normal_map && !j.normals && !j.index)
         return fail(BICOS_E_ARG, "normals: no output (normal_map and normals both null)");
     if (j.normals && !j.index) return fail(BICOS_E_ARG, "normals: normals without index");
@@ -768,17 +777,12 @@ int check_normals(const NormalsJob& j) {
         if (!j.disp) return fail(BICOS_E_ARG, "normals: null disparity map");
         if (!j.Q) return fail(BICOS_E_ARG, "normals: null Q");
         const uintptr_t pixels = (uintptr_t)j.rows * j.cols;
-        const uintptr_t a = (uintptr_t)j.disp;
         const uintptr_t bytes = pixels * (j.disp_type == BICOS_CV_32F ? 4 : 2);
-        auto overlaps = [&](const void* p, uintptr_t n) {
-            const uintptr_t b = (uintptr_t)p;
-            return p && n && a < b + n && b < a + bytes;
-        };
-        if (overlaps(j.normal_map, pixels * 12))
+        if (overlaps(j.normal_map, pixels * 12, j.disp, bytes))
             return fail(BICOS_E_ARG, "normals: normal_map overlaps the map");
-        if (overlaps(j.normals, (uintptr_t)j.count * 12))
+        if (overlaps(j.normals, (uintptr_t)j.count * 12, j.disp, bytes))
             return fail(BICOS_E_ARG, "normals: normals overlaps the map");
-        if (overlaps(j.counts, 4 * sizeof(uint32_t)))
+        if (overlaps(j.counts, 4 * sizeof(uint32_t), j.disp, bytes))
             return fail(BICOS_E_ARG, "normals: counts overlaps the map");
     }
     return BICOS_OK;
@@ -802,11 +806,8 @@ int normals_device(const NormalsJob& j, hipStream_t st) {
     a.count = j.count;
     const bool f32 = j.disp_type == BICOS_CV_32F;
     if (j.normal_map) {
-        if (pixels == 0) {  // no map to launch: the counts are all zero
-            if (j.counts)
-                if (int rc = check_hip(hipMemsetAsync(j.counts, 0, 4 * sizeof(uint32_t), st),
-                                       "hipMemsetAsync(counts)"))
-                    return rc;
+        if (pixels == 0) {  // no map to launch
+            if (int rc = zero_counts(j.counts, 4, st)) return rc;
         } else if (int rc = check_hip(bicos_hip::launch_normals_map(a, f32, st),
                                       "normals map launch")) {
             return rc;
@@ -827,14 +828,11 @@ size_t mesh_quads(int rows, int cols) {
 }  // namespace
 
 int check_mesh(const MeshJob& j, const bicos_engine* e, bool needs_engine) {
-    if (j.disp_type != BICOS_CV_16S && j.disp_type != BICOS_CV_32F)
-        return fail(BICOS_E_ARG, "mesh: the disparity map must be CV_16S or CV_32F");
+    if (int rc0 = check_map_type("mesh", j.disp_type)) return rc0;
     if (j.flags & ~(BICOS_MESH_ALLOW_NEGATIVE_Z | BICOS_MESH_F32_SENTINEL))
         return fail(BICOS_E_ARG, "mesh: unknown flag bits");
     if (!(j.max_diff >= 0.0f)) return fail(BICOS_E_ARG, "mesh: max_diff must be >= 0 and not NaN");
-    if (j.rows < 0 || j.cols < 0) return fail(BICOS_E_ARG, "mesh: negative image size");
-    if ((int64_t)j.rows * j.cols > INT32_MAX)
-        return fail(BICOS_E_ARG, "mesh: rows * cols exceeds int32");
+    if (int rc0 = check_map_size("mesh", j.rows, j.cols)) return rc0;
     if (needs_engine && !e) return fail(BICOS_E_ARG, "mesh: null engine (workspace)");
     if (j.rows == 0 || j.cols == 0) return BICOS_OK;
     if (!j.disp) return fail(BICOS_E_ARG, "mesh: null disparity map");
@@ -861,26 +859,18 @@ int check_mesh(const MeshJob& j, const bicos_engine* e, bool needs_engine) {
                 {j.vertex_map, pixels * 4, "vertex_map"}};
     const int n = (int)(sizeof span / sizeof span[0]);
     for (int i = 1; i < n; ++i)
-        for (int k = 0; k < i; ++k) {
-            const uintptr_t a = (uintptr_t)span[i].p, b = (uintptr_t)span[k].p;
-            if (a && b && span[i].bytes && span[k].bytes && a < b + span[k].bytes &&
-                b < a + span[i].bytes)
+        for (int k = 0; k < i; ++k)
+            if (overlaps(span[i].p, span[i].bytes, span[k].p, span[k].bytes))
                 return fail(BICOS_E_ARG, std::string("mesh: ") + span[i].name + " overlaps " +
                                              span[k].name);
-        }
     return BICOS_OK;
 }
 
 int mesh_device(bicos_engine* e, const MeshJob& j, hipStream_t st) {
     const uint32_t pixels = (uint32_t)j.rows * (uint32_t)j.cols;
-    if (pixels == 0) {  // nothing to launch: the counts are all zero
-        if (j.counts)
-            if (int rc = check_hip(hipMemsetAsync(j.counts, 0, 4 * sizeof(uint32_t), st),
-                                   "hipMemsetAsync(counts)"))
-                return rc;
-        return j.mesh_counts ? check_hip(hipMemsetAsync(j.mesh_counts, 0, 4 * sizeof(uint32_t), st),
-                                         "hipMemsetAsync(mesh_counts)")
-                             : (int)BICOS_OK;
+    if (pixels == 0) {
+        if (int rc = zero_counts(j.counts, 4, st)) return rc;
+        return zero_counts(j.mesh_counts, 4, st, "hipMemsetAsync(mesh_counts)");
     }
     bicos_hip::MeshArgs a{};
     a.v.disp = j.disp;
@@ -927,8 +917,7 @@ int check_guide_params(const GuideJob& j) {
 }
 
 int check_guide_job(const GuideJob& j) {
-    if (j.prior_type != BICOS_CV_16S && j.prior_type != BICOS_CV_32F)
-        return fail(BICOS_E_ARG, "guide: the prior map must be CV_16S or CV_32F");
+    if (int rc0 = check_map_type("guide", j.prior_type, "prior map")) return rc0;
     if (int rc0 = check_guide_params(j)) return rc0;
     if (j.rows < 0 || j.cols < 0 || j.prows < 0 || j.pcols < 0)
         return fail(BICOS_E_ARG, "guide: negative image size");
@@ -947,10 +936,7 @@ int check_guide_job(const GuideJob& j) {
 }
 
 int guide_device(const GuideJob& j, hipStream_t st) {
-    if ((size_t)j.rows * j.cols == 0)  // nothing to launch: the counts are zero
-        return j.counts ? check_hip(hipMemsetAsync(j.counts, 0, 2 * sizeof(uint32_t), st),
-                                    "hipMemsetAsync(counts)")
-                        : (int)BICOS_OK;
+    if ((size_t)j.rows * j.cols == 0) return zero_counts(j.counts, 2, st);
     bicos_hip::GuideArgs a{};
     a.prior = j.prior;
     a.prows = j.prows;

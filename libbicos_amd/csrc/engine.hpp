@@ -13,9 +13,10 @@
 //               reprojection's point list); guide_device (a prior disparity map ->
 //               per-pixel search windows); pool_device (a stack pooled by an integer factor);
 //               match_pyramid_device (pool, coarse ranged match, guide, guided match)
-//   host.cpp    the banded host-buffer pipeline (HostPool, match_host); reproject_host;
-//               speckle_host; rectify_host, rectify_maps_host; median_host; normals_host;
-//               mesh_host; guide_host; pool_host; match_pyramid_host
+//   host.cpp    the banded host-buffer pipeline (HostPool, match_host); the staged host call
+//               (Staging) and the ten paths on it: reproject_host; speckle_host; rectify_host,
+//               rectify_maps_host; median_host; normals_host; mesh_host; guide_host; pool_host;
+//               match_pyramid_host
 //   entries.cpp the bicos_* extern "C" entries (bicos_c.h) but the multi-GPU ones
 //   multi.cpp   bicos_match_host_multi, bicos_match_bands_device
 //   cxxapi.cpp  namespace BICOS (HipImage, match, reproject, filter_speckles, median_filter,
@@ -181,6 +182,89 @@ class Lease {
     hipStream_t st_;
     size_t off_ = 0;
     bool held_ = false;
+};
+
+// One staged host call (host.cpp; every *_host path but match_host's banded pipeline): a lease
+// on e->stage over e->own_stream whose buffers are declared once each -- size, host side,
+// direction, the name check_hip reports, where the device pointer goes -- so that a buffer's
+// size is written once for its layout, its upload and its download.
+//     Staging s(e);  declarations;  int rc = s.begin();  if (!rc) rc = ..._device(.., s.stream());
+//     return s.finish(rc);
+// begin() leases the sum, hands out the 256-byte aligned pointers and issues the uploads in
+// declaration order; finish(rc) issues the downloads in declaration order if nothing failed,
+// then synchronises in any case and returns the first error, else the synchronisation's. The
+// lease is released (ws_ready recorded) by the destructor, on every exit path.
+// e is not null and its lock is held: the entries (entries.cpp) find the engine.
+class Staging {
+  public:
+    explicit Staging(bicos_engine* e)
+        : lease_(e, e->stage, e->stage_bytes, e->own_stream), st_(e->own_stream) {}
+    hipStream_t stream() const { return st_; }
+
+    // A device-only buffer of `bytes` -> its number, for up() / down() into parts of it
+    template <class T>
+    int buffer(T*& dev, size_t bytes) {
+        bufs_.push_back({bytes, &dev, [](void* slot, char* p) { *(T**)slot = (T*)p; }});
+        return (int)bufs_.size() - 1;
+    }
+    // ... one that is uploaded from / downloaded into `host` whole. A null host is an absent
+    // optional buffer: no bytes, a null device pointer, no copy.
+    template <class T>
+    void in(T*& dev, const void* host, size_t bytes, const char* what) {
+        if (!host) return (void)(dev = nullptr);
+        up(buffer(dev, bytes), 0, host, bytes, what);
+    }
+    template <class T>
+    void out(T*& dev, void* host, size_t bytes, const char* what) {
+        if (!host) return (void)(dev = nullptr);
+        down(buffer(dev, bytes), 0, host, bytes, what);
+    }
+    // Copies between `host` and byte `at` of buffer `buf`: dense (hipMemcpyAsync), or `rows` rows
+    // of `row_bytes`, `host_pitch` bytes apart on the host and dense in the buffer
+    // (hipMemcpy2DAsync)
+    void up(int buf, size_t at, const void* host, size_t bytes, const char* what) {
+        copies_.push_back({buf, at, (void*)host, 0, bytes, 0, true, what});
+    }
+    void down(int buf, size_t at, void* host, size_t bytes, const char* what) {
+        copies_.push_back({buf, at, host, 0, bytes, 0, false, what});
+    }
+    void up2d(int buf, size_t at, const void* host, size_t host_pitch, size_t row_bytes,
+              size_t rows, const char* what) {
+        copies_.push_back({buf, at, (void*)host, host_pitch, row_bytes, rows, true, what});
+    }
+    void down2d(int buf, size_t at, void* host, size_t host_pitch, size_t row_bytes, size_t rows,
+                const char* what) {
+        copies_.push_back({buf, at, host, host_pitch, row_bytes, rows, false, what});
+    }
+
+    int begin();
+    // For a download whose length an earlier one decides (reproject_host, mesh_host), between the
+    // device call and finish(): both do nothing but return the first error once there is one.
+    int download(void* host, const void* dev, size_t bytes, const char* what);
+    int sync();
+    int finish(int rc);
+
+  private:
+    struct Buf {
+        size_t bytes;
+        void* slot;
+        void (*set)(void* slot, char* p);
+        char* dev = nullptr;
+    };
+    struct Copy {
+        int buf;
+        size_t at;
+        void* host;
+        size_t host_pitch, row_bytes, rows;  // rows 0: dense, row_bytes in all
+        bool upload;
+        const char* what;
+    };
+    int issue(bool upload);
+    Lease lease_;
+    hipStream_t st_;
+    std::vector<Buf> bufs_;
+    std::vector<Copy> copies_;
+    int rc_ = BICOS_OK;
 };
 
 // Engine resources, each grown on demand and freed by free_resources (bicos_engine_destroy)
@@ -497,6 +581,7 @@ int mesh_device(bicos_engine* e, const MeshJob& j, hipStream_t st);
 // Host buffers: the map uploaded into the engine's staging, the same launches on the engine's
 // own stream, both counts downloaded and then min(kept, vertex_capacity) points and
 // min(triangles, tri_capacity) triangles. Synchronous.
+// rows * cols > 0 (bicos_mesh_host answers an empty map itself, without an engine).
 int mesh_host(bicos_engine* e, const MeshJob& j);
 
 // One remap of a stack (bicos_c.h "rectification"): the arguments of bicos_rectify_device, the

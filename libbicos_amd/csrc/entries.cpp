@@ -22,6 +22,33 @@ int check_words(int words) {
     return fail(BICOS_E_ARG, "words must be 1, 2, 4 or 8");
 }
 
+// The one way from an entry to its engine: f(e) under `guarded` with e's lock held. The
+// engine's workspace and staging may be shared with other threads (the default engine's are):
+// enqueueing is serialised per engine, the GPU work is ordered through ws_ready.
+// e is not NULL (the device entries, which refuse a NULL engine among their argument errors).
+template <class F>
+int with_engine(bicos_engine* e, F&& f) {
+    return guarded([&]() -> int {
+        std::lock_guard<std::mutex> g(e->lock);
+        return f(e);
+    });
+}
+
+// ... and with a NULL e replaced by the current device's default engine (the host entries)
+template <class F>
+int with_default_engine(bicos_engine* e, F&& f) {
+    return guarded([&]() -> int {
+        if (!e) {
+            int dev = 0;
+            if (int rc = check_hip(hipGetDevice(&dev), "hipGetDevice")) return rc;
+            e = default_engine(dev);
+            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
+        }
+        std::lock_guard<std::mutex> g(e->lock);
+        return f(e);
+    });
+}
+
 int match_device_entry(bicos_engine* e, const void* stack0, const void* stack1, int n, int rows,
                        int cols, size_t row_pitch, size_t plane_pitch, int depth,
                        const BicosConfig* cfg, int has_nxcorr, void* disparity, void* corrmap,
@@ -31,10 +58,7 @@ int match_device_entry(bicos_engine* e, const void* stack0, const void* stack1, 
         if (int rc0 = check_range(range->min, range->max)) return rc0;
     if (!cfg) return fail(BICOS_E_ARG, "null config");
     if (!e) return fail(BICOS_E_ARG, "null engine");
-    return guarded([&]() -> int {
-        // the engine's workspace may be shared with other threads (the default engine is):
-        // enqueueing is serialised per engine, the GPU work is ordered through ws_ready
-        std::lock_guard<std::mutex> g(e->lock);
+    return with_engine(e, [&](bicos_engine* e) -> int {
         return match_device(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch, depth, *cfg,
                             has_nxcorr != 0, nxc_threshold(*cfg), disparity, corrmap,
                             (hipStream_t)stream, disp_i16, desc0, desc1, range);
@@ -48,15 +72,7 @@ int match_host_entry(bicos_engine* e, const void* const* stack0, const void* con
         if (int rc0 = check_range(range->min, range->max)) return rc0;
     if (!cfg) return fail(BICOS_E_ARG, "null config");
     if (n < 0) return fail(BICOS_E_ARG, "negative stack size");
-    return guarded([&]() -> int {
-        if (!e) {
-            int dev = 0;
-            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-            if (rc) return rc;
-            e = default_engine(dev);
-            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
-        }
-        std::lock_guard<std::mutex> g(e->lock);
+    return with_default_engine(e, [&](bicos_engine* e) -> int {
         const std::vector<size_t> steps((size_t)n, step ? step : (size_t)(cols > 0 ? cols : 0) * depth);
         return match_host(e, stack0, steps.data(), stack1, steps.data(), n, rows, cols, depth, *cfg,
                           has_nxcorr != 0, nxc_threshold(*cfg), disparity, corrmap, range);
@@ -396,17 +412,7 @@ int bicos_guide_host(bicos_engine* e, const void* prior, int prior_type, int pro
     const GuideJob job{prior, prior_type, prows, pcols, rows, cols, scale, radius, spread,
                        fallback_lo, fallback_hi, flags, guide, guide_pitch, counts};
     if (int rc0 = check_guide_job(job)) return rc0;
-    return guarded([&]() -> int {
-        if (!e) {
-            int dev = 0;
-            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-            if (rc) return rc;
-            e = default_engine(dev);
-            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
-        }
-        std::lock_guard<std::mutex> g(e->lock);
-        return guide_host(e, job);
-    });
+    return with_default_engine(e, [&](bicos_engine* e) { return guide_host(e, job); });
 }
 
 int bicos_agree_stage_device(const int16_t* raw, const void* stack0, const void* stack1, int n,
@@ -441,11 +447,10 @@ int bicos_reproject_device(bicos_engine* e, const void* disparity, int disp_type
     const ReprojectJob job{disparity, disp_type, rows, cols, Q, flags, xyz_map, points, index,
                            capacity, counts};
     if (int rc0 = check_reproject(job, e, true)) return rc0;
-    return guarded([&]() -> int {
-        if (!points) return reproject_device(e, job, (hipStream_t)stream);  // no workspace
-        std::lock_guard<std::mutex> g(e->lock);
-        return reproject_device(e, job, (hipStream_t)stream);
-    });
+    hipStream_t st = (hipStream_t)stream;
+    if (!points)  // no workspace: nothing of the engine is used, so it is not locked
+        return guarded([&]() -> int { return reproject_device(e, job, st); });
+    return with_engine(e, [&](bicos_engine* e) { return reproject_device(e, job, st); });
 }
 
 int bicos_reproject_host(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
@@ -454,17 +459,7 @@ int bicos_reproject_host(bicos_engine* e, const void* disparity, int disp_type, 
     const ReprojectJob job{disparity, disp_type, rows, cols, Q, flags, xyz_map, points, index,
                            capacity, counts};
     if (int rc0 = check_reproject(job, e, false)) return rc0;
-    return guarded([&]() -> int {
-        if (!e) {
-            int dev = 0;
-            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-            if (rc) return rc;
-            e = default_engine(dev);
-            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
-        }
-        std::lock_guard<std::mutex> g(e->lock);
-        return reproject_host(e, job);
-    });
+    return with_default_engine(e, [&](bicos_engine* e) { return reproject_host(e, job); });
 }
 
 int bicos_reproject_segment(void) { return bicos_hip::REPROJECT_SEGMENT; }
@@ -477,8 +472,7 @@ int bicos_mesh_device(bicos_engine* e, const void* disparity, int disp_type, int
     const MeshJob job{disparity, disp_type, rows, cols, Q, flags, max_diff, points, index,
                       vertex_capacity, counts, triangles, tri_capacity, mesh_counts, vertex_map};
     if (int rc0 = check_mesh(job, e, true)) return rc0;
-    return guarded([&]() -> int {
-        std::lock_guard<std::mutex> g(e->lock);
+    return with_engine(e, [&](bicos_engine* e) -> int {
         return mesh_device(e, job, (hipStream_t)stream);
     });
 }
@@ -495,17 +489,7 @@ int bicos_mesh_host(bicos_engine* e, const void* disparity, int disp_type, int r
         if (mesh_counts) std::fill(mesh_counts, mesh_counts + 4, 0u);
         return BICOS_OK;
     }
-    return guarded([&]() -> int {
-        if (!e) {
-            int dev = 0;
-            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-            if (rc) return rc;
-            e = default_engine(dev);
-            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
-        }
-        std::lock_guard<std::mutex> g(e->lock);
-        return mesh_host(e, job);
-    });
+    return with_default_engine(e, [&](bicos_engine* e) { return mesh_host(e, job); });
 }
 
 int bicos_mesh_segment(void) { return bicos_hip::REPROJECT_SEGMENT; }
@@ -516,8 +500,7 @@ int bicos_speckle_device(bicos_engine* e, const void* disparity, int disp_type, 
     const SpeckleJob job{disparity, disp_type, rows, cols, max_size, max_diff, flags, out, labels,
                          counts};
     if (int rc0 = check_speckle(job, e, true)) return rc0;
-    return guarded([&]() -> int {
-        std::lock_guard<std::mutex> g(e->lock);
+    return with_engine(e, [&](bicos_engine* e) -> int {
         return speckle_device(e, job, (hipStream_t)stream);
     });
 }
@@ -528,17 +511,7 @@ int bicos_speckle_host(bicos_engine* e, const void* disparity, int disp_type, in
     const SpeckleJob job{disparity, disp_type, rows, cols, max_size, max_diff, flags, out, labels,
                          counts};
     if (int rc0 = check_speckle(job, e, false)) return rc0;
-    return guarded([&]() -> int {
-        if (!e) {
-            int dev = 0;
-            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-            if (rc) return rc;
-            e = default_engine(dev);
-            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
-        }
-        std::lock_guard<std::mutex> g(e->lock);
-        return speckle_host(e, job);
-    });
+    return with_default_engine(e, [&](bicos_engine* e) { return speckle_host(e, job); });
 }
 
 int bicos_speckle_tile(int* rows, int* cols) {
@@ -562,15 +535,8 @@ int bicos_rectify_maps_host(const double K[9], const double* D, int nd, const do
     const RectifyMapsJob job{K, D, nd, R, P, p_cols, rows, cols, map_x, map_y};
     bicos_hip::RectifyCamera cam;
     if (int rc0 = check_rectify_maps(job, &cam)) return rc0;
-    return guarded([&]() -> int {
-        int dev = 0;
-        int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-        if (rc) return rc;
-        bicos_engine* e = default_engine(dev);
-        if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
-        std::lock_guard<std::mutex> g(e->lock);
-        return rectify_maps_host(e, job, cam);
-    });
+    return with_default_engine(nullptr,
+                               [&](bicos_engine* e) { return rectify_maps_host(e, job, cam); });
 }
 
 int bicos_rectify_device(bicos_engine* e, const void* src, int n, int src_rows, int src_cols,
@@ -607,15 +573,7 @@ int bicos_rectify_host(bicos_engine* e, const void* const* src, int n, int src_r
     }
     const RectifyJob job{src[0], n, src_rows, src_cols, 0, 0, depth, map_x, map_y, map_pitch,
                          rows, cols, dst[0], 0, 0, border, valid};
-    return guarded([&]() -> int {
-        if (!e) {
-            int dev = 0;
-            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-            if (rc) return rc;
-            e = default_engine(dev);
-            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
-        }
-        std::lock_guard<std::mutex> g(e->lock);
+    return with_default_engine(e, [&](bicos_engine* e) -> int {
         return rectify_host(e, src, sstep, dst, dstep, job);
     });
 }
@@ -639,17 +597,7 @@ int bicos_median_host(bicos_engine* e, const void* disparity, int disp_type, int
                       int ksize, int fill_min, int flags, void* out, uint32_t counts[4]) {
     const MedianJob job{disparity, disp_type, rows, cols, ksize, fill_min, flags, out, counts};
     if (int rc0 = check_median(job, false)) return rc0;
-    return guarded([&]() -> int {
-        if (!e) {
-            int dev = 0;
-            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-            if (rc) return rc;
-            e = default_engine(dev);
-            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
-        }
-        std::lock_guard<std::mutex> g(e->lock);
-        return median_host(e, job);
-    });
+    return with_default_engine(e, [&](bicos_engine* e) { return median_host(e, job); });
 }
 
 int bicos_median_tile(int* rows, int* cols) {
@@ -682,17 +630,7 @@ int bicos_normals_host(bicos_engine* e, const void* disparity, int disp_type, in
         if (normals) std::fill(normals, normals + count * 3, std::numeric_limits<float>::quiet_NaN());
         return BICOS_OK;
     }
-    return guarded([&]() -> int {
-        if (!e) {
-            int dev = 0;
-            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-            if (rc) return rc;
-            e = default_engine(dev);
-            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
-        }
-        std::lock_guard<std::mutex> g(e->lock);
-        return normals_host(e, job);
-    });
+    return with_default_engine(e, [&](bicos_engine* e) { return normals_host(e, job); });
 }
 
 int bicos_normals_tile(int* rows, int* cols) {
@@ -732,15 +670,7 @@ int bicos_pool_host(bicos_engine* e, const void* const* src, int n, int rows, in
         if (!dst[t]) return fail(BICOS_E_ARG, "pool: null output stack");
     }
     const PoolJob job{src[0], n, rows, cols, 0, 0, depth, scale, dst[0], 0, 0};
-    return guarded([&]() -> int {
-        if (!e) {
-            int dev = 0;
-            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-            if (rc) return rc;
-            e = default_engine(dev);
-            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
-        }
-        std::lock_guard<std::mutex> g(e->lock);
+    return with_default_engine(e, [&](bicos_engine* e) -> int {
         return pool_host(e, src, sstep, dst, dstep, job);
     });
 }
@@ -785,8 +715,7 @@ int bicos_match_device_pyramid(bicos_engine* e, const void* stack0, const void* 
                                 has_nxcorr != 0, range, job, disparity))
         return rc0;
     if (!e) return fail(BICOS_E_ARG, "null engine");
-    return guarded([&]() -> int {
-        std::lock_guard<std::mutex> g(e->lock);
+    return with_engine(e, [&](bicos_engine* e) -> int {
         return match_pyramid_device(e, stack0, stack1, n, rows, cols, row_pitch, plane_pitch,
                                     depth, *cfg, has_nxcorr != 0, nxc_threshold(*cfg), range, job,
                                     disparity, corrmap, (hipStream_t)stream);
@@ -818,15 +747,7 @@ int bicos_match_host_pyramid(bicos_engine* e, const void* const* stack0, const v
                                 (size_t)(rows > 0 ? rows : 0) * (size_t)(cols > 0 ? cols : 0),
                                 depth, *cfg, has_nxcorr != 0, range, job, disparity))
         return rc0;
-    return guarded([&]() -> int {
-        if (!e) {
-            int dev = 0;
-            int rc = check_hip(hipGetDevice(&dev), "hipGetDevice");
-            if (rc) return rc;
-            e = default_engine(dev);
-            if (!e) return (int)BICOS_E_HIP;  // bicos_last_error says why
-        }
-        std::lock_guard<std::mutex> g(e->lock);
+    return with_default_engine(e, [&](bicos_engine* e) -> int {
         return match_pyramid_host(e, stack0, stack1, row, n, rows, cols, depth, *cfg,
                                   has_nxcorr != 0, nxc_threshold(*cfg), range, job, disparity,
                                   corrmap);

@@ -394,391 +394,272 @@ int match_host(bicos_engine* e, const void* const* p0, const size_t* steps0,
     return m.drain(rc);
 }
 
-int reproject_host(bicos_engine* e, const ReprojectJob& j) {
-    if (!e) return fail(BICOS_E_ARG, "null engine");
-    if (int rc0 = check_reproject(j, e, false)) return rc0;
-    const size_t pixels = (size_t)j.rows * j.cols;
-    if (pixels == 0) {
-        if (j.counts) std::fill(j.counts, j.counts + 4, 0u);
-        return BICOS_OK;
+// -------------------------------------------------------- the staged host call
+
+int Staging::begin() {
+    for (const Buf& b : bufs_) lease_.take(b.bytes);
+    rc_ = lease_.acquire();
+    if (rc_) return rc_;
+    for (Buf& b : bufs_) {
+        b.dev = lease_.take(b.bytes);
+        b.set(b.slot, b.dev);
     }
-    hipStream_t st = e->own_stream;
-    const size_t esz = j.disp_type == BICOS_CV_32F ? 4 : 2;
-    const size_t cap = std::min(j.capacity, pixels);
-    ReprojectJob d = j;  // the same job on staged device buffers
-    Lease stage(e, e->stage, e->stage_bytes, st);
-    auto carve = [&] {
-        d.disp = stage.take(pixels * esz);
-        d.xyz_map = j.xyz_map ? stage.take<float>(3 * pixels) : nullptr;
-        d.points = j.points ? stage.take<float>(3 * cap + 1) : nullptr;  // (non-null at cap 0)
-        d.index = j.index ? stage.take<int32_t>(cap + 1) : nullptr;
-        d.counts = j.points ? stage.take<uint32_t>(4) : nullptr;
-    };
-    carve();
-    int rc = stage.acquire();
-    if (rc) return rc;
-    carve();
-    d.capacity = cap;
-    rc = check_hip(hipMemcpyAsync((void*)d.disp, j.disp, pixels * esz, hipMemcpyHostToDevice, st),
-                   "disparity upload");
-    if (!rc) rc = reproject_device(e, d, st);
-    if (!rc && j.points) {
-        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 4 * sizeof(uint32_t),
-                                      hipMemcpyDeviceToHost, st), "counts download");
-        if (!rc) rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-        const size_t got = rc ? 0 : std::min<size_t>(j.counts[0], cap);
-        if (!rc && got)
-            rc = check_hip(hipMemcpyAsync(j.points, d.points, got * 3 * sizeof(float),
-                                          hipMemcpyDeviceToHost, st), "points download");
-        if (!rc && got && j.index)
-            rc = check_hip(hipMemcpyAsync(j.index, d.index, got * sizeof(int32_t),
-                                          hipMemcpyDeviceToHost, st), "index download");
-    }
-    if (!rc && j.xyz_map)
-        rc = check_hip(hipMemcpyAsync(j.xyz_map, d.xyz_map, pixels * 3 * sizeof(float),
-                                      hipMemcpyDeviceToHost, st), "xyz map download");
-    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    return rc ? rc : rc2;
+    return issue(true);
 }
 
-int mesh_host(bicos_engine* e, const MeshJob& j) {
-    if (!e) return fail(BICOS_E_ARG, "null engine");
-    if (int rc0 = check_mesh(j, e, false)) return rc0;
+// the declared copies of one direction, in their order; none after an error
+int Staging::issue(bool upload) {
+    const hipMemcpyKind kind = upload ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    for (const Copy& c : copies_) {
+        if (c.upload != upload || rc_) continue;
+        char* dev = bufs_[c.buf].dev + c.at;
+        void* dst = upload ? dev : c.host;
+        const void* src = upload ? c.host : dev;
+        rc_ = check_hip(c.rows ? hipMemcpy2DAsync(dst, upload ? c.row_bytes : c.host_pitch, src,
+                                                  upload ? c.host_pitch : c.row_bytes,
+                                                  c.row_bytes, c.rows, kind, st_)
+                               : hipMemcpyAsync(dst, src, c.row_bytes, kind, st_),
+                        c.what);
+    }
+    return rc_;
+}
+
+int Staging::download(void* host, const void* dev, size_t bytes, const char* what) {
+    if (!rc_) rc_ = check_hip(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st_), what);
+    return rc_;
+}
+
+int Staging::sync() {
+    if (!rc_) rc_ = check_hip(hipStreamSynchronize(st_), "hipStreamSynchronize");
+    return rc_;
+}
+
+int Staging::finish(int rc) {
+    if (!rc_) rc_ = rc;
+    issue(false);
+    const int synced = check_hip(hipStreamSynchronize(st_), "hipStreamSynchronize");
+    return rc_ ? rc_ : synced;
+}
+
+// --------------------------------------------------- the stages on host buffers
+// Each takes a job its entry has validated (entries.cpp), copies it and points the copy at
+// staged device buffers.
+
+int reproject_host(bicos_engine* e, const ReprojectJob& j) {
     const size_t pixels = (size_t)j.rows * j.cols;
     if (pixels == 0) {
         if (j.counts) std::fill(j.counts, j.counts + 4, 0u);
-        if (j.mesh_counts) std::fill(j.mesh_counts, j.mesh_counts + 4, 0u);
         return BICOS_OK;
     }
-    hipStream_t st = e->own_stream;
+    const size_t esz = j.disp_type == BICOS_CV_32F ? 4 : 2;
+    const size_t cap = std::min(j.capacity, pixels);
+    ReprojectJob d = j;
+    d.capacity = cap;
+    d.counts = nullptr;
+    Staging s(e);
+    s.in(d.disp, j.disp, pixels * esz, "disparity upload");
+    s.out(d.xyz_map, j.xyz_map, pixels * 3 * sizeof(float), "xyz map download");
+    if (j.points) {  // the list comes down by hand: the counts, then as much as they say
+        s.buffer(d.points, (3 * cap + 1) * sizeof(float));  // (non-null at cap 0)
+        if (j.index) s.buffer(d.index, (cap + 1) * sizeof(int32_t));
+        s.buffer(d.counts, 4 * sizeof(uint32_t));
+    }
+    int rc = s.begin();
+    if (!rc) rc = reproject_device(e, d, s.stream());
+    if (!rc && j.points) {
+        s.download(j.counts, d.counts, 4 * sizeof(uint32_t), "counts download");
+        rc = s.sync();
+        const size_t got = rc ? 0 : std::min<size_t>(j.counts[0], cap);
+        if (got) rc = s.download(j.points, d.points, got * 3 * sizeof(float), "points download");
+        if (got && j.index)
+            rc = s.download(j.index, d.index, got * sizeof(int32_t), "index download");
+    }
+    return s.finish(rc);
+}
+
+// rows * cols > 0 (bicos_mesh_host answers an empty map itself, without an engine)
+int mesh_host(bicos_engine* e, const MeshJob& j) {
+    const size_t pixels = (size_t)j.rows * j.cols;
     const size_t esz = j.disp_type == BICOS_CV_32F ? 4 : 2;
     const size_t quads = j.rows < 2 || j.cols < 2 ? 0 : (size_t)(j.rows - 1) * (j.cols - 1);
     const size_t vcap = std::min(j.vertex_capacity, pixels);
     const size_t tcap = std::min(j.tri_capacity, 2 * quads);
-    MeshJob d = j;  // the same job on staged device buffers
-    Lease stage(e, e->stage, e->stage_bytes, st);
-    auto carve = [&] {
-        d.disp = stage.take(pixels * esz);
-        d.points = stage.take<float>(3 * vcap + 1);  // (non-null at capacity 0)
-        d.index = j.index ? stage.take<int32_t>(vcap + 1) : nullptr;
-        d.counts = stage.take<uint32_t>(4);
-        d.triangles = stage.take<int32_t>(3 * tcap + 1);
-        d.mesh_counts = stage.take<uint32_t>(4);
-        d.vertex_map = j.vertex_map ? stage.take<int32_t>(pixels) : nullptr;
-    };
-    carve();
-    int rc = stage.acquire();
-    if (rc) return rc;
-    carve();
+    MeshJob d = j;
     d.vertex_capacity = vcap;
     d.tri_capacity = tcap;
-    rc = check_hip(hipMemcpyAsync((void*)d.disp, j.disp, pixels * esz, hipMemcpyHostToDevice, st),
-                   "disparity upload");
-    if (!rc) rc = mesh_device(e, d, st);
-    if (!rc)
-        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 4 * sizeof(uint32_t),
-                                      hipMemcpyDeviceToHost, st), "counts download");
-    if (!rc)
-        rc = check_hip(hipMemcpyAsync(j.mesh_counts, d.mesh_counts, 4 * sizeof(uint32_t),
-                                      hipMemcpyDeviceToHost, st), "mesh_counts download");
-    if (!rc) rc = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    const size_t verts = rc ? 0 : std::min<size_t>(j.counts[0], vcap);
-    const size_t tris = rc ? 0 : std::min<size_t>(j.mesh_counts[0], tcap);
-    if (!rc && verts)
-        rc = check_hip(hipMemcpyAsync(j.points, d.points, verts * 3 * sizeof(float),
-                                      hipMemcpyDeviceToHost, st), "points download");
-    if (!rc && verts && j.index)
-        rc = check_hip(hipMemcpyAsync(j.index, d.index, verts * sizeof(int32_t),
-                                      hipMemcpyDeviceToHost, st), "index download");
-    if (!rc && tris)
-        rc = check_hip(hipMemcpyAsync(j.triangles, d.triangles, tris * 3 * sizeof(int32_t),
-                                      hipMemcpyDeviceToHost, st), "triangles download");
-    if (!rc && j.vertex_map)
-        rc = check_hip(hipMemcpyAsync(j.vertex_map, d.vertex_map, pixels * sizeof(int32_t),
-                                      hipMemcpyDeviceToHost, st), "vertex_map download");
-    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    return rc ? rc : rc2;
+    Staging s(e);
+    s.in(d.disp, j.disp, pixels * esz, "disparity upload");
+    // the lists come down by hand: both counts, then as much as they say
+    s.buffer(d.points, (3 * vcap + 1) * sizeof(float));  // (non-null at capacity 0)
+    if (j.index) s.buffer(d.index, (vcap + 1) * sizeof(int32_t));
+    s.buffer(d.counts, 4 * sizeof(uint32_t));
+    s.buffer(d.triangles, (3 * tcap + 1) * sizeof(int32_t));
+    s.buffer(d.mesh_counts, 4 * sizeof(uint32_t));
+    s.out(d.vertex_map, j.vertex_map, pixels * sizeof(int32_t), "vertex_map download");
+    int rc = s.begin();
+    if (!rc) rc = mesh_device(e, d, s.stream());
+    if (!rc) {
+        s.download(j.counts, d.counts, 4 * sizeof(uint32_t), "counts download");
+        s.download(j.mesh_counts, d.mesh_counts, 4 * sizeof(uint32_t), "mesh_counts download");
+        rc = s.sync();
+        const size_t verts = rc ? 0 : std::min<size_t>(j.counts[0], vcap);
+        const size_t tris = rc ? 0 : std::min<size_t>(j.mesh_counts[0], tcap);
+        if (verts)
+            rc = s.download(j.points, d.points, verts * 3 * sizeof(float), "points download");
+        if (verts && j.index)
+            rc = s.download(j.index, d.index, verts * sizeof(int32_t), "index download");
+        if (tris)
+            rc = s.download(j.triangles, d.triangles, tris * 3 * sizeof(int32_t),
+                            "triangles download");
+    }
+    return s.finish(rc);
 }
 
 int speckle_host(bicos_engine* e, const SpeckleJob& j) {
-    if (!e) return fail(BICOS_E_ARG, "null engine");
-    if (int rc0 = check_speckle(j, e, false)) return rc0;
     const size_t pixels = (size_t)j.rows * j.cols;
     if (pixels == 0) {
         if (j.counts) std::fill(j.counts, j.counts + 4, 0u);
         return BICOS_OK;
     }
-    hipStream_t st = e->own_stream;
+    const size_t bytes = pixels * (j.disp_type == BICOS_CV_32F ? 4 : 2);
+    SpeckleJob d = j;
+    Staging s(e);
+    const int map = s.buffer(d.out, bytes);  // filtered in place
+    s.up(map, 0, j.disp, bytes, "disparity upload");
+    s.down(map, 0, j.out, bytes, "filtered map download");
+    s.out(d.labels, j.labels, pixels * sizeof(int32_t), "labels download");
+    s.out(d.counts, j.counts, 4 * sizeof(uint32_t), "counts download");
+    int rc = s.begin();
+    d.disp = d.out;
+    if (!rc) rc = speckle_device(e, d, s.stream());
+    return s.finish(rc);
+}
+
+int median_host(bicos_engine* e, const MedianJob& j) {
+    const size_t pixels = (size_t)j.rows * j.cols;
+    if (pixels == 0) {
+        if (j.counts) std::fill(j.counts, j.counts + 4, 0u);
+        return BICOS_OK;
+    }
+    const size_t bytes = pixels * (j.disp_type == BICOS_CV_32F ? 4 : 2);
+    MedianJob d = j;
+    Staging s(e);
+    // two buffers, because the launch reads neighbours (which is why the caller's out may be
+    // its map)
+    s.in(d.disp, j.disp, bytes, "disparity upload");
+    s.out(d.out, j.out, bytes, "filtered map download");
+    s.out(d.counts, j.counts, 4 * sizeof(uint32_t), "counts download");
+    int rc = s.begin();
+    if (!rc) rc = median_device(d, s.stream());
+    return s.finish(rc);
+}
+
+// rows * cols > 0 (bicos_normals_host answers an empty map itself, without an engine)
+int normals_host(bicos_engine* e, const NormalsJob& j) {
+    const size_t pixels = (size_t)j.rows * j.cols;
+    const size_t count = j.normals ? j.count : 0;
     const size_t esz = j.disp_type == BICOS_CV_32F ? 4 : 2;
-    SpeckleJob d = j;  // the same job on staged device buffers, filtered in place
-    Lease stage(e, e->stage, e->stage_bytes, st);
-    auto carve = [&] {
-        d.out = stage.take(pixels * esz);
-        d.disp = d.out;
-        d.labels = j.labels ? stage.take<int32_t>(pixels) : nullptr;
-        d.counts = j.counts ? stage.take<uint32_t>(4) : nullptr;
-    };
-    carve();
-    int rc = stage.acquire();
-    if (rc) return rc;
-    carve();
-    rc = check_hip(hipMemcpyAsync(d.out, j.disp, pixels * esz, hipMemcpyHostToDevice, st),
-                   "disparity upload");
-    if (!rc) rc = speckle_device(e, d, st);
-    if (!rc)
-        rc = check_hip(hipMemcpyAsync(j.out, d.out, pixels * esz, hipMemcpyDeviceToHost, st),
-                       "filtered map download");
-    if (!rc && j.labels)
-        rc = check_hip(hipMemcpyAsync(j.labels, d.labels, pixels * sizeof(int32_t),
-                                      hipMemcpyDeviceToHost, st), "labels download");
-    if (!rc && j.counts)
-        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 4 * sizeof(uint32_t),
-                                      hipMemcpyDeviceToHost, st), "counts download");
-    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    return rc ? rc : rc2;
+    NormalsJob d = j;
+    d.count = count;
+    Staging s(e);
+    s.in(d.disp, j.disp, pixels * esz, "disparity upload");
+    s.out(d.normal_map, j.normal_map, pixels * 3 * sizeof(float), "normal map download");
+    s.in(d.index, count ? j.index : nullptr, count * sizeof(int32_t), "index upload");
+    s.out(d.normals, count ? j.normals : nullptr, count * 3 * sizeof(float), "normals download");
+    s.out(d.counts, j.counts, 4 * sizeof(uint32_t), "counts download");
+    int rc = s.begin();
+    if (!rc) rc = normals_device(d, s.stream());
+    return s.finish(rc);
+}
+
+int guide_host(bicos_engine* e, const GuideJob& j) {
+    const size_t pixels = (size_t)j.rows * j.cols;
+    if (pixels == 0) {
+        if (j.counts) std::fill(j.counts, j.counts + 2, 0u);
+        return BICOS_OK;
+    }
+    const size_t prior_bytes = (size_t)j.prows * j.pcols * (j.prior_type == BICOS_CV_32F ? 4 : 2);
+    const size_t pitch = j.guide_pitch ? j.guide_pitch : (size_t)j.cols;
+    GuideJob d = j;
+    d.guide_pitch = (size_t)j.cols;  // the staged guide is dense
+    Staging s(e);
+    s.in(d.prior, j.prior, prior_bytes, "prior upload");
+    s.down2d(s.buffer(d.guide, pixels * 4), 0, j.guide, pitch * 4, (size_t)j.cols * 4,
+             (size_t)j.rows, "guide download");
+    s.out(d.counts, j.counts, 2 * sizeof(uint32_t), "counts download");
+    int rc = s.begin();
+    if (!rc) rc = guide_device(d, s.stream());
+    return s.finish(rc);
 }
 
 // --------------------------------------------------------------- rectification
 
 int rectify_host(bicos_engine* e, const void* const* src, size_t src_step, void* const* dst,
                  size_t dst_step, const RectifyJob& j) {
-    if (!e) return fail(BICOS_E_ARG, "null engine");
-    hipStream_t st = e->own_stream;
     const size_t d = (size_t)j.depth;
     const size_t src_row = (size_t)j.src_cols * d, dst_row = (size_t)j.cols * d;
     const size_t map_row = (size_t)j.cols * sizeof(float);
     const size_t src_plane = src_row * j.src_rows, dst_plane = dst_row * j.rows;
-    RectifyJob dj = j;  // the same job on dense staged device buffers
+    RectifyJob dj = j;  // dense
     dj.src_row_pitch = (size_t)j.src_cols;
     dj.src_plane_pitch = (size_t)j.src_cols * j.src_rows;
     dj.dst_row_pitch = (size_t)j.cols;
     dj.dst_plane_pitch = (size_t)j.cols * j.rows;
     dj.map_pitch = 0;
-    Lease stage(e, e->stage, e->stage_bytes, st);
-    char *s = nullptr, *o = nullptr;
-    auto carve = [&] {
-        s = stage.take(src_plane * j.n);
-        o = stage.take(dst_plane * j.n);
-        dj.map_x = stage.take<float>((size_t)j.rows * j.cols);
-        dj.map_y = stage.take<float>((size_t)j.rows * j.cols);
-        dj.valid = j.valid ? stage.take<uint8_t>((size_t)j.rows * j.cols) : nullptr;
-    };
-    carve();
-    int rc = stage.acquire();
-    if (rc) return rc;
-    carve();
-    dj.src = s;
-    dj.dst = o;
-    for (int t = 0; t < j.n && !rc; ++t)
-        rc = check_hip(hipMemcpy2DAsync(s + t * src_plane, src_row, src[t], src_step, src_row,
-                                        (size_t)j.src_rows, hipMemcpyHostToDevice, st),
-                       "stack upload");
     const size_t mp = j.map_pitch ? j.map_pitch : map_row;
-    if (!rc)
-        rc = check_hip(hipMemcpy2DAsync((void*)dj.map_x, map_row, j.map_x, mp, map_row,
-                                        (size_t)j.rows, hipMemcpyHostToDevice, st), "map upload");
-    if (!rc)
-        rc = check_hip(hipMemcpy2DAsync((void*)dj.map_y, map_row, j.map_y, mp, map_row,
-                                        (size_t)j.rows, hipMemcpyHostToDevice, st), "map upload");
-    if (!rc) rc = rectify_device(dj, st);
-    for (int t = 0; t < j.n && !rc; ++t)
-        rc = check_hip(hipMemcpy2DAsync(dst[t], dst_step, o + t * dst_plane, dst_row, dst_row,
-                                        (size_t)j.rows, hipMemcpyDeviceToHost, st),
-                       "stack download");
-    if (!rc && j.valid)
-        rc = check_hip(hipMemcpyAsync(j.valid, dj.valid, (size_t)j.rows * j.cols,
-                                      hipMemcpyDeviceToHost, st), "valid download");
-    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    return rc ? rc : rc2;
+    Staging s(e);
+    const int in = s.buffer(dj.src, src_plane * j.n), out = s.buffer(dj.dst, dst_plane * j.n);
+    for (int t = 0; t < j.n; ++t)
+        s.up2d(in, t * src_plane, src[t], src_step, src_row, (size_t)j.src_rows, "stack upload");
+    s.up2d(s.buffer(dj.map_x, map_row * j.rows), 0, j.map_x, mp, map_row, (size_t)j.rows,
+           "map upload");
+    s.up2d(s.buffer(dj.map_y, map_row * j.rows), 0, j.map_y, mp, map_row, (size_t)j.rows,
+           "map upload");
+    for (int t = 0; t < j.n; ++t)
+        s.down2d(out, t * dst_plane, dst[t], dst_step, dst_row, (size_t)j.rows, "stack download");
+    s.out(dj.valid, j.valid, (size_t)j.rows * j.cols, "valid download");
+    int rc = s.begin();
+    if (!rc) rc = rectify_device(dj, s.stream());
+    return s.finish(rc);
 }
 
 int rectify_maps_host(bicos_engine* e, const RectifyMapsJob& j,
                       const bicos_hip::RectifyCamera& cam) {
-    if (!e) return fail(BICOS_E_ARG, "null engine");
-    hipStream_t st = e->own_stream;
-    const size_t pixels = (size_t)j.rows * j.cols;
+    const size_t bytes = (size_t)j.rows * j.cols * sizeof(float);
     RectifyMapsJob dj = j;
-    Lease stage(e, e->stage, e->stage_bytes, st);
-    auto carve = [&] {
-        dj.map_x = stage.take<float>(pixels);
-        dj.map_y = stage.take<float>(pixels);
-    };
-    carve();
-    int rc = stage.acquire();
-    if (rc) return rc;
-    carve();
-    rc = rectify_maps_device(dj, cam, st);
-    if (!rc)
-        rc = check_hip(hipMemcpyAsync(j.map_x, dj.map_x, pixels * sizeof(float),
-                                      hipMemcpyDeviceToHost, st), "map download");
-    if (!rc)
-        rc = check_hip(hipMemcpyAsync(j.map_y, dj.map_y, pixels * sizeof(float),
-                                      hipMemcpyDeviceToHost, st), "map download");
-    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    return rc ? rc : rc2;
-}
-
-int median_host(bicos_engine* e, const MedianJob& j) {
-    if (!e) return fail(BICOS_E_ARG, "null engine");
-    if (int rc0 = check_median(j, false)) return rc0;
-    const size_t pixels = (size_t)j.rows * j.cols;
-    if (pixels == 0) {
-        if (j.counts) std::fill(j.counts, j.counts + 4, 0u);
-        return BICOS_OK;
-    }
-    hipStream_t st = e->own_stream;
-    const size_t esz = j.disp_type == BICOS_CV_32F ? 4 : 2;
-    // the same job on staged device buffers: two of them, because the launch reads
-    // neighbours (which is why the caller's out may be its map)
-    MedianJob d = j;
-    Lease stage(e, e->stage, e->stage_bytes, st);
-    void* map = nullptr;
-    auto carve = [&] {
-        map = stage.take(pixels * esz);
-        d.disp = map;
-        d.out = stage.take(pixels * esz);
-        d.counts = j.counts ? stage.take<uint32_t>(4) : nullptr;
-    };
-    carve();
-    int rc = stage.acquire();
-    if (rc) return rc;
-    carve();
-    rc = check_hip(hipMemcpyAsync(map, j.disp, pixels * esz, hipMemcpyHostToDevice, st),
-                   "disparity upload");
-    if (!rc) rc = median_device(d, st);
-    if (!rc)
-        rc = check_hip(hipMemcpyAsync(j.out, d.out, pixels * esz, hipMemcpyDeviceToHost, st),
-                       "filtered map download");
-    if (!rc && j.counts)
-        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 4 * sizeof(uint32_t),
-                                      hipMemcpyDeviceToHost, st), "counts download");
-    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    return rc ? rc : rc2;
-}
-
-int normals_host(bicos_engine* e, const NormalsJob& j) {
-    if (!e) return fail(BICOS_E_ARG, "null engine");
-    if (int rc0 = check_normals(j)) return rc0;
-    const size_t pixels = (size_t)j.rows * j.cols;
-    const size_t count = j.normals ? j.count : 0;
-    if (pixels == 0) return fail(BICOS_E_ARG, "normals: empty map (the entry answers it)");
-    hipStream_t st = e->own_stream;
-    const size_t esz = j.disp_type == BICOS_CV_32F ? 4 : 2;
-    NormalsJob d = j;  // the same job on staged device buffers
-    Lease stage(e, e->stage, e->stage_bytes, st);
-    void* map = nullptr;
-    int32_t* index = nullptr;
-    auto carve = [&] {
-        map = stage.take(pixels * esz);
-        d.disp = map;
-        d.normal_map = j.normal_map ? stage.take<float>(pixels * 3) : nullptr;
-        index = count ? stage.take<int32_t>(count) : nullptr;
-        d.index = index;
-        d.normals = count ? stage.take<float>(count * 3) : nullptr;
-        d.count = count;
-        d.counts = j.counts ? stage.take<uint32_t>(4) : nullptr;
-    };
-    carve();
-    int rc = stage.acquire();
-    if (rc) return rc;
-    carve();
-    rc = check_hip(hipMemcpyAsync(map, j.disp, pixels * esz, hipMemcpyHostToDevice, st),
-                   "disparity upload");
-    if (!rc && count)
-        rc = check_hip(hipMemcpyAsync(index, j.index, count * sizeof(int32_t),
-                                      hipMemcpyHostToDevice, st), "index upload");
-    if (!rc) rc = normals_device(d, st);
-    if (!rc && j.normal_map)
-        rc = check_hip(hipMemcpyAsync(j.normal_map, d.normal_map, pixels * 3 * sizeof(float),
-                                      hipMemcpyDeviceToHost, st), "normal map download");
-    if (!rc && count)
-        rc = check_hip(hipMemcpyAsync(j.normals, d.normals, count * 3 * sizeof(float),
-                                      hipMemcpyDeviceToHost, st), "normals download");
-    if (!rc && j.counts)
-        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 4 * sizeof(uint32_t),
-                                      hipMemcpyDeviceToHost, st), "counts download");
-    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    return rc ? rc : rc2;
-}
-
-int guide_host(bicos_engine* e, const GuideJob& j) {
-    if (!e) return fail(BICOS_E_ARG, "null engine");
-    if (int rc0 = check_guide_job(j)) return rc0;
-    const size_t pixels = (size_t)j.rows * j.cols;
-    if (pixels == 0) {
-        if (j.counts) std::fill(j.counts, j.counts + 2, 0u);
-        return BICOS_OK;
-    }
-    hipStream_t st = e->own_stream;
-    const size_t prior_bytes = (size_t)j.prows * j.pcols * (j.prior_type == BICOS_CV_32F ? 4 : 2);
-    const size_t pitch = j.guide_pitch ? j.guide_pitch : (size_t)j.cols;
-    GuideJob d = j;  // the same job on staged device buffers, the guide dense
-    d.guide_pitch = (size_t)j.cols;
-    Lease stage(e, e->stage, e->stage_bytes, st);
-    auto carve = [&] {
-        d.prior = stage.take(prior_bytes);
-        d.guide = stage.take<int16_t>(2 * pixels);
-        d.counts = j.counts ? stage.take<uint32_t>(2) : nullptr;
-    };
-    carve();
-    int rc = stage.acquire();
-    if (rc) return rc;
-    carve();
-    rc = check_hip(hipMemcpyAsync((void*)d.prior, j.prior, prior_bytes, hipMemcpyHostToDevice, st),
-                   "prior upload");
-    if (!rc) rc = guide_device(d, st);
-    if (!rc)
-        rc = check_hip(hipMemcpy2DAsync(j.guide, pitch * 4, d.guide, (size_t)j.cols * 4,
-                                        (size_t)j.cols * 4, (size_t)j.rows, hipMemcpyDeviceToHost,
-                                        st), "guide download");
-    if (!rc && j.counts)
-        rc = check_hip(hipMemcpyAsync(j.counts, d.counts, 2 * sizeof(uint32_t),
-                                      hipMemcpyDeviceToHost, st), "counts download");
-    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    return rc ? rc : rc2;
+    Staging s(e);
+    s.out(dj.map_x, j.map_x, bytes, "map download");
+    s.out(dj.map_y, j.map_y, bytes, "map download");
+    int rc = s.begin();
+    if (!rc) rc = rectify_maps_device(dj, cam, s.stream());
+    return s.finish(rc);
 }
 
 // --------------------------------------------------------------- stack pooling
 
 int pool_host(bicos_engine* e, const void* const* src, size_t src_step, void* const* dst,
               size_t dst_step, const PoolJob& j) {
-    if (!e) return fail(BICOS_E_ARG, "null engine");
-    hipStream_t st = e->own_stream;
     const size_t d = (size_t)j.depth;
     const int prows = j.rows / j.scale, pcols = j.cols / j.scale;
     // only what the launch reads is uploaded: the remainder rows and columns stay on the host
     const size_t src_row = (size_t)pcols * j.scale * d, dst_row = (size_t)pcols * d;
     const size_t src_plane = src_row * prows * j.scale, dst_plane = dst_row * prows;
-    PoolJob dj = j;  // the same job on dense staged device buffers
+    PoolJob dj = j;  // dense
     dj.rows = prows * j.scale;
     dj.cols = pcols * j.scale;
     dj.src_row_pitch = (size_t)dj.cols;
     dj.src_plane_pitch = (size_t)dj.cols * dj.rows;
     dj.dst_row_pitch = (size_t)pcols;
     dj.dst_plane_pitch = (size_t)pcols * prows;
-    Lease stage(e, e->stage, e->stage_bytes, st);
-    char *s = nullptr, *o = nullptr;
-    auto carve = [&] {
-        s = stage.take(src_plane * j.n);
-        o = stage.take(dst_plane * j.n);
-    };
-    carve();
-    int rc = stage.acquire();
-    if (rc) return rc;
-    carve();
-    dj.src = s;
-    dj.dst = o;
-    for (int t = 0; t < j.n && !rc; ++t)
-        rc = check_hip(hipMemcpy2DAsync(s + t * src_plane, src_row, src[t], src_step, src_row,
-                                        (size_t)dj.rows, hipMemcpyHostToDevice, st),
-                       "stack upload");
-    if (!rc) rc = pool_device(dj, st);
-    for (int t = 0; t < j.n && !rc; ++t)
-        rc = check_hip(hipMemcpy2DAsync(dst[t], dst_step, o + t * dst_plane, dst_row, dst_row,
-                                        (size_t)prows, hipMemcpyDeviceToHost, st),
-                       "stack download");
-    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    return rc ? rc : rc2;
+    Staging s(e);
+    const int in = s.buffer(dj.src, src_plane * j.n), out = s.buffer(dj.dst, dst_plane * j.n);
+    for (int t = 0; t < j.n; ++t)
+        s.up2d(in, t * src_plane, src[t], src_step, src_row, (size_t)dj.rows, "stack upload");
+    for (int t = 0; t < j.n; ++t)
+        s.down2d(out, t * dst_plane, dst[t], dst_step, dst_row, (size_t)prows, "stack download");
+    int rc = s.begin();
+    if (!rc) rc = pool_device(dj, s.stream());
+    return s.finish(rc);
 }
 
 // --------------------------------------------------------------- pyramid match
@@ -787,58 +668,31 @@ int match_pyramid_host(bicos_engine* e, const void* const* p0, const void* const
                        int n, int rows, int cols, int depth, const BicosConfig& cfg,
                        bool has_nxcorr, float threshold, const DispRange& range,
                        const PyramidJob& j, void* disp, void* corr) {
-    if (!e) return fail(BICOS_E_ARG, "null engine");
-    hipStream_t st = e->own_stream;
     const size_t row = (size_t)cols * depth, plane = row * rows;
     const size_t pix = (size_t)rows * cols;
     const size_t ppix = (size_t)(rows / j.scale) * (size_t)(cols / j.scale);
-    const bool f32 = has_nxcorr;  // bicos_output_type: of the fine map and of the coarse one
-    const size_t esz = f32 ? 4 : 2;
+    const size_t esz = has_nxcorr ? 4 : 2;  // bicos_output_type: of the fine map and the coarse one
     const size_t csz = cfg.precision != 0 ? sizeof(double) : sizeof(float);  // of the corrmap
-    PyramidJob dj = j;  // the same job on staged device buffers
-    char *s0 = nullptr, *s1 = nullptr;
+    PyramidJob dj = j;
+    const void *s0 = nullptr, *s1 = nullptr;
     void *d_disp = nullptr, *d_corr = nullptr;
-    Lease stage(e, e->stage, e->stage_bytes, st);
-    auto carve = [&] {
-        s0 = stage.take(plane * n);
-        s1 = stage.take(plane * n);
-        d_disp = stage.take(pix * esz);
-        d_corr = corr && has_nxcorr ? stage.take(pix * csz) : nullptr;
-        dj.coarse = j.coarse ? stage.take(ppix * esz) : nullptr;
-        dj.guide = j.guide ? stage.take<int16_t>(2 * pix) : nullptr;
-        dj.counts = j.counts ? stage.take<uint32_t>(2) : nullptr;
-    };
-    carve();
-    int rc = stage.acquire();
-    if (rc) return rc;
-    carve();
-    for (int t = 0; t < n && !rc; ++t) {
-        rc = check_hip(hipMemcpy2DAsync(s0 + t * plane, row, p0[t], step, row, (size_t)rows,
-                                        hipMemcpyHostToDevice, st), "stack upload");
-        if (!rc)
-            rc = check_hip(hipMemcpy2DAsync(s1 + t * plane, row, p1[t], step, row, (size_t)rows,
-                                            hipMemcpyHostToDevice, st), "stack upload");
+    Staging s(e);
+    const int b0 = s.buffer(s0, plane * n), b1 = s.buffer(s1, plane * n);
+    for (int t = 0; t < n; ++t) {
+        s.up2d(b0, t * plane, p0[t], step, row, (size_t)rows, "stack upload");
+        s.up2d(b1, t * plane, p1[t], step, row, (size_t)rows, "stack upload");
     }
+    s.out(d_disp, disp, pix * esz, "disparity download");
+    s.out(d_corr, has_nxcorr ? corr : nullptr, pix * csz, "corrmap download");
+    s.out(dj.coarse, j.coarse, ppix * esz, "coarse map download");
+    s.out(dj.guide, j.guide, pix * 4, "guide download");
+    s.out(dj.counts, j.counts, 2 * sizeof(uint32_t), "counts download");
+    int rc = s.begin();
     if (!rc)
         rc = match_pyramid_device(e, s0, s1, n, rows, cols, (size_t)cols, pix, depth, cfg,
-                                  has_nxcorr, threshold, range, dj, d_disp, d_corr, st);
-    if (!rc)
-        rc = check_hip(hipMemcpyAsync(disp, d_disp, pix * esz, hipMemcpyDeviceToHost, st),
-                       "disparity download");
-    if (!rc && d_corr)
-        rc = check_hip(hipMemcpyAsync(corr, d_corr, pix * csz, hipMemcpyDeviceToHost, st),
-                       "corrmap download");
-    if (!rc && j.coarse)
-        rc = check_hip(hipMemcpyAsync(j.coarse, dj.coarse, ppix * esz, hipMemcpyDeviceToHost, st),
-                       "coarse map download");
-    if (!rc && j.guide)
-        rc = check_hip(hipMemcpyAsync(j.guide, dj.guide, pix * 4, hipMemcpyDeviceToHost, st),
-                       "guide download");
-    if (!rc && j.counts)
-        rc = check_hip(hipMemcpyAsync(j.counts, dj.counts, 2 * sizeof(uint32_t),
-                                      hipMemcpyDeviceToHost, st), "counts download");
-    const int rc2 = check_hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-    return rc ? rc : rc2;
+                                  has_nxcorr, threshold, range, dj, d_disp, d_corr, s.stream());
+    return s.finish(rc);
 }
 
 }  // namespace bicos_impl
+
