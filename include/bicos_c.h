@@ -315,6 +315,12 @@ int bicos_match_plan(bicos_engine* e, const void* stack0, const void* stack1, in
  * (0 where that launch is not planned); else n is ignored. For tests; no HIP call, e may be
  * NULL. */
 int bicos_search_packed(bicos_engine* e, int rows, int cols, int words, int bits, int n, int fused);
+/* Which of its four matrix products (0-3, 32 bits each) the pruned packed-key search multiplies
+ * bit `bit` (0-127: bit b % 32 of descriptor word b / 32) of a 128-bit descriptor in; -1 for any
+ * other bit. Product 0 is what that search probes a block with, products 0 and 1 together are
+ * words 0 and 1, products 2 and 3 are words 2 and 3. Results do not depend on the map. For tests
+ * and tools; no HIP call. */
+int bicos_search_packed_product(int bit);
 /* Which kernel the agree stage (bicos_agree_device, bicos_agree_stage_device without a step, the
  * agree launch of a match) runs for these stacks: 2 = the left tile staged through LDS with
  * dword loads (stack0's base and both pitches, in bytes, multiples of 4; stack1's base is

@@ -59,7 +59,8 @@ EXPORTS = (
     "bicos_match_device", "bicos_match_device_i16", "bicos_match_host", "bicos_match_host_multi", "bicos_match_bands_device",
     "bicos_desc_pitch", "bicos_transform_device", "bicos_search_device",
     "bicos_agree_device", "bicos_subpixel_device", "bicos_agree_stage_device", "bicos_build_info",
-    "bicos_match_plan", "bicos_search_agree_device", "bicos_search_packed", "bicos_agree_kernel",
+    "bicos_match_plan", "bicos_search_agree_device", "bicos_search_packed", "bicos_search_packed_product",
+    "bicos_agree_kernel",
     "bicos_transform_kernel",
     "bicos_match_device_range", "bicos_match_host_range", "bicos_search_device_range",
     "bicos_reproject_device", "bicos_reproject_host", "bicos_reproject_segment",
@@ -194,6 +195,8 @@ def lib() -> ctypes.CDLL:
     L.bicos_match_plan.restype = I
     L.bicos_search_packed.argtypes = [P, I, I, I, I, I, I]
     L.bicos_search_packed.restype = I
+    L.bicos_search_packed_product.argtypes = [I]
+    L.bicos_search_packed_product.restype = I
     L.bicos_agree_kernel.argtypes = [P, P, I, Z, Z, I]
     L.bicos_agree_kernel.restype = I
     L.bicos_transform_kernel.argtypes = [P, P, I, I, I, Z, Z, I, I, I]

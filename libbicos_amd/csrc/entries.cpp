@@ -7,6 +7,7 @@
 #include "normals.hpp"
 #include "guide.hpp"
 #include "pool.hpp"
+#include "search_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -271,6 +272,10 @@ int bicos_match_plan(bicos_engine* e, const void* stack0, const void* stack1, in
 
 int bicos_search_packed(bicos_engine* e, int rows, int cols, int words, int bits, int n, int fused) {
     return search_runs_packed(e, rows, cols, words, bits, n, fused != 0) ? 1 : 0;
+}
+
+int bicos_search_packed_product(int bit) {
+    return bit >= 0 && bit < 128 ? bicos_hip::pkp_bit_product(bit) : -1;
 }
 
 int bicos_agree_kernel(const void* stack0, const void* stack1, int n, size_t row_pitch,

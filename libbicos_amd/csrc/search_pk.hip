@@ -20,6 +20,7 @@
 //                           the end of a row, for both kernels
 //   search_pk_kernel        1/2/4 words, 1/2/4 wide tiles, tail and list launches, the drop
 //                           branch (pair_step) or lazy drops
+//   pkp_mix                 which 32 descriptor bits each product of the pruned search holds
 //   search_pkp_kernel       the pruned 128-bit search: ST at its staging (raw_col), pruning and
 //                           the fallback at block_pr, EOR at pair_update and its end of row
 //   launch_pk_variant       the instantiations that are built
@@ -38,8 +39,8 @@ constexpr uint32_t LUT_PB = 0x11199199u;  // left: bit 0 -> -0.5 (0x9), 1 -> +0.
 constexpr int PK_SCALE_HI = 127 + 16;     // E8M0 2^16 for the K-half-0 (col0 P) lanes
 constexpr uint32_t PK_PAD = 0x7BFF7BFFu;  // the largest finite f16 in both fields
 // search_pkp_kernel's reach test: thr = R + 33 per field, so that the saturated thr - lb is 0
-// exactly where ham_lo lies above the running minimum (a probe of words 0 and 1); R + 49 where
-// the probe is word 0 alone
+// exactly where ham_lo lies above the running minimum (a probe of products 0 and 1, that is of
+// words 0 and 1); R + 49 where the probe is product 0 alone
 constexpr uint32_t PKP_THR = 0x00210021u;
 constexpr uint32_t PKP_THR1 = 0x00310031u;
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -73,14 +74,16 @@ __device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) {
 // Packed keys and operands. Right A = 1 - 2b in {+1, -1}, left B = -(1 - 2a) / 2 in {-0.5,
 // +0.5} (both exact FP4 e2m1), so one K position contributes -(1 - 2a)(1 - 2b) / 2 and K
 // positions sum to ham - K / 2 (K = 32 WORDS, the zero bits past the used ones included: they
-// add the same -1/2 to every pair). One MFMA multiplies ONE descriptor word: the B lanes of
-// K-half 0 hold word w of col0 P, those of K-half 1 word w of col0 Q = P + 32, and the E8M0
+// add the same -1/2 to every pair). One MFMA multiplies the 32 bits of ONE product -- in
+// search_pk_kernel descriptor word w, in search_pkp_kernel the 32 bits pkp_mix gives product w;
+// any fixed 32 of the descriptor's bit positions do, the same in both operands: the B lanes of
+// K-half 0 hold them of col0 P, those of K-half 1 of col0 Q = P + 32, and the E8M0
 // scale sb of the K-half-0 lanes is 2^16. With C = 2^23 + 2^16 (K/2) + 0x4B00 + K/2 (pk_cb)
 // every D is an integer in [2^23, 2^24) (ulp 1), so
 //     bits(D) = 0x4B000000 + 2^16 ham(P, col1) + 0x4B00 + ham(Q, col1)
 // exactly: the high half is 0x4B00 + ham_P, the low half 0x4B00 + ham_Q, both positive normal
 // f16 values whose order is the order of the distances (ham <= 127 keeps each in 7 bits; the
-// partial sums of the first words stay inside [0, 127] too). WORDS MFMAs cover 32 col1 x 64
+// partial sums of the first products stay inside [0, 127] too). WORDS MFMAs cover 32 col1 x 64
 // col0 pairs: the same matrix-core work per pair as the one-product keys.
 __device__ __forceinline__ v16f mfma_pk(v4i a, v4i b, v16f c, int sb) {
     const v8i a8 = {a[0], a[1], a[2], a[3], 0, 0, 0, 0};
@@ -542,12 +545,40 @@ void search_pk_kernel(typename SearchKArgs<AG>::type ka) {
     }
 }
 
+// The pruned search's four products: e holds the expansions of a descriptor's four words on entry
+// and the operands of its four products on return. Dword m of an expansion holds the bits p of
+// its word with (p mod 8) div 2 == m (expand_bits), and products 0 and 1 take words 0 and 1 by
+// alternate dwords (search_plan.hpp pkp_dword_word): product 0 is {E(w0)[0], E(w1)[1], E(w0)[2],
+// E(w1)[3]}, product 1 {E(w1)[0], E(w0)[1], E(w1)[2], E(w0)[3]}, products 2 and 3 words 2 and 3.
+// Every dword of an expansion is a shift, mask and v_perm of its own, so this chooses which
+// word feeds which dword and adds no instruction. The search is exact for any fixed assignment of
+// descriptor bits to K positions that both operands share (expand_bits); this one is chosen for
+// the one-word probe (block_pr). The bits of a LIMITED word are those of about 8 consecutive
+// image steps and share samples (a < b, a < c, a < mean, the pair sums of steps t and t + 1),
+// so the distance of unrelated pixels over one WORD has a fat lower tail and blocks reach that 32
+// less correlated bits rule out: on the cfg2 frame 18.0 % of wide-tile-blocks with word 0, 11.9 %
+// with this product 0, 11.4 % with the two-word probe (tools/prune_sim.py --mix).
+// Products 0 and 1 together are still exactly words 0 and 1. (The price: rows of slightly noisy
+// descriptors, 2 % of the bits flipped, reach with this product in 68 % of the blocks where word 0
+// reached in 99 %; the window rule keeps such waves at depth 1, and they are slower than they
+// were -- DESIGN.md s5.1, round 17.)
+__device__ __forceinline__ void pkp_mix(v4i (&e)[4]) {
+    v4i o[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int m = 0; m < 4; ++m) o[k][m] = e[pkp_dword_word(k, m)][m];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) e[k] = o[k];
+}
+
 // The pruned 128-bit search: WORDS = 4, one pair of wide tiles per wave, lazy drops, every
-// col0 of the row (no tail, no list), main launches only; a block is probed with word 0, or
-// with words 0 and 1, and the other words are multiplied only where they can matter
-// (block_pr). ST: the right row streamed (raw_col); EOR: a shorter end of row
-// (pair_update, and the end of the kernel). Prologue, lazy step and, without EOR, the end of
-// row are search_pk_kernel<4, 2, false, false, AG, true>'s.
+// col0 of the row (no tail, no list), main launches only; the 128 descriptor bits go to four
+// products of 32 bits each (pkp_mix), a block is probed with product 0, or with products 0
+// and 1, and the other products are multiplied only where they can matter (block_pr). ST: the
+// right row streamed (raw_col); EOR: a shorter end of row (pair_update, and the end of the
+// kernel). Prologue but for pkp_mix, lazy step and, without EOR, the end of row are
+// search_pk_kernel<4, 2, false, false, AG, true>'s.
 template <bool AG, bool ST, bool EOR>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4)))
 void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
@@ -564,9 +595,9 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     const int j = lane & 31;
     const int cols = a.cols;
     // ST: the chunk is PKP_ST_CHUNK (search_plan.hpp: the default geometry's, 8 waves over a 64
-    // KiB stage), a constant of those instantiations so that a block's words 1-3 are read at
+    // KiB stage), a constant of those instantiations so that a block's products 1-3 are read at
     // immediate offsets (16, 32, 48 KiB: the ds_read offset field has 16 bits) from the address
-    // of its word-0 fragment. plan_mx (search_plan.cpp) streams the packed search at that
+    // of its product-0 fragment. plan_mx (search_plan.cpp) streams the packed search at that
     // geometry only; launch_pk_variant refuses a streamed launch with any other.
     const int chunk = ST ? PKP_ST_CHUNK : a.chunk;
     const int waves = blockDim.x >> 6;
@@ -575,10 +606,10 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
     const uint32_t* __restrict__ row0 = a.desc0 + (size_t)row * a.desc_pitch;
     const uint32_t* __restrict__ row1 = a.desc1 + (size_t)row * a.desc_pitch;
 
-    // The block loops name a block by the LDS address of the lane's word-0 fragment of it and
+    // The block loops name a block by the LDS address of the lane's product-0 fragment of it and
     // step that address by a scalar delta (-512 bytes, or back up to the step's last full block
-    // at the wrap); words 1-3 lie 16 chunk bytes apart. frag: the fragment of word w of the
-    // block whose word-0 fragment this lane reads at LDS address ad (ST: at an immediate
+    // at the wrap); products 1-3 lie 16 chunk bytes apart. frag: the fragment of product w of the
+    // block whose product-0 fragment this lane reads at LDS address ad (ST: at an immediate
     // offset). LDS addresses as integers, lds0 the chunk region's: with the region's pointer in
     // the sum the compiler adds its address, 0, to ad at every read.
     typedef const __attribute__((address_space(3))) v4i* lds_frag_ptr;
@@ -603,9 +634,13 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         }
         return x;
     };
-    auto put_col = [&](int c, const v4i& x) {  // LDS column c of the chunk region
+    auto put_col = [&](int c, const v4i& x) {  // LDS column c of the chunk region, by products
+        v4i e[WORDS];
 #pragma unroll
-        for (int w = 0; w < WORDS; ++w) lds_mx[w * chunk + c] = expand_bits((uint32_t)x[w], LUT_PA);
+        for (int w = 0; w < WORDS; ++w) e[w] = expand_bits((uint32_t)x[w], LUT_PA);
+        pkp_mix(e);
+#pragma unroll
+        for (int w = 0; w < WORDS; ++w) lds_mx[w * chunk + c] = e[w];
     };
     const int half = chunk >> 1;
     const int nchunks = (cols + chunk - 1) / chunk;
@@ -619,6 +654,8 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
 
     v4i bf[T][WORDS];
     pk_bfrags<WORDS, T>(bf, row0, c0_wave, lane, cols, [](int i) { return i; });
+#pragma unroll
+    for (int t = 0; t < T; ++t) pkp_mix(bf[t]);  // by products, as put_col's
     const int sb = h ? 127 : PK_SCALE_HI;
     v16f cb = pk_cb<WORDS>();
     // (C kept in VGPRs: left alone the compiler re-copies it from SGPRs every block. Made opaque
@@ -627,7 +664,7 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
 
     // lanes 0-31: tile 0, lanes 32-63: tile 1 -- running minimum, tie marker, block base of
     // the last drop; the reach test's threshold R + thr_off per field (49 at probe depth 1, 33
-    // at depth 2); the fallback's state (wave-uniform): the probe depth in descriptor words,
+    // at depth 2); the fallback's state (wave-uniform): the probe depth in products,
     // from the launch (a.split: 1 or 2), 1 -> 2 -> 0 (the unpruned loop), never back up
     uint32_t R = PK_PAD, M = 0xFFFFFFFFu, C = 0u;
     int depth = a.split == 1 ? 1 : 2;
@@ -714,7 +751,7 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
 
         const int nfull = ncols / 32;
         // (block indices: LDS blocks of the chunk region, the step's first one b0; the loops
-        // name block b by ad, the LDS address of this lane's word-0 fragment of it: lds0 +
+        // name block b by ad, the LDS address of this lane's product-0 fragment of it: lds0 +
         // 16 (32 b + j))
         // a block in full, at col1 B, the step's block bi: the partial last block (pad) and the
         // fallback's loop
@@ -727,16 +764,20 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
             if (pad) pk_pad(dx, dy, bi, ncols, h);
             pair_update(B, pk_tree(dx), pk_tree(dy));
         };
-        // A full block, at col1 B, with words 2 and 3 only for the wide tiles that can reach.
-        // After the MFMAs of words 0 and 1 both fields of every accumulator hold 0x4B00 + 32 +
-        // ham_lo (C carries + 64, each word adds ham_w - 16), and the final field is 0x4B00 +
+        // A full block, at col1 B, with products 2 and 3 only for the wide tiles that can reach.
+        // The four products partition the 128 bit positions into groups of 32 (pkp_mix); ham'_k
+        // is the distance over product k's bits, each in [0, 32], ham = ham'_0 + ham'_1 + ham'_2
+        // + ham'_3, and ham_lo = ham'_0 + ham'_1 is the distance over words 0 and 1, whichever 32
+        // of their bits product 0 holds. Nothing below depends on which bits a product holds.
+        // After the MFMAs of products 0 and 1 both fields of every accumulator hold 0x4B00 + 32 +
+        // ham_lo (C carries + 64, each product adds ham'_k - 16), and the final field is 0x4B00 +
         // ham with ham >= ham_lo. The packed tree of these partial keys, combined over the lane
         // halves as in the pair step, is tested per field against thr = R + 0x00210021 as
         // UNSIGNED 16-BIT INTEGERS (not f16: PK_PAD + 0x21 is a NaN pattern) by one saturating
         // subtraction, thr - key != 0 (v_pk_sub_u16 clamp; neither field of thr wraps: R <=
         // 0x7BFF): reach is ham_lo <= running minimum, "<=" because a tie must never be pruned
         // (NoDuplicates needs it). The decision is per wide tile (the ballot's halves): a tile
-        // none of whose 64 col0 reaches skips its MFMAs of words 2 and 3 and its tree; it
+        // none of whose 64 col0 reaches skips its MFMAs of products 2 and 3 and its tree; it
         // enters the pair step, if the other tile takes one, with its partial keys. That is
         // safe under lazy drops: a pruned tile-block has block minimum > R for every col0, and
         // R only falls, so the block is neither a drop nor a tie now or later; its partial keys
@@ -748,31 +789,35 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         // of 16) send it to the unpruned loop for the rest of the row. (Lazy drops stay under
         // pruning: with the drop branch in the reaching blocks instead of the rescans the fused
         // cfg2 launch took 313.8 instead of 276.2 us.)
-        // Probe depth 1 (D = 1): one scaled MFMA multiplies exactly one descriptor word, so the
-        // block can be tested after word 0 alone. After that MFMA both fields of every
-        // accumulator hold 0x4B00 + 48 + ham_0 (C carries + 64, word 0 adds ham_0 - 16), and
-        // the final field is 0x4B00 + ham with ham >= ham_lo >= ham_0. The packed tree of these
-        // keys, combined over the lane halves, is tested per field against thr = R + 0x00310031
-        // as unsigned 16-bit integers by the same saturating subtraction, thr - key != 0
-        // (neither field of thr wraps: R <= 0x7BFF, and 0x7BFF + 0x31 < 2^16): reach is ham_0
+        // Probe depth 1 (D = 1): one scaled MFMA multiplies the 32 bits of exactly one product,
+        // so the block can be tested after product 0 alone. After that MFMA both fields of every
+        // accumulator hold 0x4B00 + 48 + ham'_0 (C carries + 64, product 0 adds ham'_0 - 16),
+        // and the final field is 0x4B00 + ham with ham >= ham_lo >= ham'_0. The packed tree of
+        // these keys, combined over the lane halves, is tested per field against thr = R +
+        // 0x00310031 as unsigned 16-bit integers by the same saturating subtraction, thr - key !=
+        // 0 (neither field of thr wraps: R <= 0x7BFF, and 0x7BFF + 0x31 < 2^16): reach is ham'_0
         // <= running minimum, "<=" because a tie must never be pruned. A tile none of whose 64
-        // col0 reaches skips its MFMAs of words 1, 2 and 3 and its second tree, and enters the
-        // pair step, if the other tile takes one, with its word-0 keys. That is safe under lazy
-        // drops for the same reason: a tile-block pruned at depth 1 has ham >= ham_0 > R for
-        // every col0 and every column of the block, and R only falls, so the block is neither
-        // a drop nor a tie now or later; its word-0 keys, 0x4B00 + 48 + ham_0, lie above R in
-        // every field too, so all they can give M is a positive value, which never decides
-        // anything. A tile that reaches takes words 1-3 at once and the full tree. The window
-        // rule is the same at both depths: at depth 1 a wave 14 of whose 16 wide-tile-blocks
-        // reach goes on at depth 2 (thr = R + 33) for the rest of the row, and from depth 2 to
-        // the unpruned loop; it never goes back up. Noisy rows so pay one window more than
+        // col0 reaches skips its MFMAs of products 1, 2 and 3 and its second tree, and enters the
+        // pair step, if the other tile takes one, with its product-0 keys. That is safe under
+        // lazy drops for the same reason: a tile-block pruned at depth 1 has ham >= ham'_0 > R
+        // for every col0 and every column of the block, and R only falls, so the block is
+        // neither a drop nor a tie now or later; its product-0 keys, 0x4B00 + 48 + ham'_0, lie
+        // above R in every field too, so all they can give M is a positive value, which never
+        // decides anything. A tile that reaches takes products 1-3 at once and the full tree.
+        // Which 32 bits product 0 holds decides only how often a block reaches: with 16 bits of
+        // each of words 0 and 1 (pkp_mix) a one-product probe prunes nearly like the two-word
+        // one. The window rule is the same at both depths: at depth 1 a wave 14 of whose 16
+        // wide-tile-blocks reach goes on at depth 2 (thr = R + 33) for the rest of the row, and
+        // from depth 2 to the unpruned loop; it never goes back up. Depth 2 tests words 0 and
+        // 1 whole, so its decisions, BICOS_PKP_PROBE=2 and the windows at depth 2 are bit for bit
+        // what they were before the products were mixed. Noisy rows so pay one window more than
         // they did.
-        // af0 holds the block's word-0 fragment on entry and the next block's on return, read
+        // af0 holds the block's product-0 fragment on entry and the next block's on return, read
         // once the probe products are issued; the other words' fragments are read here, at the
         // top of the block, and ad then steps by d bytes to the next block.
         auto block_pr = [&](auto depth_tag, int B, uint32_t& ad, v4i& af0, int d) {
-            constexpr int D = decltype(depth_tag)::value;  // the probe's words
-            // (the words behind the probe read here too: words 2 and 3 read only in the blocks
+            constexpr int D = decltype(depth_tag)::value;  // the probe's products
+            // (the products behind the probe read here too: 2 and 3 read only in the blocks
             // that reach, the fused cfg2 launch took 275.9 instead of 273.5 us at depth 2)
             v4i af[WORDS];
             af[0] = af0;
@@ -822,7 +867,7 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         // full blocks downwards from the one holding the wave's highest col0 (clamped)
         const int sb0 = max(0, min(nfull - 1, (min(cols - 1, c0_wave + 64 * T - 1) - base - 32 * b0) / 32));
         // The visiting order as one carried address: so = 512 x the step's block index (a
-        // block's word-0 fragments are 512 bytes), stepped by -512, or from block 0 back up to
+        // block's product-0 fragments are 512 bytes), stepped by -512, or from block 0 back up to
         // the last full block; ad follows it by the same scalar step. A read never leaves
         // the step's nfull blocks.
         int so = 512 * sb0;
@@ -831,7 +876,7 @@ void search_pkp_kernel(typename SearchKArgs<AG>::type ka) {
         // The pruned loop over the first i0 blocks of the visiting order -- all of them unless
         // a window sends the wave to the unpruned loop below for the rest of the row. Shaped
         // as search_mx_kernel's: an inner run of blocks up to the window's end that only steps
-        // the (wrapping) block offset, the next block's word-0 fragment read unconditionally
+        // the (wrapping) block offset, the next block's product-0 fragment read unconditionally
         // (behind the last block: the wrapped offset, a block nobody uses). The run is at the
         // wave's probe depth; a window that falls at depth 1 goes on here at depth 2
         int i0 = 0;
@@ -1015,8 +1060,8 @@ bool pkp_eor() {
     }();
     return on;
 }
-// search_pkp_kernel's probe depth at the start of a row, in descriptor words (block_pr): 1, or
-// with BICOS_PKP_PROBE=2 the two-word probe from the first block on (read once)
+// search_pkp_kernel's probe depth at the start of a row, in products (block_pr): 1, or with
+// BICOS_PKP_PROBE=2 the two-product probe, words 0 and 1, from the first block on (read once)
 int pkp_probe() {
     static const int depth = [] {
         const char* v = std::getenv("BICOS_PKP_PROBE");

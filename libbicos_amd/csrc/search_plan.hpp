@@ -28,6 +28,20 @@ constexpr int PRUNE_WINDOW = 8;
 // (a tuned engine: 512 with 4 waves over 32 KiB); plan_mx gives the packed search of such a
 // geometry the chunk loop, and launch_pk_variant refuses what it did not plan.
 constexpr int PKP_ST_CHUNK = 1024;
+// Which 32 descriptor bits each of search_pkp_kernel's four products holds (search_pk.hip
+// pkp_mix, block_pr). expand_bits puts the bits p of a word with (p mod 8) div 2 == m into dword
+// m of its expansion; dword m of product k's operands is dword m of the expansion of word
+// pkp_dword_word(k, m): products 0 and 1 take words 0 and 1 by alternate dwords (16 bits of
+// each), products 2 and 3 are words 2 and 3. The one-word probe, product 0, so holds bits of
+// twice as many image steps as a descriptor word does. pkp_bit_product: the product that
+// descriptor bit 0-127 is multiplied in (bicos_search_packed_product, bicos_c.h).
+constexpr int pkp_dword_word(int k, int m) { return k < 2 ? k ^ (m & 1) : k; }
+constexpr int pkp_bit_product(int bit) {
+    const int w = bit >> 5, m = (bit & 7) >> 1;
+    for (int k = 0; k < 4; ++k)
+        if (pkp_dword_word(k, m) == w) return k;
+    return -1;
+}
 
 // Lazy drops of the packed-key search (search_pk.hip lazy_drop). They pay a fixed rescan per
 // col0 (~32 popcounts of WORDS words); the drop branch pays per drop. Narrow rows (few blocks,

@@ -18,8 +18,16 @@ the same window rule (a wave never goes back up). It prints the reach rate per d
 waves that left each depth, and the scaled MFMAs and trees per wave-block that follow (probe
 2 D, + (4 - D) per reaching tile; trees 2, + 1 per reaching tile; unpruned 8 and 2).
 
+--mix K (with --probe-words) chooses which 32 bits each of the kernel's four products holds.
+expand_bits puts the bits p of a word with (p mod 8) div 2 == m into dword m of its expansion;
+product k < K takes dword m from word (k - m) mod K, the products from K on their own word. K = 1:
+a product is a descriptor word (the kernel before the mix); K = 2: the kernel's map
+(search_plan.hpp pkp_dword_word; tests/test_pkp_probe_mix.py holds the two together); K = 3, 4:
+the wider rotations. The probe at depth D is then the first D products.
+
   python tools/prune_sim.py [--rows 0 500 767 1535] [--W 2048] [--flip 0 0.02 0.05 0.1]
                             [--random] [--lo-bits 0] [--fallback] [--probe-words 1] [--window1 8]
+                            [--mix 1]
 """
 import argparse
 import os
@@ -87,6 +95,17 @@ def simulate(C, Clo, cols, unit_tiles, fallback, waves=8, T=4, chunk=1024):
                 want = cols - 1 - np.argmin(c[:, ::-1], axis=1)
                 assert (last[s] == want).all()
     return units, reach, second, nwaves, fell
+
+
+def mix_product(bit, K):
+    """The product (0-3) that holds descriptor bit 0-127 under --mix K"""
+    w, m = bit // 32, (bit % 8) // 2
+    return (w + m) % K if w < K else w
+
+
+def mix_order(K):
+    """The 128 descriptor bit positions, product by product"""
+    return np.array(sorted(range(128), key=lambda b: (mix_product(b, K), b)))
 
 
 def simulate_chain(C, Cw, cols, depth0, window1=PRUNE_WINDOW, waves=8, chunk=1024):
@@ -159,7 +178,11 @@ def main():
     ap.add_argument("--probe-words", type=int, default=0, choices=[0, 1, 2],
                     help="the packed kernel's chain from this probe depth (0: the one-product kernel)")
     ap.add_argument("--window1", type=int, default=PRUNE_WINDOW, help="the chain's window at depth 1, in blocks")
+    ap.add_argument("--mix", type=int, default=1, choices=[1, 2, 3, 4],
+                    help="the packed kernel's products: expansion dwords rotated over the first K words")
     args = ap.parse_args()
+    if args.mix > 1 and (not args.probe_words or args.lo_bits):
+        ap.error("--mix goes with --probe-words and without --lo-bits")
     H = 1536
     for flip in ([0.0] if args.random else args.flip):
         tot = {1: np.zeros(5, np.int64), 2: np.zeros(5, np.int64)}
@@ -177,6 +200,10 @@ def main():
             nb = b0.shape[-1]
             sel = (np.arange(64) + args.lo_bits) % nb
             C = costs(pack(b0), pack(b1))
+            if args.mix > 1:    # (the zero bits past the used ones take their places too)
+                z = np.zeros(b0.shape[:-1] + (128 - nb,), bool)
+                b0, b1 = np.concatenate([b0, z], -1), np.concatenate([b1, z], -1)
+                sel = mix_order(args.mix)
             if args.probe_words:
                 Cw = {d: costs(pack(b0[:, sel[:32 * d]]), pack(b1[:, sel[:32 * d]])) for d in (1, 2)}
                 chain = chain + simulate_chain(C, Cw, args.W, args.probe_words, args.window1)
@@ -186,6 +213,8 @@ def main():
             for ut in (1, 2):
                 tot[ut] += np.array(simulate(C, Clo, args.W, ut, args.fallback))
         name = "random" if args.random else "flip %.2f" % flip
+        if args.mix > 1:
+            name += " mix %d" % args.mix
         if args.probe_words:
             wb, tb, t1, r1, t2, r2, mf, tr, f1, f2, wr = chain
             print("%-10s start depth %d: depth 1 reach %.3f of %d tile-blocks, depth 2 reach %.3f of %d, "
