@@ -731,6 +731,99 @@ int bicos_mesh_host(bicos_engine* e, const void* disparity, int disp_type, int r
 /* Pixels per segment of the mesh's launches: bicos_reproject_segment's (tests). */
 int bicos_mesh_segment(void);
 
+/* -------------------------------------------------------------- projection */
+/* A point list projected into another camera on the GPU: a pixel position, a depth and a class
+ * per point, the value of that camera's image at the point (a texture), and the scan as that
+ * camera sees it: a depth image and an index image registered to its pixel grid, through a
+ * z-buffer that also tells which points a nearer surface hides. The reference has no such step.
+ * Inputs:
+ *     points  float32 [count][3] in the frame of Q (the rectified left camera): the list of
+ *             bicos_reproject_* or bicos_mesh_*, or a dense xyz_map taken as a list, whose NaN
+ *             triples are simply of class invalid. count must fit int32; count == 0 is legal.
+ *     R, t    9 doubles, row-major (NULL = identity) and 3 doubles (NULL = zero): Pc = R*P + t.
+ *     K, D, nd   the rectification section's model and coefficient order: fx = K[0], cx = K[2],
+ *             fy = K[4], cy = K[5], the skew K[1] ignored; nd in {0, 4, 5, 8} doubles
+ *             k1 k2 p1 p2 [k3 [k4 k5 k6]], missing coefficients 0 (D may be NULL with nd = 0).
+ *     img_rows x img_cols   the camera's image size; img_rows*img_cols must fit int32. An empty
+ *             image is legal: every point in front of the camera is then outside.
+ *     splat   0 .. 3: in the z-buffer a point covers the (2*splat+1)^2 pixels around its own,
+ *             clipped to the image.
+ *     tol     a float32 >= 0 and not NaN; +inf is legal and means no occlusion test.
+ *     image   optional, the texture source: u8 (img_depth 1) or u16 (img_depth 2), channels in
+ *             {1, 3} interleaved, element (y, x, k) at base[y*img_pitch + x*channels + k] with
+ *             img_pitch in ELEMENTS, >= img_cols*channels. fill, 0 <= fill <= 255 or 65535: the
+ *             value of every channel of a point that is not visible. With image == NULL,
+ *             img_depth, channels, img_pitch and fill are not looked at.
+ * Per point i. All arithmetic is IEEE double, one rounding per written operation and no
+ * contraction, unless it says float32:
+ *     1. invalid: X, Y or Z is not finite.
+ *     2. Xc = ((R00*X + R01*Y) + R02*Z) + t0, likewise Yc (row 1) and Zc (row 2), X Y Z converted
+ *        to double. behind: !(Zc > 0).
+ *     3. x = Xc/Zc, y = Yc/Zc, then r2, kr, xd, yd exactly as the rectification section writes
+ *        them; u = fx*xd + cx, v = fy*yd + cy; uf = (float)u, vf = (float)v, zf = (float)Zc.
+ *     4. pxf = floorf(uf + 0.5f), pyf = floorf(vf + 0.5f), one float32 addition each: the point's
+ *        own pixel. outside: unless uf and vf are finite and 0 <= pxf < img_cols and
+ *        0 <= pyf < img_rows (float32 compares, the sizes converted to float32). So uf = -0.5 is
+ *        inside and uf = img_cols - 0.5 is outside.
+ *     5. z-buffer: every point that is none of the above offers the key
+ *        ((uint64)bits(zf) << 32) | (uint32)i to each pixel of its splat; a pixel keeps the
+ *        smallest key. zf is a non-negative float, so its bits order as its value does: the
+ *        nearest point wins and equal depths go to the smaller i. The result does not depend on
+ *        the order of arrival: it is deterministic.
+ *     6. zmin = the depth kept at the point's own pixel (which its own splat always covers).
+ *        occluded: !(zf <= zmin + tol), one float32 addition. Otherwise visible.
+ *     7. texture of a visible point, per channel, the remap's arithmetic with the edge replicated:
+ *        x0 = floorf(uf), fx = uf - x0 (one float32 subtraction), the taps at the columns
+ *        clamp(x0, 0, img_cols-1) and clamp(x0+1, 0, img_cols-1); y0, fy and the rows likewise;
+ *        top = p00 + fx*(p01 - p00)   bot = p10 + fx*(p11 - p10)   v = top + fy*(bot - top)
+ *        every operation rounded to float32 on its own, no fma;
+ *        out = (T)min(max(rintf(v), 0), max of the depth)            (ties to even)
+ *        Every other class gets fill in every channel.
+ * Outputs, each optional, at least one required:
+ *     uv         float32 [count][2]: two NaNs for invalid and behind, (uf, vf) for every other
+ *                class, outside included.
+ *     depth      float32 [count]: zf, or NaN for invalid and behind.
+ *     cls        uint8 [count]: BICOS_PROJECT_VISIBLE 0, _OCCLUDED 1, _OUTSIDE 2, _BEHIND 3,
+ *                _INVALID 4.
+ *     tex        [count][channels] of the image's type; requires image.
+ *     depth_map  float32 [img_rows][img_cols]: the kept depth, NaN where no splat fell.
+ *     index_map  int32 [img_rows][img_cols]: the list position of the point that won the pixel,
+ *                -1 where none.
+ *     counts     uint32[5] = {visible, occluded, outside, behind, invalid}, summing to count.
+ *     Every NaN the stage writes is the quiet NaN 0x7FC00000.
+ * The z-buffer is needed only when tol is finite or a map is asked for; its keys, 8 bytes per
+ * pixel, live in the engine's workspace. Otherwise the stage is one launch with no workspace, and
+ * e may be NULL. A point's (uf, vf, zf) is computed again by the launch that needs it, not kept:
+ * the stage has no per-point workspace.
+ * Argument errors are BICOS_E_ARG before any HIP call, and bicos_last_error says which: no
+ * output; tex without image; channels, img_depth, nd, splat, tol or fill out of range; a pitch
+ * shorter than a row; a negative size; count or img_rows*img_cols beyond int32; a nonfinite
+ * camera entry; a NULL points or K with count > 0 (a NULL D with nd > 0); an output overlapping
+ * an input or another output; a NULL engine where the z-buffer is needed. */
+#define BICOS_PROJECT_VISIBLE 0
+#define BICOS_PROJECT_OCCLUDED 1
+#define BICOS_PROJECT_OUTSIDE 2
+#define BICOS_PROJECT_BEHIND 3
+#define BICOS_PROJECT_INVALID 4
+#define BICOS_PROJECT_MAX_SPLAT 3
+/* device: asynchronous on `stream`. */
+int bicos_project_device(bicos_engine* e, const float* points, size_t count, const double* R,
+                         const double* t, const double K[9], const double* D, int nd, int img_rows,
+                         int img_cols, int splat, float tol, const void* image, int img_depth,
+                         int channels, size_t img_pitch, int fill, float* uv, float* depth,
+                         uint8_t* cls, void* tex, float* depth_map, int32_t* index_map,
+                         uint32_t* counts, void* stream);
+/* host buffers, synchronous, e NULL = default engine: uploads the points and the image, runs the
+ * same launches, downloads what was asked for. */
+int bicos_project_host(bicos_engine* e, const float* points, size_t count, const double* R,
+                       const double* t, const double K[9], const double* D, int nd, int img_rows,
+                       int img_cols, int splat, float tol, const void* image, int img_depth,
+                       int channels, size_t img_pitch, int fill, float* uv, float* depth,
+                       uint8_t* cls, void* tex, float* depth_map, int32_t* index_map,
+                       uint32_t counts[5]);
+/* Points per workgroup of the point launches (tests). */
+int bicos_project_group(void);
+
 /* --------------------------------------------------------- disparity guide */
 /* The search restricted to one disparity window PER LEFT PIXEL, from a prior: the previous
  * frame's map of a continuous scan, the match of a downsampled stack, a CAD pose, a

@@ -70,6 +70,7 @@ EXPORTS = (
     "bicos_median_device", "bicos_median_host", "bicos_median_tile",
     "bicos_normals_device", "bicos_normals_host", "bicos_normals_tile",
     "bicos_mesh_device", "bicos_mesh_host", "bicos_mesh_segment",
+    "bicos_project_device", "bicos_project_host", "bicos_project_group",
     "bicos_search_device_guided", "bicos_match_device_guided", "bicos_match_host_guided",
     "bicos_guide_device", "bicos_guide_host",
     "bicos_pool_device", "bicos_pool_host", "bicos_pool_tile", "bicos_pool_kernel",
@@ -103,6 +104,11 @@ NORMALS_MAX_RADIUS = 4
 # bicos_mesh_* flags (include/bicos_c.h): the values of the bicos_reproject_* flags
 MESH_ALLOW_NEGATIVE_Z = 1
 MESH_F32_SENTINEL = 2
+
+# bicos_project_* classes and the largest splat (include/bicos_c.h)
+PROJECT_VISIBLE, PROJECT_OCCLUDED, PROJECT_OUTSIDE, PROJECT_BEHIND, PROJECT_INVALID = range(5)
+PROJECT_CLASSES = ("visible", "occluded", "outside", "behind", "invalid")
+PROJECT_MAX_SPLAT = 3
 
 # bicos_guide_* flag (include/bicos_c.h)
 GUIDE_F32_SENTINEL = 1
@@ -253,6 +259,13 @@ def lib() -> ctypes.CDLL:
     L.bicos_mesh_host.restype = I
     L.bicos_mesh_segment.argtypes = []
     L.bicos_mesh_segment.restype = I
+    project_args = [P, P, Z, PD, PD, PD, PD, I, I, I, I, F, P, I, I, Z, I, P, P, P, P, P, P, P]
+    L.bicos_project_device.argtypes = project_args + [P]
+    L.bicos_project_device.restype = I
+    L.bicos_project_host.argtypes = project_args
+    L.bicos_project_host.restype = I
+    L.bicos_project_group.argtypes = []
+    L.bicos_project_group.restype = I
     L.bicos_search_device_guided.argtypes = [P, P, P, I, I, I, I, I, I, I, P, Z, P, P]
     L.bicos_search_device_guided.restype = I
     L.bicos_match_device_guided.argtypes = [P, P, P, I, I, I, Z, Z, I,
@@ -489,6 +502,62 @@ def mesh_max_diff(max_diff) -> float:
 def mesh_quads(rows: int, cols: int) -> int:
     """(rows - 1) * (cols - 1): the quads of a map, 0 without a second row or column"""
     return 0 if rows < 2 or cols < 2 else (rows - 1) * (cols - 1)
+
+
+def project_camera(K, D=None, R=None, t=None):
+    """One camera as the bicos_project_* entries take it: (R, t, K, D, nd) with ctypes double
+    arrays (R, t and D None for the identity, zero and no distortion). K is 3x3, D None or 0, 4,
+    5 or 8 coefficients, R None or 3x3, t None or 3 values. ValueError for other shapes; the
+    values are checked by the library."""
+    import numpy as np
+
+    def arr(a, name, size, shape=None):
+        a = np.asarray(a, dtype=np.float64)
+        if a.size != size or (shape is not None and a.shape != shape):
+            raise ValueError("%s must have %s, got shape %s"
+                             % (name, "shape %s" % (shape,) if shape else "%d values" % size,
+                                a.shape))
+        return (ctypes.c_double * size)(*a.ravel().tolist())
+
+    k = arr(K, "K", 9, (3, 3))
+    d = np.zeros(0) if D is None else np.asarray(D, dtype=np.float64).ravel()
+    if d.size not in (0, 4, 5, 8):
+        raise ValueError("D must hold 0, 4, 5 or 8 coefficients, got %d" % d.size)
+    dd = (ctypes.c_double * d.size)(*d.tolist()) if d.size else None
+    r = None if R is None else arr(R, "R", 9, (3, 3))
+    tt = None if t is None else arr(t, "t", 3)
+    return r, tt, k, dd, int(d.size)
+
+
+def project_params(size, splat, tol, fill):
+    """(int rows, int cols, int splat, float tol, int fill) as the bicos_project_* entries take
+    them (ValueError for what they would refuse but a fill beyond the image type, which the
+    library sees)."""
+    try:
+        rows, cols = size
+        rows, cols = int(rows), int(cols)
+    except (TypeError, ValueError):
+        raise ValueError("size must be a pair (rows, cols)") from None
+    if rows < 0 or cols < 0 or rows * cols >= 2 ** 31:
+        raise ValueError("size must not be negative, with fewer than 2^31 pixels, got %r"
+                         % (size,))
+    try:
+        s, f, tl = int(splat), int(fill), float(tol)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("splat, tol and fill must be numbers, got %r, %r, %r"
+                         % (splat, tol, fill)) from None
+    if s != splat or not 0 <= s <= PROJECT_MAX_SPLAT:
+        raise ValueError("splat must be an integer 0 .. %d, got %r" % (PROJECT_MAX_SPLAT, splat))
+    if not tl >= 0:
+        raise ValueError("tol must be >= 0 and not NaN, got %r" % (tol,))
+    if f != fill or f < 0:
+        raise ValueError("fill must be a non-negative integer, got %r" % (fill,))
+    return rows, cols, s, tl, f
+
+
+def project_group() -> int:
+    """points per workgroup of the projection's point launches"""
+    return int(lib().bicos_project_group())
 
 
 def normals_params(radius, max_diff, min_points):

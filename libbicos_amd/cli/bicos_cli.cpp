@@ -7,7 +7,8 @@
 //             [-q Q.yml] [--allow-negative-z] [-m MAXDIFF] [--double] [--limited]
 //             [--corrmap] [--no-dupes] [-h]
 // and, beyond the reference: --speckle-size / --speckle-diff, --median / --median-fill,
-// --rectify, --normals / --normals-diff / --normals-min, --mesh / --mesh-diff (see USAGE below).
+// --rectify, --normals / --normals-diff / --normals-min, --mesh / --mesh-diff, --texture /
+// --texture-camera / --texture-tol / --texture-splat (see USAGE below).
 //
 // Same options, defaults and semantics as the reference (FULL transform unless --limited;
 // --threshold <= 0 disables the NXC filter; --corrmap without a threshold computes with
@@ -24,6 +25,7 @@
 #include <cstdlib>
 #include <filesystem>
 #include <iostream>
+#include <limits>
 #include <map>
 #include <optional>
 #include <string>
@@ -78,6 +80,19 @@ const char* USAGE =
     "                          two triangles\n"
     "      --mesh-diff F       a triangle's edge may join disparities that differ by at most F\n"
     "                          (1; only with --mesh)\n"
+    "      --texture IMAGE     with --mesh: colour every vertex with the grey value that IMAGE\n"
+    "                          (PNG or PGM, the picture of the camera of --texture-camera) has\n"
+    "                          where the vertex projects to; the .ply gains red, green and blue\n"
+    "                          per vertex, 0 for a vertex that camera does not see\n"
+    "      --texture-camera FILE  OpenCV FileStorage (YAML/XML) with the 3x3 \"K\" of that camera\n"
+    "                          and optionally \"D\" (0, 4, 5 or 8 coefficients), \"R\" (3x3) and\n"
+    "                          \"T\" (3 values) from the rectified left camera to it; for the\n"
+    "                          rectified left camera itself K is the left 3x3 of P1\n"
+    "      --texture-tol F     also test occlusion: a vertex is not seen where a nearer one lies\n"
+    "                          more than F in depth in front of it on its pixel (default: no\n"
+    "                          test)\n"
+    "      --texture-splat S   each vertex covers (2S+1) x (2S+1) pixels in that test (1; 0..3;\n"
+    "                          only with --texture-tol)\n"
     "      --rectify FILE      the inputs are raw frames: OpenCV FileStorage (YAML/XML) with\n"
     "                          the matrices M1 D1 R1 P1 M2 D2 R2 P2 of cv::stereoRectify;\n"
     "                          both stacks are rectified to their own size before the match.\n"
@@ -106,7 +121,9 @@ Args parse(int argc, char** argv) {
         {"allow-negative-z", false}, {"double", false}, {"limited", false},
         {"corrmap", false}, {"no-dupes", false}, {"speckle-size", true}, {"speckle-diff", true},
         {"rectify", true}, {"median", true}, {"median-fill", true}, {"normals", true},
-        {"normals-diff", true}, {"normals-min", true}, {"mesh", false}, {"mesh-diff", true}};
+        {"normals-diff", true}, {"normals-min", true}, {"mesh", false}, {"mesh-diff", true},
+        {"texture", true}, {"texture-camera", true}, {"texture-tol", true},
+        {"texture-splat", true}};
     Args a;
     for (int i = 1; i < argc; ++i) {
         std::string s = argv[i];
@@ -205,6 +222,40 @@ void rectify_stack(const std::string& file, const std::string& side, std::vector
     stack.swap(out);
 }
 
+// --texture: one grey value per vertex from the picture of another camera (K, D, R, T in `file`),
+// on the GPU (bicos_project_host), as the rgb triples of write_ply_colored
+std::vector<uint8_t> texture_vertices(const Args& args, const float* points, size_t count) {
+    const std::string file = args.val.at("texture-camera");
+    if (!fs::exists(file)) throw std::invalid_argument("'" + file + "' does not exist");
+    bicos_cli::Gray img = bicos_cli::read_gray(args.val.at("texture"), false);
+    const std::vector<double> K = bicos_cli::read_filestorage_matrix(file, "K", 3, 3);
+    const auto D = bicos_cli::find_filestorage_matrix(file, "D");
+    const auto R = bicos_cli::find_filestorage_matrix(file, "R");
+    const auto T = bicos_cli::find_filestorage_matrix(file, "T");
+    if (R && (R->rows != 3 || R->cols != 3)) throw std::runtime_error(file + ": \"R\" is not 3x3");
+    if (T && T->data.size() != 3) throw std::runtime_error(file + ": \"T\" has not 3 values");
+    const bool test = args.has("texture-tol");
+    const float tol = test ? as_float(args, "texture-tol") : std::numeric_limits<float>::infinity();
+    const unsigned splat = args.has("texture-splat") ? as_uint(args, "texture-splat") : 1u;
+    if (splat > BICOS_PROJECT_MAX_SPLAT) throw std::invalid_argument("--texture-splat: S must lie in 0 .. 3");
+    if (!test && args.has("texture-splat"))
+        std::cerr << "'texture-splat' has no effect without 'texture-tol'.\n";
+    std::vector<uint8_t> grey(count + 1);
+    uint32_t counts[5] = {0, 0, 0, 0, 0};  // visible, occluded, outside, behind, invalid
+    if (bicos_project_host(nullptr, points, count, R ? R->data.data() : nullptr,
+                           T ? T->data.data() : nullptr, K.data(),
+                           D && !D->data.empty() ? D->data.data() : nullptr,
+                           D ? (int)D->data.size() : 0, img.rows, img.cols, (int)splat, tol,
+                           img.pixels.data(), 1, 1, (size_t)img.cols, 0, nullptr, nullptr, nullptr,
+                           grey.data(), nullptr, nullptr, counts) != BICOS_OK)
+        throw std::runtime_error(std::string("texture failed: ") + bicos_last_error());
+    std::cout << "Texture:\t" << counts[0] << " vertices seen, " << counts[1] << " occluded, "
+              << counts[2] + counts[3] << " out of view" << std::endl;
+    std::vector<uint8_t> rgb(3 * count + 1);
+    for (size_t i = 0; i < count; ++i) rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = grey[i];
+    return rgb;
+}
+
 int run(int argc, char** argv) {
     const Args args = parse(argc, argv);
     if (args.has("help") || args.pos.empty()) {
@@ -216,6 +267,11 @@ int run(int argc, char** argv) {
     if (!isatty(STDOUT_FILENO)) std::cerr << "Danger: bicos-cli does not have a stable CLI interface\n";
     if (args.has("no-dupes") && !args.has("lr-maxdiff"))
         std::cerr << "'no-dupes' is the default when 'lr-maxdiff' is not set.\n";
+
+    if (args.has("texture") != args.has("texture-camera"))
+        throw std::invalid_argument("--texture and --texture-camera go together");
+    if (args.has("texture") && !fs::exists(args.val.at("texture")))
+        throw std::invalid_argument("'" + args.val.at("texture") + "' does not exist");
 
     const std::string folder0 = args.pos[0];
     const fs::path outfile = args.has("out") ? args.val.at("out") : "bicosdisp.png";
@@ -345,8 +401,14 @@ int run(int argc, char** argv) {
                 throw std::runtime_error(std::string("mesh failed: ") + bicos_last_error());
             fs::path ply = outfile;
             ply.replace_extension("ply");
-            bicos_cli::write_ply(ply.string(), points.data(), counts[0], triangles.data(),
-                                 mesh_counts[0]);
+            if (args.has("texture")) {
+                const std::vector<uint8_t> rgb = texture_vertices(args, points.data(), counts[0]);
+                bicos_cli::write_ply_colored(ply.string(), points.data(), rgb.data(), counts[0],
+                                             triangles.data(), mesh_counts[0]);
+            } else {
+                bicos_cli::write_ply(ply.string(), points.data(), counts[0], triangles.data(),
+                                     mesh_counts[0]);
+            }
             std::cout << "Saved mesh (" << counts[0] << " vertices, " << mesh_counts[0]
                       << " triangles) to\t" << ply << std::endl;
         } else if (bicos_reproject_host(nullptr, disp.data(), disp.type(), disp.rows(),
@@ -388,6 +450,12 @@ int run(int argc, char** argv) {
             if (args.has(k)) std::cerr << "'" << k << "' has no effect without 'normals'.\n";
     if (q_store && !args.has("mesh") && args.has("mesh-diff"))
         std::cerr << "'mesh-diff' has no effect without 'mesh'.\n";
+    if (!(q_store && args.has("mesh")))
+        for (const char* k : {"texture", "texture-tol", "texture-splat"})
+            if (args.has(k)) std::cerr << "'" << k << "' has no effect without 'mesh'.\n";
+    if (q_store && args.has("mesh") && !args.has("texture"))
+        for (const char* k : {"texture-tol", "texture-splat"})
+            if (args.has(k)) std::cerr << "'" << k << "' has no effect without 'texture'.\n";
     return 0;
 }
 

@@ -508,6 +508,37 @@ void write_ply(const std::string& path, const float* points, size_t vertices,
     if (!ply) throw std::runtime_error("cannot write " + path);
 }
 
+void write_ply_colored(const std::string& path, const float* points, const uint8_t* rgb,
+                       size_t vertices, const int32_t* triangles, size_t faces) {
+    std::ofstream ply(path, std::ios::binary);
+    if (!ply) throw std::runtime_error("cannot write " + path);
+    ply << "ply\nformat binary_little_endian 1.0\ncomment bicos-cli\n"
+        << "element vertex " << vertices << "\nproperty float x\nproperty float y\n"
+        << "property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+        << "element face " << faces << "\nproperty list uchar int vertex_indices\nend_header\n";
+    // (the hosts of this engine are little-endian: the records are the arrays' own bytes)
+    std::vector<char> rec(15 * std::min<size_t>(std::max(vertices, faces), 4096));
+    for (size_t v = 0; v < vertices;) {
+        const size_t n = std::min<size_t>(vertices - v, 4096);
+        for (size_t i = 0; i < n; ++i) {
+            std::memcpy(&rec[15 * i], points + 3 * (v + i), 12);
+            std::memcpy(&rec[15 * i + 12], rgb + 3 * (v + i), 3);
+        }
+        ply.write(rec.data(), (std::streamsize)(15 * n));
+        v += n;
+    }
+    for (size_t f = 0; f < faces;) {
+        const size_t n = std::min<size_t>(faces - f, 4096);
+        for (size_t i = 0; i < n; ++i) {
+            rec[13 * i] = 3;
+            std::memcpy(&rec[13 * i + 1], triangles + 3 * (f + i), 12);
+        }
+        ply.write(rec.data(), (std::streamsize)(13 * n));
+        f += n;
+    }
+    if (!ply) throw std::runtime_error("cannot write " + path);
+}
+
 void read_stacks(const std::string& folder0, const std::optional<std::string>& folder1,
                  std::vector<Gray>& left, std::vector<Gray>& right) {
     namespace fs = std::filesystem;

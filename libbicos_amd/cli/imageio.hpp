@@ -86,6 +86,12 @@ void write_xyz_points_normals(const std::string& path, const float* points, cons
 void write_ply(const std::string& path, const float* points, size_t vertices,
                const int32_t* triangles, size_t faces);
 
+// The same file with a colour per vertex: after property float z the header gains property uchar
+// red / green / blue, and every vertex record is three float32 and three bytes; rgb is
+// [vertices][3].
+void write_ply_colored(const std::string& path, const float* points, const uint8_t* rgb,
+                       size_t vertices, const int32_t* triangles, size_t faces);
+
 // reference read_sequence + sort_sequence_to_stack (src/fileutils.cpp:60-154): with two
 // folders, files named <idx>.<ext> in each (16-bit kept); with one, <idx>_left.<ext> and
 // <idx>_right.<ext> (8-bit). Sorted by index.

@@ -8,6 +8,7 @@
 //   BICOS::median_filter  (bicos/median.hpp; no reference counterpart)
 //   BICOS::normals  (bicos/normals.hpp; no reference counterpart)
 //   BICOS::mesh  (bicos/mesh.hpp; likewise)
+//   BICOS::project  (bicos/project.hpp; likewise)
 //   BICOS::guide_from_disparity, the guided BICOS::match  (bicos/guide.hpp; likewise)
 //   BICOS::pool_stack, BICOS::match_pyramid  (bicos/pool.hpp; likewise)
 #include "engine.hpp"
@@ -27,6 +28,7 @@
 #include "../../include/bicos/median.hpp"
 #include "../../include/bicos/normals.hpp"
 #include "../../include/bicos/mesh.hpp"
+#include "../../include/bicos/project.hpp"
 #include "../../include/bicos/guide.hpp"
 #include "../../include/bicos/pool.hpp"
 
@@ -637,6 +639,85 @@ MeshStats mesh(const Image& disparity, const Matx44d& Q, std::vector<float>& poi
     s.quads_half = mesh_counts[2];
     s.quads_empty = mesh_counts[3];
     return s;
+}
+
+// ------------------------------------------------------------------ BICOS::project
+// over the C entries (entries.cpp), which validate, lock the engine and launch
+
+namespace {
+// The texture source as the entries take it: depth in bytes, pitch in elements
+struct ImageArgs {
+    const void* data = nullptr;
+    int depth = 1, channels = 1;
+    size_t pitch = 0;
+};
+ImageArgs image_args(const ProjectImage& image, const Camera& cam, Memory mem) {
+    ImageArgs a;
+    if (!image.image) return a;
+    const Image& im = *image.image;
+    if (im.type() != U8 && im.type() != U16) throw Exception("project: the image must be U8 or U16");
+    if (image.channels != 1 && image.channels != 3)
+        throw Exception("project: channels must be 1 or 3");
+    if (im.rows() != cam.rows || (int64_t)im.cols() != (int64_t)cam.cols * image.channels)
+        throw Exception("project: the image must be cam.rows x channels * cam.cols");
+    if (im.memory() != mem)
+        throw Exception("project: the image must be in the memory of the points");
+    if (im.step() % im.elemSize()) throw Exception("project: the image's step splits an element");
+    a.data = im.data();
+    a.depth = (int)im.elemSize();
+    a.channels = image.channels;
+    a.pitch = im.step() / im.elemSize();
+    return a;
+}
+void check_camera(const Camera& cam) {
+    const size_t nd = cam.D.size();
+    if (nd != 0 && nd != 4 && nd != 5 && nd != 8)
+        throw Exception("project: D must hold 0, 4, 5 or 8 coefficients");
+}
+}  // namespace
+
+void project(const float* points, size_t count, const Camera& cam, const ProjectDeviceOutputs& out,
+             const ProjectParams& params, const ProjectImage& image, hipStream_t stream) {
+    check_camera(cam);
+    const ImageArgs im = image_args(image, cam, Memory::Device);
+    throw_rc(bicos_project_device(
+        current_engine(), points, count, cam.R.data(), cam.T.data(), cam.K.data(),
+        cam.D.empty() ? nullptr : cam.D.data(), (int)cam.D.size(), cam.rows, cam.cols, params.splat,
+        params.tol, im.data, im.depth, im.channels, im.pitch, params.fill, out.uv, out.depth,
+        out.cls, out.tex, out.depth_map, out.index_map, out.counts, stream));
+}
+
+ProjectStats project(const float* points, size_t count, const Camera& cam,
+                     const ProjectHostOutputs& out, const ProjectParams& params,
+                     const ProjectImage& image) {
+    check_camera(cam);
+    const ImageArgs im = image_args(image, cam, Memory::Host);
+    if (out.tex && !im.data) throw Exception("project: tex without image");
+    const size_t pixels = (size_t)(cam.rows > 0 ? cam.rows : 0) * (size_t)(cam.cols > 0 ? cam.cols : 0);
+    // (+1: never a null pointer)
+    if (out.uv) out.uv->resize(2 * count + 1);
+    if (out.depth) out.depth->resize(count + 1);
+    if (out.cls) out.cls->resize(count + 1);
+    if (out.tex) out.tex->resize(count * im.channels * im.depth + 1);
+    if (out.depth_map) out.depth_map->resize(pixels + 1);
+    if (out.index_map) out.index_map->resize(pixels + 1);
+    uint32_t counts[5] = {0, 0, 0, 0, 0};
+    const int rc = bicos_project_host(
+        nullptr, points, count, cam.R.data(), cam.T.data(), cam.K.data(),
+        cam.D.empty() ? nullptr : cam.D.data(), (int)cam.D.size(), cam.rows, cam.cols, params.splat,
+        params.tol, im.data, im.depth, im.channels, im.pitch, params.fill,
+        out.uv ? out.uv->data() : nullptr, out.depth ? out.depth->data() : nullptr,
+        out.cls ? out.cls->data() : nullptr, out.tex ? (void*)out.tex->data() : nullptr,
+        out.depth_map ? out.depth_map->data() : nullptr,
+        out.index_map ? out.index_map->data() : nullptr, counts);
+    if (out.uv) out.uv->resize(2 * count);
+    if (out.depth) out.depth->resize(count);
+    if (out.cls) out.cls->resize(count);
+    if (out.tex) out.tex->resize(count * im.channels * im.depth);
+    if (out.depth_map) out.depth_map->resize(pixels);
+    if (out.index_map) out.index_map->resize(pixels);
+    throw_rc(rc);
+    return ProjectStats{counts[0], counts[1], counts[2], counts[3], counts[4]};
 }
 
 // ------------------------------------------------------ BICOS::guide_from_disparity

@@ -10,6 +10,7 @@
 #include "median.hpp"
 #include "normals.hpp"
 #include "mesh.hpp"
+#include "project.hpp"
 #include "guide.hpp"
 #include "pool.hpp"
 
@@ -900,6 +901,116 @@ int mesh_device(bicos_engine* e, const MeshJob& j, hipStream_t st) {
     if (int rc = ws.acquire()) return rc;
     carve();
     return check_hip(bicos_hip::launch_mesh(a, j.disp_type == BICOS_CV_32F, st), "mesh launches");
+}
+
+// ---------------------------------------------------------------- projection
+
+int check_project(const ProjectJob& j, const bicos_engine* e, bool needs_engine) {
+    if (!j.uv && !j.depth && !j.cls && !j.tex && !j.depth_map && !j.index_map && !j.counts)
+        return fail(BICOS_E_ARG, "project: no output");
+    if (j.tex && !j.image) return fail(BICOS_E_ARG, "project: tex without image");
+    if (j.image) {
+        if (j.channels != 1 && j.channels != 3)
+            return fail(BICOS_E_ARG, "project: channels must be 1 or 3");
+        if (j.img_depth != 1 && j.img_depth != 2)
+            return fail(BICOS_E_ARG, "project: img_depth must be 1 (u8) or 2 (u16)");
+    }
+    if (j.nd != 0 && j.nd != 4 && j.nd != 5 && j.nd != 8)
+        return fail(BICOS_E_ARG, "project: nd must be 0, 4, 5 or 8");
+    if (j.splat < 0 || j.splat > BICOS_PROJECT_MAX_SPLAT)
+        return fail(BICOS_E_ARG, "project: splat must be 0 .. 3");
+    if (!(j.tol >= 0.0f)) return fail(BICOS_E_ARG, "project: tol must be >= 0 and not NaN");
+    if (j.image && (j.fill < 0 || j.fill > (j.img_depth == 1 ? 255 : 65535)))
+        return fail(BICOS_E_ARG, "project: fill out of the image type's range");
+    if (int rc0 = check_map_size("project", j.img_rows, j.img_cols)) return rc0;
+    if (j.image && j.img_pitch < (size_t)j.img_cols * j.channels)
+        return fail(BICOS_E_ARG, "project: img_pitch is shorter than a row");
+    if (j.count > (size_t)INT32_MAX) return fail(BICOS_E_ARG, "project: count exceeds int32");
+    if (j.count > 0 && !j.points) return fail(BICOS_E_ARG, "project: null points");
+    if (j.count > 0 && !j.K) return fail(BICOS_E_ARG, "project: null K");
+    if (j.nd > 0 && !j.D) return fail(BICOS_E_ARG, "project: null D");
+    bool finite = true;
+    for (int i = 0; j.K && i < 9; ++i) finite = finite && std::isfinite(j.K[i]);
+    for (int i = 0; i < j.nd; ++i) finite = finite && std::isfinite(j.D[i]);
+    for (int i = 0; j.R && i < 9; ++i) finite = finite && std::isfinite(j.R[i]);
+    for (int i = 0; j.t && i < 3; ++i) finite = finite && std::isfinite(j.t[i]);
+    if (!finite) return fail(BICOS_E_ARG, "project: a camera value is not finite");
+    // the inputs, then every output with the bytes the call may write
+    const uintptr_t n = (uintptr_t)j.count, pixels = (uintptr_t)j.img_rows * j.img_cols;
+    const uintptr_t esz = (uintptr_t)j.img_depth, ch = (uintptr_t)j.channels;
+    const uintptr_t img_bytes =
+        j.image && pixels ? ((uintptr_t)(j.img_rows - 1) * j.img_pitch + j.img_cols * ch) * esz : 0;
+    const struct {
+        const void* p;
+        uintptr_t bytes;
+        const char* name;
+    } span[] = {{j.points, n * 12, "points"},
+                {j.image, img_bytes, "image"},
+                {j.uv, n * 8, "uv"},
+                {j.depth, n * 4, "depth"},
+                {j.cls, n, "cls"},
+                {j.tex, j.image ? n * ch * esz : 0, "tex"},
+                {j.depth_map, pixels * 4, "depth_map"},
+                {j.index_map, pixels * 4, "index_map"},
+                {j.counts, 5 * sizeof(uint32_t), "counts"}};
+    const int spans = (int)(sizeof span / sizeof span[0]);
+    for (int i = 2; i < spans; ++i)
+        for (int k = 0; k < i; ++k)
+            if (overlaps(span[i].p, span[i].bytes, span[k].p, span[k].bytes))
+                return fail(BICOS_E_ARG, std::string("project: ") + span[i].name + " overlaps " +
+                                             span[k].name);
+    if (needs_engine && !e && j.zbuffer())
+        return fail(BICOS_E_ARG, "project: null engine (the z-buffer's workspace)");
+    return BICOS_OK;
+}
+
+int project_device(bicos_engine* e, const ProjectJob& j, hipStream_t st) {
+    bicos_hip::ProjectArgs a{};
+    static const double identity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    std::copy(j.R ? j.R : identity, (j.R ? j.R : identity) + 9, a.cam.R);
+    for (int i = 0; i < 3; ++i) a.cam.t[i] = j.t ? j.t[i] : 0.0;
+    if (j.K) {  // (NULL only with count == 0: no point kernel runs)
+        a.cam.fx = j.K[0];
+        a.cam.cx = j.K[2];
+        a.cam.fy = j.K[4];
+        a.cam.cy = j.K[5];
+    }
+    const auto d = [&](int i) { return i < j.nd ? j.D[i] : 0.0; };
+    a.cam.k1 = d(0);
+    a.cam.k2 = d(1);
+    a.cam.p1 = d(2);
+    a.cam.p2 = d(3);
+    a.cam.k3 = d(4);
+    a.cam.k4 = d(5);
+    a.cam.k5 = d(6);
+    a.cam.k6 = d(7);
+    a.points = j.points;
+    a.count = (uint32_t)j.count;
+    a.img_rows = j.img_rows;
+    a.img_cols = j.img_cols;
+    a.splat = j.splat;
+    a.tol = j.tol;
+    a.image = j.image;
+    a.depth = j.img_depth;
+    a.channels = j.channels;
+    a.img_pitch = j.img_pitch;
+    a.fill = (uint32_t)j.fill;
+    a.uv = j.uv;
+    a.zdepth = j.depth;
+    a.cls = j.cls;
+    a.tex = j.tex;
+    a.depth_map = j.depth_map;
+    a.index_map = j.index_map;
+    a.counts = j.counts;
+    if (!j.zbuffer())
+        return check_hip(bicos_hip::launch_project(a, st), "project launches");
+    const size_t pixels = (size_t)j.img_rows * j.img_cols;
+    Lease ws(e, e->ws, e->ws_bytes, st);
+    auto carve = [&] { a.keys = ws.take<unsigned long long>(std::max<size_t>(pixels, 1)); };
+    carve();
+    if (int rc = ws.acquire()) return rc;
+    carve();
+    return check_hip(bicos_hip::launch_project(a, st), "project launches");
 }
 
 // ------------------------------------------------------------ disparity guide

@@ -10,21 +10,23 @@
 //               rectify_maps_device (raw stacks -> rectified stacks); median_device (the
 //               median filter of a disparity map); normals_device (a disparity map -> unit
 //               surface normals); mesh_device (a disparity map -> a triangle mesh over the
-//               reprojection's point list); guide_device (a prior disparity map ->
-//               per-pixel search windows); pool_device (a stack pooled by an integer factor);
+//               reprojection's point list); project_device (a point list -> another camera's
+//               pixels, visibility, texture and registered depth); guide_device (a prior
+//               disparity map -> per-pixel search windows); pool_device (a stack pooled by an integer factor);
 //               match_pyramid_device (pool, coarse ranged match, guide, guided match)
 //   host.cpp    the banded host-buffer pipeline (HostPool, match_host); the staged host call
-//               (Staging) and the ten paths on it: reproject_host; speckle_host; rectify_host,
-//               rectify_maps_host; median_host; normals_host; mesh_host; guide_host; pool_host;
-//               match_pyramid_host
+//               (Staging) and the eleven paths on it: reproject_host; speckle_host; rectify_host,
+//               rectify_maps_host; median_host; normals_host; mesh_host; project_host; guide_host;
+//               pool_host; match_pyramid_host
 //   entries.cpp the bicos_* extern "C" entries (bicos_c.h) but the multi-GPU ones
 //   multi.cpp   bicos_match_host_multi, bicos_match_bands_device
 //   cxxapi.cpp  namespace BICOS (HipImage, match, reproject, filter_speckles, median_filter,
-//               normals, mesh, guide_from_disparity, pool_stack, match_pyramid)
+//               normals, mesh, project, guide_from_disparity, pool_stack, match_pyramid)
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <condition_variable>
 #include <exception>
 #include <functional>
@@ -583,6 +585,44 @@ int mesh_device(bicos_engine* e, const MeshJob& j, hipStream_t st);
 // min(triangles, tri_capacity) triangles. Synchronous.
 // rows * cols > 0 (bicos_mesh_host answers an empty map itself, without an engine).
 int mesh_host(bicos_engine* e, const MeshJob& j);
+
+// One projection (bicos_c.h "projection"): the arguments of bicos_project_device /
+// bicos_project_host, the pointers all in device or all in host memory (the camera always in
+// host memory).
+struct ProjectJob {
+    const float* points;
+    size_t count;
+    const double* R;
+    const double* t;
+    const double* K;
+    const double* D;
+    int nd, img_rows, img_cols, splat;
+    float tol;
+    const void* image;
+    int img_depth, channels;
+    size_t img_pitch;
+    int fill;
+    float* uv;
+    float* depth;
+    uint8_t* cls;
+    void* tex;
+    float* depth_map;
+    int32_t* index_map;
+    uint32_t* counts;
+    // the z-buffer is needed: tol is finite or a map is asked for
+    bool zbuffer() const { return tol < INFINITY || depth_map || index_map; }
+};
+// BICOS_E_ARG (with a message) for what the entries refuse; no HIP call. needs_engine: a NULL
+// engine is an error where the z-buffer is needed (the device entry; the host entry has a
+// default engine).
+int check_project(const ProjectJob& j, const bicos_engine* e, bool needs_engine);
+// The launches on `st` (validated arguments), the z-buffer's keys in the engine's workspace; e
+// may be NULL where no z-buffer is needed.
+int project_device(bicos_engine* e, const ProjectJob& j, hipStream_t st);
+// Host buffers: the points and the image (its rows made dense) uploaded into the engine's
+// staging, the same launches on the engine's own stream, every output asked for downloaded.
+// Synchronous.
+int project_host(bicos_engine* e, const ProjectJob& j);
 
 // One remap of a stack (bicos_c.h "rectification"): the arguments of bicos_rectify_device, the
 // pointers all in device memory, the stack pitches in elements, map_pitch in bytes (0 = dense).

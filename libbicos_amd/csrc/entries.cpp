@@ -5,6 +5,7 @@
 #include "speckle.hpp"
 #include "median.hpp"
 #include "normals.hpp"
+#include "project.hpp"
 #include "guide.hpp"
 #include "pool.hpp"
 #include "search_plan.hpp"
@@ -498,6 +499,39 @@ int bicos_mesh_host(bicos_engine* e, const void* disparity, int disp_type, int r
 }
 
 int bicos_mesh_segment(void) { return bicos_hip::REPROJECT_SEGMENT; }
+
+int bicos_project_device(bicos_engine* e, const float* points, size_t count, const double* R,
+                         const double* t, const double K[9], const double* D, int nd, int img_rows,
+                         int img_cols, int splat, float tol, const void* image, int img_depth,
+                         int channels, size_t img_pitch, int fill, float* uv, float* depth,
+                         uint8_t* cls, void* tex, float* depth_map, int32_t* index_map,
+                         uint32_t* counts, void* stream) {
+    const ProjectJob job{points, count, R, t, K, D, nd, img_rows, img_cols, splat, tol, image,
+                         img_depth, channels, img_pitch, fill, uv, depth, cls, tex, depth_map,
+                         index_map, counts};
+    if (int rc0 = check_project(job, e, true)) return rc0;
+    hipStream_t st = (hipStream_t)stream;
+    // (no z-buffer: one launch, no workspace, nothing of an engine)
+    if (!e) return guarded([&]() -> int { return project_device(nullptr, job, st); });
+    return with_engine(e, [&](bicos_engine* e) { return project_device(e, job, st); });
+}
+
+int bicos_project_host(bicos_engine* e, const float* points, size_t count, const double* R,
+                       const double* t, const double K[9], const double* D, int nd, int img_rows,
+                       int img_cols, int splat, float tol, const void* image, int img_depth,
+                       int channels, size_t img_pitch, int fill, float* uv, float* depth,
+                       uint8_t* cls, void* tex, float* depth_map, int32_t* index_map,
+                       uint32_t counts[5]) {
+    const ProjectJob job{points, count, R, t, K, D, nd, img_rows, img_cols, splat, tol, image,
+                         img_depth, channels, img_pitch, fill, uv, depth, cls, tex, depth_map,
+                         index_map, counts};
+    if (int rc0 = check_project(job, e, false)) return rc0;
+    return with_default_engine(e, [&](bicos_engine* e) { return project_host(e, job); });
+}
+
+int bicos_project_group(void) {
+    return bicos_hip::PROJECT_THREADS * bicos_hip::PROJECT_PER_LANE;
+}
 
 int bicos_speckle_device(bicos_engine* e, const void* disparity, int disp_type, int rows, int cols,
                          int max_size, float max_diff, int flags, void* out, int32_t* labels,

@@ -515,6 +515,32 @@ int mesh_host(bicos_engine* e, const MeshJob& j) {
     return s.finish(rc);
 }
 
+int project_host(bicos_engine* e, const ProjectJob& j) {
+    const size_t n = j.count, pixels = (size_t)j.img_rows * j.img_cols;
+    ProjectJob d = j;
+    Staging s(e);
+    // (a zero-length list still gets a buffer of its own: the launches take pointers)
+    const int pts = s.buffer(d.points, std::max<size_t>(n * 12, 4));
+    if (n) s.up(pts, 0, j.points, n * 12, "points upload");
+    if (j.image) {  // the rows made dense
+        const size_t esz = (size_t)j.img_depth, row = (size_t)j.img_cols * j.channels * esz;
+        const int img = s.buffer(d.image, std::max<size_t>(pixels * j.channels * esz, 4));
+        if (pixels)
+            s.up2d(img, 0, j.image, j.img_pitch * esz, row, (size_t)j.img_rows, "image upload");
+        d.img_pitch = (size_t)j.img_cols * j.channels;
+        s.out(d.tex, j.tex, n * j.channels * esz, "tex download");
+    }
+    s.out(d.uv, j.uv, n * 8, "uv download");
+    s.out(d.depth, j.depth, n * 4, "depth download");
+    s.out(d.cls, j.cls, n, "cls download");
+    s.out(d.depth_map, j.depth_map, pixels * 4, "depth_map download");
+    s.out(d.index_map, j.index_map, pixels * 4, "index_map download");
+    s.out(d.counts, j.counts, 5 * sizeof(uint32_t), "counts download");
+    int rc = s.begin();
+    if (!rc) rc = project_device(e, d, s.stream());
+    return s.finish(rc);
+}
+
 int speckle_host(bicos_engine* e, const SpeckleJob& j) {
     const size_t pixels = (size_t)j.rows * j.cols;
     if (pixels == 0) {

@@ -650,6 +650,102 @@ class Engine:
         return out_points[:kept], out_triangles[:tris], \
             (index[:kept] if index is not None else None), vmap, stats
 
+    # -------------------------------------------------------------- projection
+    PROJECT_OUTPUTS = ("uv", "depth", "cls", "tex", "depth_map", "index_map", "counts")
+
+    def project(self, points: torch.Tensor, K, size=None, *, D=None, R=None, t=None,
+                splat: int = 0, tol: float = float("inf"),
+                image: Optional[torch.Tensor] = None, fill: int = 0,
+                outputs: Optional[Sequence[str]] = None, out: Optional[dict] = None,
+                stream=None) -> dict:
+        """bicos_project_device: float32 points [count, 3] in the frame of Q (reproject_points',
+        mesh's, or a dense xyz map reshaped to a list) projected into the camera Pc = R*P + t,
+        K, D with an image of size = (rows, cols); include/bicos_c.h, "projection". Returns a
+        dict of tensors, the `outputs` asked for among
+            uv [count, 2] float32, depth [count] float32, cls [count] uint8 (0 visible,
+            1 occluded, 2 outside, 3 behind, 4 invalid), tex [count, channels] of the image's
+            dtype, depth_map / index_map [rows, cols] float32 / int32 (the scan as that camera
+            sees it: the nearest depth and its point's position per pixel, NaN / -1 where none),
+            counts int32 [5] = visible, occluded, outside, behind, invalid.
+        The default is uv, depth, cls and, with an image, tex. `image`: uint8 or uint16
+        [rows, cols] or [rows, cols, 3] on the device, the pixels contiguous, any row stride;
+        `size` defaults to its shape. A point covers (2*splat+1)^2 pixels of the z-buffer; it is
+        occluded where !(depth <= nearest depth at its pixel + tol); tol = inf (the default) with
+        no map asked for runs no z-buffer at all. `out`: a dict of caller-provided tensors by the
+        same names, written in place and returned. Asynchronous on `stream`; nothing is
+        synchronised."""
+        if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or \
+                points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be a float32 tensor [count, 3]")
+        if not points.is_contiguous():
+            raise ValueError("points must be contiguous")
+        dev = points.device
+        count = points.shape[0]
+        ptr, depth, channels, pitch = None, 1, 1, 0
+        if image is not None:
+            if not isinstance(image, torch.Tensor) or image.dtype not in (torch.uint8, torch.uint16):
+                raise ValueError("image must be a uint8 or uint16 tensor")
+            if image.device != dev:
+                raise ValueError("image must be on %s, got %s" % (dev, image.device))
+            if image.dim() not in (2, 3) or (image.dim() == 3 and image.shape[2] not in (1, 3)):
+                raise ValueError("image must be [rows, cols] or [rows, cols, 3]")
+            channels = image.shape[2] if image.dim() == 3 else 1
+            if size is None:
+                size = tuple(image.shape[:2])
+            if tuple(image.shape[:2]) != tuple(size):
+                raise ValueError("image must have the camera's size %s" % (tuple(size),))
+            rows_i, cols_i = image.shape[:2]
+            if image.dim() == 3 and cols_i > 0 and channels > 1 and image.stride(2) != 1:
+                raise ValueError("image channels must be interleaved")
+            if cols_i > 1 and image.stride(1) != channels:
+                raise ValueError("image pixels must be contiguous along a row")
+            pitch = cols_i * channels
+            if rows_i > 1:
+                if image.stride(0) < pitch:
+                    raise ValueError("image row stride must be >= a row")
+                pitch = image.stride(0)
+            depth = image.element_size()
+            ptr = image.data_ptr() if rows_i * cols_i else None
+        if size is None:
+            raise ValueError("size = (rows, cols) is required without an image")
+        rows, cols, splat, tol, fill = _lib.project_params(size, splat, tol, fill)
+        r, tt, k, d, nd = _lib.project_camera(K, D, R, t)
+        out = dict(out) if out else {}
+        if outputs is None:
+            outputs = () if out else ("uv", "depth", "cls") + (("tex",) if image is not None else ())
+        names = [n for n in self.PROJECT_OUTPUTS if n in outputs or n in out]
+        unknown = [n for n in list(outputs) + list(out) if n not in self.PROJECT_OUTPUTS]
+        if unknown:
+            raise ValueError("unknown outputs %r (of %r)" % (unknown, self.PROJECT_OUTPUTS))
+        if not names:
+            raise ValueError("at least one output is required")
+        if "tex" in names and image is None:
+            raise ValueError("tex requires an image")
+        spec = {"uv": ((count, 2), torch.float32), "depth": ((count,), torch.float32),
+                "cls": ((count,), torch.uint8),
+                "tex": ((count, channels), image.dtype if image is not None else torch.uint8),
+                "depth_map": ((rows, cols), torch.float32),
+                "index_map": ((rows, cols), torch.int32), "counts": ((5,), torch.int32)}
+        res = {}
+        for n in names:
+            shape, dtype = spec[n]
+            if n in out:
+                _check_out(out[n], n, shape, (dtype,), dev)
+                res[n] = out[n]
+            else:
+                res[n] = torch.empty(shape, dtype=dtype, device=dev)
+
+        def p(n):  # (an empty tensor has no pointer to hand over; it is not written either)
+            return res[n].data_ptr() if n in res and res[n].numel() else None
+        args = [p(n) for n in self.PROJECT_OUTPUTS]
+        if all(a is None for a in args):  # nothing but empty outputs: nothing to do
+            return res
+        rc = self._L.bicos_project_device(
+            self._h, points.data_ptr() if count else None, count, r, tt, k, d, nd, rows, cols,
+            splat, tol, ptr, depth, channels, pitch, fill, *args, _stream(dev, stream))
+        _lib.check(rc, "bicos_project_device")
+        return res
+
     # --------------------------------------------------------- disparity guide
     def guide_from_disparity(self, prior: torch.Tensor, radius: int, spread: int = 0,
                              scale: int = 1, fallback: Optional[Tuple[int, int]] = None,

@@ -369,6 +369,70 @@ def mesh(disparity, Q, max_diff=1.0, allow_negative_z=False, sentinel=True):
     return points[:counts[0]].copy(), triangles[:mesh_counts[0]].copy()
 
 
+PROJECT_OUTPUTS = ("uv", "depth", "cls", "tex", "depth_map", "index_map", "counts")
+
+
+def project(points, K, size=None, D=None, R=None, t=None, splat=0, tol=float("inf"), image=None,
+            fill=0, outputs=None):
+    """An extension (the reference has no such step): float32 points [count, 3] in the frame of
+    Q -- reproject()'s or mesh()'s list, or an xyz map reshaped to one -- projected into the
+    camera Pc = R*P + t, K, D with an image of size = (rows, cols) (bicos_project_host,
+    include/bicos_c.h "projection": on the GPU, exact). Returns a dict of the `outputs` asked
+    for among uv [count, 2] float32, depth [count] float32, cls [count] uint8 (0 visible,
+    1 occluded, 2 outside, 3 behind, 4 invalid), tex [count, channels] of the image's dtype,
+    depth_map / index_map [rows, cols] float32 / int32 and counts uint32 [5]; the default is
+    uv, depth, cls, counts and, with an image, tex. `image`: uint8 or uint16, [rows, cols] or
+    [rows, cols, 3]; `size` defaults to its shape. A point covers (2*splat+1)^2 pixels of the
+    z-buffer and is occluded where !(depth <= nearest depth at its pixel + tol)."""
+    pts = np.ascontiguousarray(points)
+    if pts.dtype != np.float32 or pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("points must be a float32 array [count, 3]")
+    count = pts.shape[0]
+    img, depth, channels, pitch = None, 1, 1, 0
+    if image is not None:
+        img = np.ascontiguousarray(image)
+        if img.dtype != np.uint8 and img.dtype != np.uint16:
+            raise ValueError(f"Unsupported image dtype: {img.dtype}")
+        if img.ndim not in (2, 3) or (img.ndim == 3 and img.shape[2] not in (1, 3)):
+            raise ValueError("image must be [rows, cols] or [rows, cols, 3]")
+        channels = img.shape[2] if img.ndim == 3 else 1
+        if size is None:
+            size = img.shape[:2]
+        if tuple(img.shape[:2]) != tuple(size):
+            raise ValueError("image must have the camera's size %s" % (tuple(size),))
+        depth, pitch = img.itemsize, img.shape[1] * channels
+    if size is None:
+        raise ValueError("size = (rows, cols) is required without an image")
+    rows, cols, splat, tol, fill = _lib.project_params(size, splat, tol, fill)
+    r, tt, k, d, nd = _lib.project_camera(K, D, R, t)
+    if outputs is None:
+        outputs = ("uv", "depth", "cls", "counts") + (("tex",) if img is not None else ())
+    unknown = [n for n in outputs if n not in PROJECT_OUTPUTS]
+    if unknown:
+        raise ValueError("unknown outputs %r (of %r)" % (unknown, PROJECT_OUTPUTS))
+    if "tex" in outputs and img is None:
+        raise ValueError("tex requires an image")
+    spec = {"uv": ((count, 2), np.float32), "depth": ((count,), np.float32),
+            "cls": ((count,), np.uint8),
+            "tex": ((count, channels), img.dtype if img is not None else np.uint8),
+            "depth_map": ((rows, cols), np.float32), "index_map": ((rows, cols), np.int32),
+            "counts": ((5,), np.uint32)}
+    res = {n: np.empty(*spec[n]) for n in PROJECT_OUTPUTS if n in outputs}
+    if not res:
+        raise ValueError("at least one output is required")
+    args = [res[n].ctypes.data if n in res and res[n].size else None for n in PROJECT_OUTPUTS]
+    if all(a is None for a in args):  # nothing but empty outputs: nothing to do
+        return res
+    L = _lib.lib()
+    rc = L.bicos_project_host(None, pts.ctypes.data if count else None, count, r, tt, k, d, nd,
+                              rows, cols, splat, tol,
+                              img.ctypes.data if img is not None and img.size else None, depth,
+                              channels, pitch, fill, *args)
+    if rc != 0:
+        raise RuntimeError("BICOS project failed: " + L.bicos_last_error().decode(errors="replace"))
+    return res
+
+
 def filter_speckles(disparity, max_size, max_diff=1.0, sentinel=True):
     """An extension (the reference has no such step; cv2.filterSpeckles is the CPU
     counterpart): removes from a disparity map of match() -- int16 or float32, [rows, cols] --
